@@ -14,9 +14,13 @@ data-path collective ("weak" scaling); the only exchange is the max-over-ranks o
 
 `value` is measured into the FIRST output allocation the process gets -- what a rosdyn::Chain caller has.  The speed of the
 stacked store pattern depends on the physical backing of the 2.88 GB output; the best of a few probed
-allocations is reported beside it as "tuned_output_placement" and is never `value`.
+allocations is reported beside it as "tuned_output_placement" (--full) and is never `value`.
 
-Beside `value` the line carries
+A plain run (no --full) does only what `value` needs: set up, --warmup untimed steps, --steps timed steps, the outputs of the
+last step if --dump-outputs DIR is given, and the line (`value`, `ms_per_step`, the headline's roofline).  With --full the line
+carries beside `value`
+  * "drop_in_layout", "tuned_output_placement": the headline step into the per-sample images and into the best of a few probed
+    output allocations (side blocks, never `value`);
   * "config4": BASELINE.json configs[3] -- every rank's regressor -> fp64 Gram of its shard (the regressor never reaches
     HBM) written straight into the packed payload [G | c | bb | count], followed by ONE in-place all-reduce of it
     (P*P + P + 2 doubles, RCCL over xGMI; no packing kernels, no host synchronisation inside a step), timed as its own
@@ -29,14 +33,17 @@ Beside `value` the line carries
     configs[4]'s 256 chains split 256 / N per rank (no collective) -- both timed like the headline (barrier, max over ranks);
   * "extras" (rank 0's GPU, outside every timed region of the headline): configs[2] (7-DOF, N = 4e6, Gram) and configs[4]
     (256 distinct chains x 4 096 samples) once each with their own roofline blocks;
-  * "cpu_baseline": the C oracle on rank 0's host cores (every line, also for N > 1).
+  * "cpu_baseline": the C oracle on rank 0's host cores (every --full line, also for N > 1).
+The --no-* options and --placements, --cpu-seconds, --sharded-legs select among these legs of a --full run.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--samples S] [--y-layout element|stacked|per_sample]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--samples S] [--y-layout element|stacked|per_sample] [--dump-outputs DIR] [--full]
+      --dump-outputs DIR: after the timed steps, rank 0 writes what its last step returned, tau and Y on a fixed seeded subset of the
+      samples (dump_outputs below), as DIR/tau.npy and DIR/Y.npy in float64; the inputs are seeded, so two builds compare output for output.
       --gpus N > 1 without a torch.distributed environment: this process starts
       `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py ...` as a CHILD
       (before anything touches the GPU), relays rank 0's JSON line and exits with the child's return code.
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...      (what the driver runs)
-  python bench.py --gpus 2 --backend gloo --dry     launcher / process-group / all-reduce plumbing only, no GPU (CPU tests)
+  python bench.py --gpus 2 --backend gloo --dry [--full]   launcher / process-group / all-reduce plumbing only, no GPU (CPU tests)
   python bench.py --single-process --gpus N         configs[3], configs[2]'s R factor and configs[4] through the library's in-process
                                                     multi-device paths only (one process, one JSON line)
 
@@ -621,6 +628,37 @@ def extras_config5(dev, steps=5, n_chains=256, S=4096):
                          "traffic_source": "committed profile (profiles/pmc_latest.json, builder's box), not measured in this run" if traffic else None}}
 
 
+DUMP_SAMPLES = 16384     # samples --dump-outputs writes: at n = 6, P = 60 that is 47 MB of Y and 0.8 MB of tau (cap: 64 MB in all)
+DUMP_SEED = 0x5EED00D0
+
+
+def dump_indices(N):
+    """The fixed, seeded subset of sample indices that --dump-outputs writes (every sample if N <= DUMP_SAMPLES), ascending."""
+    import numpy as np
+    if N <= DUMP_SAMPLES:
+        return np.arange(N, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(N, DUMP_SAMPLES, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir, Y, tau, y_layout, N, n, P):
+    """--dump-outputs: what the last timed step returned to its caller, on the samples of dump_indices(N), in one layout whatever
+    --y-layout: DIR/tau.npy (k, n) and DIR/Y.npy (k, n, P) -- Y[i] the n x P regressor of sample dump_indices(N)[i] -- float64."""
+    import numpy as np
+    import torch
+    idx = torch.from_numpy(dump_indices(N)).to(Y.device)
+    if y_layout == "element":        # tau (n, N); Y (P, n, N): row j N + s of the column-major A
+        t, y = tau.index_select(1, idx).T, Y.index_select(2, idx).permute(2, 1, 0)
+    elif y_layout == "stacked":      # tau (N, n); Y (P, N n): row s n + j of the column-major A
+        t, y = tau.index_select(0, idx), Y.view(P, N, n).index_select(1, idx).permute(1, 2, 0)
+    else:                            # tau (N, n); Y (N, P, n): Y[s] the column-major n x P image
+        t, y = tau.index_select(0, idx), Y.index_select(0, idx).transpose(1, 2)
+    arrays = {"tau": t, "Y": y}
+    assert sum(a.numel() * 8 for a in arrays.values()) <= 64 * 1000 * 1000
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a.cpu().numpy(), dtype=np.float64))
+
+
 def step_into(chain, q, dq, ddq, in_layout, y_layout, Y, tau):
     def step():
         chain.getRegressor(q, dq, ddq, layout=in_layout, y_layout=y_layout, out=Y, tau_out=tau)
@@ -706,7 +744,7 @@ def dry_run(args, world, rank):
     out = {"metric": "RNEA+regressor evals/s (6-DOF, batch 1e6)", "value": None, "unit": "evals/s", "n_gpus": world, "dry": True,
            "backend": args.backend, "n_ranks_seen": seen, "samples_reduced": count, "gram_trace": float(torch.trace(G).item()),
            "steps": args.steps, "warmup": args.warmup,
-           "legs": ["config4"] + (["config3_sharded", "config5_sharded"] if world > 1 and not args.no_extras else []),
+           "legs": (["config4"] + (["config3_sharded", "config5_sharded"] if world > 1 and not args.no_extras else [])) if args.full else [],
            "r_factor_gather_fold_rel_err": fold_err, "config5_chains_per_rank": chains, "config5_chains_total": int(mine.item()),
            "distinct_pids": len(set(pids))}
     if world > 1:
@@ -725,6 +763,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--samples", type=int, default=1000000, help="samples per GPU")
     ap.add_argument("--y-layout", default="stacked", choices=["element", "stacked", "per_sample"])
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write tau and Y of the last step (fixed seeded sample subset, float64) as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: side blocks, configs[2]-[4], extras, the library child, the CPU baseline")
     ap.add_argument("--placements", type=int, default=12, help="candidate output buffers probed for the tuned_output_placement side block AFTER the headline (0 or 1 = skip); never affects `value`")
     ap.add_argument("--single-process", action="store_true", help="configs[3] through the library's in-process RCCL path (rdyn_regressor_gram_multi over --gpus devices) only")
     ap.add_argument("--no-library-config4", action="store_true", help="skip the config4_library child process")
@@ -821,6 +863,16 @@ def main():
                      "traffic_source": "committed profile (profiles/pmc_latest.json, builder's box), not measured in this run" if traffic else None,
                      "kernel": kernel, "kernel_ms": kernel_ms, "algorithmic_bytes_per_launch": b_eval * N},
     }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, Y, tau, args.y_layout, N, n, P)
+    if not args.full:
+        # a plain run ends with the headline: every other leg is behind --full
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(out))
+        return
     if args.y_layout == "stacked" and world == 1 and not args.no_extras:
         # side block, never `value`: the same evaluation into the per-sample DROP-IN images (what a rosdyn::Chain caller receives per sample,
         # primitives_impl.h:1350-1354) -- its own first allocation, same step count, same timing protocol

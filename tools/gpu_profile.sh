@@ -4,7 +4,7 @@
 #   tools/gpu_profile.sh bench <tag> [bench args]   kernel-trace stats + separate --pmc FETCH_SIZE / WRITE_SIZE passes of bench.py;
 #                                                   PMC_KEY=<key> updates profiles/pmc_latest.json (read by bench.py for roofline.traffic)
 #   tools/gpu_profile.sh round <rN>                 the profile set of a round into gpurun_out/prof_<rN>/ (copy what is to be judged into
-#                                                   profiles/<rN>/): the DEFAULT bench command plain and under --kernel-trace --stats, the
+#                                                   profiles/<rN>/): the bench command with --full plain and under --kernel-trace --stats, the
 #                                                   headline kernel's HBM traffic (stacked, per-sample), the secondary workloads of
 #                                                   tools/prof_workloads.py with kernel stats, HBM traffic (streaming ones) or matrix-pipe
 #                                                   counters (Gram, robust factors)
@@ -13,8 +13,9 @@
 # (the per-round scripts of rounds 1-3 this replaces are in tools/archive/)
 set -u
 MODE=${1:-round}; shift || true
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-cd $GRAFT_REPO_ROOT
+cd "$ROOT"
 if [ "$MODE" = "bench" ]; then
   TAG=${1:-bench}; shift || true
   OUT=gpurun_out/prof_$TAG
@@ -43,9 +44,9 @@ R=${1:-r4}
 O=gpurun_out/prof_$R
 mkdir -p $O
 KERNELS="^==|^timed region|k_local_sweep|k_rowpair|k_image_sweep|k_gram|k_regressor|k_base|k_components|k_local_ik|k_cholqr|k_tsqr|k_pgram|^dispatches"
-# 1. the DEFAULT bench command: plain, then under --kernel-trace --stats
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/final/trace -o bench -- python3 bench.py > $O/bench_default_under_rocprof.json 2> $O/final_trace.log
+# 1. the default bench command with every leg (--full): plain, then under --kernel-trace --stats
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/final/trace -o bench -- python3 bench.py --full > $O/bench_default_under_rocprof.json 2> $O/final_trace.log
 python3 tools/summarize_prof.py $O/final | grep -E "$KERNELS" | cut -c1-250 > $O/bench_default_summary.txt
 cp $(find $O/final/trace -name "*kernel_stats.csv" | head -1) $O/bench_default_kernel_stats.csv
 # 2. HBM traffic of the headline kernel (stacked) and of the per-sample layout: separate --pmc passes
