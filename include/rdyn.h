@@ -52,8 +52,11 @@ extern "C" {
  *      with MORE input joints than that (up to RDYN_MAX_JOINTS of them; rdyn_long_local.hip: rolled link and row loops, the per-joint
  *      state in wave-private LDS) rdyn_regressor (+ its fused torque), rdyn_joint_inertia, the joint torques (read off the wrench
  *      recursion) and every kinematic output are served, rdyn_regressor_gram and rdyn_regressor_tsqr for 11 input joints (110 + 1 columns:
- *      what the Gram kernel and the widest R factor hold; chunk images); rdyn_local_ik, component columns and wider normal equations /
- *      factors answer RDYN_ERR_UNSUPPORTED. */
+ *      what the Gram kernel and the widest R factor hold; chunk images); rdyn_local_ik, component columns and wider factors answer
+ *      RDYN_ERR_UNSUPPORTED.
+ *  - Normal equations: rdyn_gram, rdyn_regressor_gram and rdyn_identification_gram stop at 111 columns (110 + tau_meas, after the
+ *    reduction); rdyn_gram_wide, rdyn_regressor_gram_wide and rdyn_identification_gram_wide serve the rest up to
+ *    RDYN_MAX_WIDE_COLUMNS columns (any chain above, components included).  The R factors stop at 112 columns with the rhs. */
 #define RDYN_MAX_JOINTS 32
 #define RDYN_MAX_SWEPT_JOINTS 10
 
@@ -378,6 +381,31 @@ int rdyn_identification_gram(const rdyn_chain* chain, const rdyn_component* comp
 size_t rdyn_regressor_gram_workspace_bytes(const rdyn_chain* chain, int64_t chunk_samples);
 int rdyn_regressor_gram(const rdyn_chain* chain, const rdyn_batch* batch, const double* tau_meas, double* G, double* c,
                         double* bb, int accumulate, int64_t chunk_samples, void* workspace, size_t workspace_bytes);
+
+/* ---- normal equations wider than 111 columns (column-panel fp64-MFMA Gram, rdyn_panel_gram.hip) ----------------------------
+ * rdyn_gram_wide: rdyn_gram for up to RDYN_MAX_WIDE_COLUMNS columns (always the panel kernel, whatever the width): the columns of
+ * [A | b] are cut into panels of 64 and one launch reduces every panel pair.  Same outputs, accumulate and determinism as rdyn_gram;
+ * workspace: rdyn_gram_wide_workspace_bytes(n_cols) bytes (0 unless 1 <= n_cols <= RDYN_MAX_WIDE_COLUMNS).
+ * rdyn_regressor_gram_wide / rdyn_identification_gram_wide: rdyn_regressor_gram / rdyn_identification_gram for every chain the library
+ * ingests -- up to RDYN_MAX_JOINTS chain joints, any number of input joints in any order, fixed joints anywhere, up to 30 components --
+ * as long as 10 joints_number + K <= RDYN_MAX_WIDE_COLUMNS.  A request the narrow call serves is handed to it (the workspace query
+ * then returns the narrow call's size); the rest goes through element-major chunk images of [Y | C | tau_meas] (chunk_samples per
+ * chunk; 0 = as many as keep one image within 128 MiB, at least 16 384) into the panel kernel, chains with
+ * fixed joints and at most RDYN_MAX_SWEPT_JOINTS input joints through their reduced companion.  Outputs, accumulate, N = 0 and
+ * NULL c / bb as rdyn_regressor_gram; no allocation, no synchronisation (graph-capturable).  RDYN_ERR_INVALID_ARGUMENT for null or
+ * undersized arguments (before any device work), RDYN_ERR_UNSUPPORTED only past RDYN_MAX_WIDE_COLUMNS columns. */
+#define RDYN_MAX_WIDE_COLUMNS 415
+size_t rdyn_gram_wide_workspace_bytes(int n_cols);
+int rdyn_gram_wide(const double* A, int64_t rows, int64_t lda, int n_cols, const double* b, double* G, double* c, double* bb,
+                   int accumulate, void* workspace, size_t workspace_bytes, int device, void* stream);
+size_t rdyn_regressor_gram_wide_workspace_bytes(const rdyn_chain* chain, int64_t chunk_samples);
+int rdyn_regressor_gram_wide(const rdyn_chain* chain, const rdyn_batch* batch, const double* tau_meas, double* G, double* c,
+                             double* bb, int accumulate, int64_t chunk_samples, void* workspace, size_t workspace_bytes);
+size_t rdyn_identification_gram_wide_workspace_bytes(const rdyn_chain* chain, const rdyn_component* comps, int n_comps,
+                                                     int64_t chunk_samples);
+int rdyn_identification_gram_wide(const rdyn_chain* chain, const rdyn_component* comps, int n_comps, const rdyn_batch* batch,
+                                  const double* tau_meas, double* G, double* c, double* bb, int accumulate,
+                                  int64_t chunk_samples, void* workspace, size_t workspace_bytes);
 
 /* ---- BASELINE.json configs[3] inside the library (rdyn_multi_gpu.cpp): one process, the trajectory batch
  * sharded over the GPUs of a node, every GPU the fused regressor -> Gram of its shard, then ONE

@@ -104,6 +104,12 @@ SYMBOLS = {
     "rdyn_identification_gram": (_I, [_VP, _VP, _I, _BP, _VP, _VP, _VP, _VP, _I, _VP, C.c_size_t]),
     "rdyn_regressor_gram_workspace_bytes": (C.c_size_t, [_VP, C.c_int64]),
     "rdyn_regressor_gram": (_I, [_VP, _BP, _VP, _VP, _VP, _VP, _I, C.c_int64, _VP, C.c_size_t]),
+    "rdyn_gram_wide_workspace_bytes": (C.c_size_t, [_I]),
+    "rdyn_gram_wide": (_I, [_VP, C.c_int64, C.c_int64, _I, _VP, _VP, _VP, _VP, _I, _VP, C.c_size_t, _I, _VP]),
+    "rdyn_regressor_gram_wide_workspace_bytes": (C.c_size_t, [_VP, C.c_int64]),
+    "rdyn_regressor_gram_wide": (_I, [_VP, _BP, _VP, _VP, _VP, _VP, _I, C.c_int64, _VP, C.c_size_t]),
+    "rdyn_identification_gram_wide_workspace_bytes": (C.c_size_t, [_VP, _VP, _I, C.c_int64]),
+    "rdyn_identification_gram_wide": (_I, [_VP, _VP, _I, _BP, _VP, _VP, _VP, _VP, _I, C.c_int64, _VP, C.c_size_t]),
     "rdyn_multi_gpu_create": (_I, [C.POINTER(C.c_int), _I, C.POINTER(_VP)]),
     "rdyn_multi_gpu_destroy": (None, [_VP]),
     "rdyn_multi_gpu_device_count": (_I, [_VP]),

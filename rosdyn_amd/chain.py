@@ -419,6 +419,58 @@ class Chain(object):
                                         workspace.data_ptr(), workspace.numel()))
         return G, c, bb
 
+    def getRegressorGramWide(self, q, Dq, DDq, tau_meas=None, layout="sample", chunk_samples=0, out=None, accumulate=False,
+                             workspace=None):
+        """getRegressorGram for every chain the library ingests, up to 415 columns (include/rdyn.h: rdyn_regressor_gram_wide: chains
+        with 12 to 32 input joints through the column-panel Gram; what getRegressorGram serves goes to it).
+        Returns (G = A^T A (P, P), c = A^T tau_meas (P,), bb = tau_meas^T tau_meas (1,))."""
+        torch = _torch()
+        b, N, lay = self._batch(layout, q, Dq, DDq)
+        P = 10 * self.getJointsNumber()
+        if tau_meas is not None and (tau_meas.shape != q.shape or tau_meas.dtype != torch.float64 or not tau_meas.is_contiguous()):
+            raise ValueError("Input data dimensions mismatch")
+        if out is None:
+            out = (torch.empty((P, P), dtype=torch.float64, device=q.device), torch.empty((P,), dtype=torch.float64, device=q.device),
+                   torch.empty((1,), dtype=torch.float64, device=q.device))
+            if accumulate:
+                raise ValueError("accumulate needs out=")
+        G, c, bb = out
+        nbytes = lib().rdyn_regressor_gram_wide_workspace_bytes(self._h, chunk_samples)
+        if nbytes == 0:
+            raise ValueError("rdyn_regressor_gram_wide: at most 415 columns")
+        if workspace is None:
+            workspace = torch.empty((nbytes,), dtype=torch.uint8, device=q.device)
+        check(lib().rdyn_regressor_gram_wide(self._h, C.byref(b), tau_meas.data_ptr() if tau_meas is not None else None,
+                                             G.data_ptr(), c.data_ptr(), bb.data_ptr(), 1 if accumulate else 0, chunk_samples,
+                                             workspace.data_ptr(), workspace.numel()))
+        return G, c, bb
+
+    def getIdentificationGramWide(self, components, q, Dq, DDq, tau_meas, layout="sample", chunk_samples=0, out=None,
+                                  accumulate=False, workspace=None):
+        """getIdentificationGram for every chain the library ingests, up to 415 columns of [Y | C] (include/rdyn.h:
+        rdyn_identification_gram_wide).  Returns (G (P+K, P+K), c (P+K,), bb (1,))."""
+        torch = _torch()
+        b, N, lay = self._batch(layout, q, Dq, DDq)
+        if tau_meas.shape != q.shape or tau_meas.dtype != torch.float64 or not tau_meas.is_contiguous():
+            raise ValueError("Input data dimensions mismatch")
+        arr, n_comps = (C.cast(components._arr, C.c_void_p), components.n_comps) if components is not None else (None, 0)
+        cols = 10 * self.getJointsNumber() + (components.columns if components is not None else 0)
+        if out is None:
+            out = (torch.empty((cols, cols), dtype=torch.float64, device=q.device), torch.empty((cols,), dtype=torch.float64, device=q.device),
+                   torch.empty((1,), dtype=torch.float64, device=q.device))
+            if accumulate:
+                raise ValueError("accumulate needs out=")
+        G, c, bb = out
+        nbytes = lib().rdyn_identification_gram_wide_workspace_bytes(self._h, arr, n_comps, chunk_samples)
+        if nbytes == 0:
+            raise ValueError("rdyn_identification_gram_wide: at most 415 columns (regressor + components)")
+        if workspace is None:
+            workspace = torch.empty((nbytes,), dtype=torch.uint8, device=q.device)
+        check(lib().rdyn_identification_gram_wide(self._h, arr, n_comps, C.byref(b), tau_meas.data_ptr(), G.data_ptr(), c.data_ptr(),
+                                                  bb.data_ptr(), 1 if accumulate else 0, chunk_samples, workspace.data_ptr(),
+                                                  workspace.numel()))
+        return G, c, bb
+
     def getRegressorTsqr(self, q, Dq, DDq, tau_meas=None, layout="sample", out=None, accumulate=False, workspace=None):
         """R factor of the stacked [regressor | tau_meas] of this batch WITHOUT forming A'A (include/rdyn.h: rdyn_regressor_tsqr,
         BASELINE.json configs[2]).  Returns R1 = [R d; 0 rho] as a (P + 1, P + 1) tensor in math layout (upper triangular)."""

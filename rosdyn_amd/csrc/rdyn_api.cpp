@@ -2492,6 +2492,293 @@ int rdyn_identification_gram(const rdyn_chain* c, const rdyn_component* comps, i
   return RDYN_OK;
 }
 
+// ---- normal equations wider than 111 columns: the column-panel Gram (rdyn_panel_gram.hip) -----------------------------------------
+// Default chunk: as many samples as keep one chunk image [Y | C | tau_meas] within 128 MiB (inside the 256 MiB Infinity Cache), but
+// never fewer than kWideMinChunk.  Measured (profiles/r7/wide_gram.txt): the image writers cost a fixed ~0.36 ms per launch at 32
+// input joints up to 16 384 samples, so the cache-sized chunk of 1 600 samples took 35.5 ms per 1e5 samples against 14.5 ms at 16 384;
+// the panel pairs' re-reads run at the same rate whether the matrix fits the Infinity Cache or not.
+static const int64_t kWideImageBytes = (int64_t)128 << 20;
+static const int64_t kWideMinChunk = 16384;
+
+static size_t panel_slab_bytes(int n_cols) { return (rdyn_panel_gram_slab_bytes(n_cols) + 255) & ~(size_t)255; }
+
+size_t rdyn_gram_wide_workspace_bytes(int n_cols)
+{
+  return (n_cols < 1 || n_cols > RDYN_MAX_WIDE_COLUMNS) ? 0 : panel_slab_bytes(n_cols);
+}
+
+static int panel_gram_launch(const double* A, int64_t rows, int64_t lda, int n_cols, const double* bvec, double* G, double* cvec, double* bb,
+                             int slab_accumulate, bool finish, int add_to_output, void* slabs, hipStream_t st, int64_t row_block = 0,
+                             const int* first_col = nullptr, int n_row_blocks = 0)
+{
+  RdynPanelGramArgs a;
+  memset(&a, 0, sizeof a);
+  a.row_block = first_col ? row_block : 0;
+  for (int j = 0; first_col && j < n_row_blocks && j < RDYN_MAX_JOINTS; ++j) a.first_col[j] = first_col[j];
+  a.A = A;
+  a.b = bvec;
+  a.rows = rows;
+  a.lda = lda;
+  a.P = n_cols;
+  a.accumulate = slab_accumulate;
+  a.add_to_output = add_to_output;
+  a.slabs = (double*)slabs;
+  a.G = G;
+  a.c = cvec;
+  a.bb = bb;
+  RDYN_HIP_TRY(rdyn_launch_panel_gram(a, st));
+  if (finish) RDYN_HIP_TRY(rdyn_launch_panel_gram_finish(a, st));
+  return RDYN_OK;
+}
+
+int rdyn_gram_wide(const double* A, int64_t rows, int64_t lda, int n_cols, const double* bvec, double* G, double* cvec, double* bb,
+                   int accumulate, void* workspace, size_t workspace_bytes, int device, void* stream)
+{
+  if (!A || !G || rows < 0 || lda < rows || n_cols < 1 || !workspace)
+  {
+    rdyn_set_error("rdyn_gram_wide: invalid argument");
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  if (n_cols > RDYN_MAX_WIDE_COLUMNS)
+  {
+    rdyn_set_error("rdyn_gram_wide: at most %d columns are supported", RDYN_MAX_WIDE_COLUMNS);
+    return RDYN_ERR_UNSUPPORTED;
+  }
+  if (workspace_bytes < panel_slab_bytes(n_cols))
+  {
+    rdyn_set_error("rdyn_gram_wide: workspace too small (%zu < %zu bytes)", workspace_bytes, panel_slab_bytes(n_cols));
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  DeviceGuard g;
+  int st = g.enter(device);
+  if (st != RDYN_OK) return st;
+  return panel_gram_launch(A, rows, lda, n_cols, bvec, G, cvec, bb, 0, true, accumulate ? 1 : 0, workspace, (hipStream_t)stream);
+}
+
+// How a wide request is served: by the narrow call (it already serves it), through the reduced companion (the wide normal equations
+// of the companion, then k_gram_expand), or by chunk images of the chain itself (more than RDYN_MAX_SWEPT_JOINTS input joints:
+// k_long_regressor; a swept chain: the element-major regressor sweep) with the component columns behind Y, into the panel kernel.
+enum { WIDE_NONE = 0, WIDE_NARROW, WIDE_REDUCED, WIDE_LONG_IMAGES, WIDE_SWEEP_IMAGES };
+struct WidePlan
+{
+  int route = WIDE_NONE;
+  int K = 0, cols = 0;
+  int64_t chunk = 0;
+  size_t bytes = 0;  // workspace
+};
+
+static WidePlan wide_plan(const rdyn_chain* c, const rdyn_component* comps, int n_comps, int64_t chunk_samples, bool ident)
+{
+  WidePlan p;
+  if (!c || c->n_joints() < 1 || n_comps < 0 || n_comps > RDYN_MAX_COMPONENTS || (n_comps > 0 && !comps)) return p;
+  p.K = n_comps > 0 ? rdyn_components_columns(comps, n_comps) : 0;
+  p.cols = 10 * c->n_joints() + p.K;
+  const size_t narrow = ident ? rdyn_identification_gram_workspace_bytes(c, comps, n_comps) : rdyn_regressor_gram_workspace_bytes(c, chunk_samples);
+  if (narrow > 0)
+  {
+    p.route = WIDE_NARROW;
+    p.bytes = narrow;
+    return p;
+  }
+  if (p.cols > RDYN_MAX_WIDE_COLUMNS) return p;
+  if (c->reduced)
+  {
+    const WidePlan r = wide_plan(c->reduced.get(), comps, n_comps, chunk_samples, ident);
+    if (r.bytes == 0) return p;
+    p.route = WIDE_REDUCED;
+    p.bytes = r.bytes + reduce_tmp_bytes(10 * c->reduced->n_joints() + p.K);
+    return p;
+  }
+  p.route = c->long_chain() ? WIDE_LONG_IMAGES : WIDE_SWEEP_IMAGES;
+  const int64_t per_sample = (int64_t)c->n_active() * (p.cols + 1) * (int64_t)sizeof(double);
+  const int64_t fit = (kWideImageBytes / per_sample) & ~(int64_t)63;
+  p.chunk = chunk_samples > 0 ? chunk_samples : (fit > kWideMinChunk ? fit : kWideMinChunk);
+  p.bytes = panel_slab_bytes(p.cols) + (((size_t)p.chunk * per_sample + 255) & ~(size_t)255);
+  return p;
+}
+
+static int gram_wide_run(const rdyn_chain* c, const rdyn_component* comps, int n_comps, const rdyn_batch* b, const double* tau_meas, double* G,
+                         double* cvec, double* bb, int accumulate, int64_t chunk_samples, void* workspace, size_t workspace_bytes, bool ident)
+{
+  const char* fn = ident ? "rdyn_identification_gram_wide" : "rdyn_regressor_gram_wide";
+  int st = check_batch(c, b, true, true, fn, LONG_KERNELS);
+  if (st != RDYN_OK) return st;
+  if (!G || !workspace || n_comps < 0 || n_comps > RDYN_MAX_COMPONENTS || (n_comps > 0 && !comps))
+  {
+    rdyn_set_error("%s: null output / workspace, or more than %d components", fn, RDYN_MAX_COMPONENTS);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  const int n = c->n_active();
+  RdynComponentArgs ca;
+  memset(&ca, 0, sizeof ca);
+  st = fill_components(comps, n_comps, n, &ca);
+  if (st != RDYN_OK) return st;
+  const WidePlan p = wide_plan(c, comps, n_comps, chunk_samples, ident);
+  if (p.bytes == 0)
+  {
+    rdyn_set_error("%s: at most %d columns (regressor + components) are supported", fn, RDYN_MAX_WIDE_COLUMNS);
+    return RDYN_ERR_UNSUPPORTED;
+  }
+  if (workspace_bytes < p.bytes)
+  {
+    rdyn_set_error("%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes, p.bytes);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  if (p.route == WIDE_NARROW)
+    return ident ? rdyn_identification_gram(c, comps, n_comps, b, tau_meas, G, cvec, bb, accumulate, workspace, workspace_bytes)
+                 : rdyn_regressor_gram(c, b, tau_meas, G, cvec, bb, accumulate, chunk_samples, workspace, workspace_bytes);
+  DeviceGuard g;
+  st = g.enter(b->device);
+  if (st != RDYN_OK) return st;
+  hipStream_t stream = (hipStream_t)b->stream;
+  const int cols = p.cols, K = p.K;
+  const int64_t N = b->n_samples;
+  if (N == 0)
+  {
+    if (!accumulate)
+    {
+      RDYN_HIP_TRY(hipMemsetAsync(G, 0, sizeof(double) * cols * cols, stream));
+      if (cvec) RDYN_HIP_TRY(hipMemsetAsync(cvec, 0, sizeof(double) * cols, stream));
+      if (bb) RDYN_HIP_TRY(hipMemsetAsync(bb, 0, sizeof(double), stream));
+    }
+    return RDYN_OK;
+  }
+  if (p.route == WIDE_REDUCED)
+  {
+    // G = E' G_red E (rdyn_chain.hpp): the companion's wide normal equations into the tail of the workspace, then k_gram_expand
+    const rdyn_chain* r = c->reduced.get();
+    const int Cr = 10 * r->n_joints() + K;
+    const size_t tmp = reduce_tmp_bytes(Cr);
+    double* Gr = (double*)((char*)workspace + p.bytes - tmp);
+    st = gram_wide_run(r, comps, n_comps, b, tau_meas, Gr, Gr + (size_t)Cr * Cr, Gr + (size_t)Cr * Cr + Cr, 0, chunk_samples, workspace,
+                       p.bytes - tmp, ident);
+    if (st != RDYN_OK) return st;
+    RdynGramExpandArgs ea;
+    memset(&ea, 0, sizeof ea);
+    st = device_expand(c, &ea.X);
+    if (st != RDYN_OK) return st;
+    ea.G_red = Gr;
+    ea.c_red = Gr + (size_t)Cr * Cr;
+    ea.bb_red = Gr + (size_t)Cr * Cr + Cr;
+    for (int f = 0; f < c->n_joints(); ++f) ea.red_of[f] = c->red_of[f];
+    ea.n_joints = c->n_joints();
+    ea.n_red = r->n_joints();
+    ea.n_comp_cols = K;
+    ea.add_to_output = accumulate ? 1 : 0;
+    ea.G = G;
+    ea.c = cvec;
+    ea.bb = bb;
+    RDYN_HIP_TRY(rdyn_launch_gram_expand(ea, stream));
+    return RDYN_OK;
+  }
+  // chunk images: element-major [Y (P) | C (K) | tau_meas], rows j * cnt + s, lda = n * cnt; row block j is zero left of column
+  // 10 * (chain index of input joint j) -- the component columns lie to the right of every band
+  const RdynChainConst* dc = nullptr;
+  const RdynLongChainConst* dl = nullptr;
+  st = p.route == WIDE_LONG_IMAGES ? device_const_long(c, &dl) : device_const(c, &dc);
+  if (st != RDYN_OK) return st;
+  const int P = 10 * c->n_joints();
+  int first_col[RDYN_MAX_JOINTS];
+  for (int j = 0; j < n; ++j) first_col[j] = 10 * c->active[j];
+  double* const slabs = (double*)workspace;
+  double* const image = (double*)((char*)workspace + panel_slab_bytes(cols));
+  const int64_t in_step = (b->layout == RDYN_LAYOUT_SAMPLE_MAJOR) ? n : 1;
+  int64_t prev_cnt = -1;
+  for (int64_t s0 = 0; s0 < N; s0 += p.chunk)
+  {
+    const int64_t cnt = (N - s0 < p.chunk) ? (N - s0) : p.chunk;
+    if (cnt != prev_cnt)
+    {
+      // the sweep does not store the zero band; 16-row groups that straddle two row blocks read a little of it (see rdyn_regressor_gram)
+      RDYN_HIP_TRY(hipMemsetAsync(image, 0, sizeof(double) * (size_t)cnt * n * (cols + 1), stream));
+      prev_cnt = cnt;
+    }
+    const double* q = b->q + s0 * in_step;
+    const double* dq = b->dq + s0 * in_step;
+    const double* bcol = tau_meas ? tau_meas + s0 * in_step : nullptr;
+    int64_t in_ss, in_sj;
+    rec_strides(b, n, &in_ss, &in_sj);  // element-major: the joint stride stays the FULL batch's N
+    if (p.route == WIDE_LONG_IMAGES)
+    {
+      RdynLongLocalArgs a;
+      memset(&a, 0, sizeof a);
+      a.chain_long = dl;
+      a.q = q;
+      a.dq = dq;
+      a.ddq = b->ddq + s0 * in_step;
+      a.bcol = bcol;
+      a.bcol_col = cols;
+      a.n_samples = cnt;
+      a.in_ss = in_ss;
+      a.in_sj = in_sj;
+      a.Y = image;
+      a.y_ss = 1;
+      a.y_sr = cnt;
+      a.y_sc = (int64_t)n * cnt;
+      RDYN_HIP_TRY(rdyn_launch_long_local(RDYN_MODE_REGRESSOR, c->n_joints(), a, stream));
+    }
+    else
+    {
+      RdynSweepArgs a;
+      memset(&a, 0, sizeof a);
+      a.chain = dc;
+      a.q = q;
+      a.dq = dq;
+      a.ddq = b->ddq + s0 * in_step;
+      a.bcol = bcol;
+      a.bcol_col = cols;
+      a.n_samples = cnt;
+      a.in_ss = in_ss;
+      a.in_sj = in_sj;
+      a.Y = image;
+      a.y_ss = 1;
+      a.y_sr = cnt;
+      a.y_sc = (int64_t)n * cnt;
+      RDYN_HIP_TRY(rdyn_launch_local_sweep(c->n_joints(), RDYN_MODE_REGRESSOR_GRAM, a, stream));
+    }
+    if (K > 0)
+    {
+      ca.q = q;
+      ca.dq = dq;
+      ca.n_samples = cnt;
+      ca.in_ss = in_ss;
+      ca.in_sj = in_sj;
+      ca.n_active = n;
+      ca.n_comps = n_comps;
+      ca.C = image + (int64_t)P * n * cnt;
+      ca.c_ss = 1;
+      ca.c_sr = cnt;
+      ca.c_sc = (int64_t)n * cnt;
+      ca.tau = nullptr;
+      RDYN_HIP_TRY(rdyn_launch_components(ca, stream));
+    }
+    st = panel_gram_launch(image, (int64_t)n * cnt, (int64_t)n * cnt, cols, tau_meas ? image + (int64_t)cols * n * cnt : nullptr, G, cvec, bb,
+                           s0 > 0 ? 1 : 0, s0 + cnt >= N, accumulate ? 1 : 0, slabs, stream, cnt, first_col, n);
+    if (st != RDYN_OK) return st;
+  }
+  return RDYN_OK;
+}
+
+size_t rdyn_regressor_gram_wide_workspace_bytes(const rdyn_chain* c, int64_t chunk_samples) { return wide_plan(c, nullptr, 0, chunk_samples, false).bytes; }
+
+int rdyn_regressor_gram_wide(const rdyn_chain* c, const rdyn_batch* b, const double* tau_meas, double* G, double* cvec, double* bb,
+                             int accumulate, int64_t chunk_samples, void* workspace, size_t workspace_bytes)
+{
+  return gram_wide_run(c, nullptr, 0, b, tau_meas, G, cvec, bb, accumulate, chunk_samples, workspace, workspace_bytes, false);
+}
+
+size_t rdyn_identification_gram_wide_workspace_bytes(const rdyn_chain* c, const rdyn_component* comps, int n_comps, int64_t chunk_samples)
+{
+  return wide_plan(c, comps, n_comps, chunk_samples, true).bytes;
+}
+
+int rdyn_identification_gram_wide(const rdyn_chain* c, const rdyn_component* comps, int n_comps, const rdyn_batch* b, const double* tau_meas,
+                                  double* G, double* cvec, double* bb, int accumulate, int64_t chunk_samples, void* workspace,
+                                  size_t workspace_bytes)
+{
+  return gram_wide_run(c, comps, n_comps, b, tau_meas, G, cvec, bb, accumulate, chunk_samples, workspace, workspace_bytes, true);
+}
+
 int rdyn_evaluate_all(const rdyn_chain* c, const rdyn_batch* b, const rdyn_all_outputs* o)
 {
   // (a long chain goes through the single-purpose calls below: each one decides for itself what it serves, so that a request for

@@ -334,6 +334,33 @@ int rdyn_gram_blocks_for(int P);
 hipError_t rdyn_launch_gram(const RdynGramArgs& a, int blocks, hipStream_t st);
 hipError_t rdyn_launch_gram_finish(const RdynGramArgs& a, int blocks, hipStream_t st);
 
+// Gram of a matrix wider than k_gram holds: column panels of RDYN_PANEL_BLOCKS 16-column blocks, one launch over every panel pair
+// (rdyn_panel_gram.hip).  Same outputs as RdynGramArgs; the zero band of a regressor image may come from up to RDYN_MAX_JOINTS row blocks.
+#ifndef RDYN_PANEL_BLOCKS
+#define RDYN_PANEL_BLOCKS 4
+#endif
+struct RdynPanelGramArgs
+{
+  const double* A;
+  const double* b;     // may be null
+  int64_t rows, lda;
+  int P;
+  int accumulate;      // slabs += instead of slabs =
+  int add_to_output;   // finish: G/c/bb += instead of =
+  double* slabs;       // [pairs][blocks][RDYN_PANEL_BLOCKS^2 * 256]
+  double* G;
+  double* c;
+  double* bb;
+  // rows [j * row_block, (j + 1) * row_block) are zero in the columns < first_col[j] (any order); row_block == 0: no structure
+  int64_t row_block;
+  int first_col[RDYN_MAX_JOINTS];
+};
+int rdyn_panel_gram_pairs(int P);
+int rdyn_panel_gram_blocks(int P);  // row-slice workgroups per pair
+size_t rdyn_panel_gram_slab_bytes(int P);
+hipError_t rdyn_launch_panel_gram(const RdynPanelGramArgs& a, hipStream_t st);
+hipError_t rdyn_launch_panel_gram_finish(const RdynPanelGramArgs& a, hipStream_t st);
+
 struct RdynComponentArgs
 {
   const double *q, *dq;

@@ -660,6 +660,25 @@ public:
   {
     chk(rdyn_identification_gram(m_h, comps.data(), (int)comps.size(), &b, tau_meas, G, c, bb, accumulate ? 1 : 0, workspace, workspace_bytes));
   }
+  // the same normal equations beyond 111 columns (12 to 32 input joints, or many components; include/rdyn.h: rdyn_regressor_gram_wide /
+  // rdyn_identification_gram_wide); chunk_samples = 0: the default chunk
+  size_t getRegressorGramWideWorkspaceBytes(int64_t chunk_samples = 0) const { return rdyn_regressor_gram_wide_workspace_bytes(m_h, chunk_samples); }
+  void getRegressorGramWideBatch(const rdyn_batch& b, const double* tau_meas, double* G, double* c, double* bb, bool accumulate, void* workspace,
+                                 size_t workspace_bytes, int64_t chunk_samples = 0) const
+  {
+    chk(rdyn_regressor_gram_wide(m_h, &b, tau_meas, G, c, bb, accumulate ? 1 : 0, chunk_samples, workspace, workspace_bytes));
+  }
+  size_t getIdentificationGramWideWorkspaceBytes(const std::vector<rdyn_component>& comps, int64_t chunk_samples = 0) const
+  {
+    return rdyn_identification_gram_wide_workspace_bytes(m_h, comps.data(), (int)comps.size(), chunk_samples);
+  }
+  void getIdentificationGramWideBatch(const std::vector<rdyn_component>& comps, const rdyn_batch& b, const double* tau_meas, double* G,
+                                      double* c, double* bb, bool accumulate, void* workspace, size_t workspace_bytes,
+                                      int64_t chunk_samples = 0) const
+  {
+    chk(rdyn_identification_gram_wide(m_h, comps.data(), (int)comps.size(), &b, tau_meas, G, c, bb, accumulate ? 1 : 0, chunk_samples,
+                                      workspace, workspace_bytes));
+  }
   // the same identification step WITHOUT forming the normal equations: R1 = [R d; 0 rho] of [Y | C | tau_meas] by tall-skinny QR
   // (condition number not squared; include/rdyn.h: rdyn_regressor_tsqr / rdyn_identification_tsqr), solved by solveRFactor
   size_t getIdentificationTsqrWorkspaceBytes(const std::vector<rdyn_component>& comps) const

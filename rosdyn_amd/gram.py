@@ -32,6 +32,30 @@ def gram(A, b=None, out=None, accumulate=False, workspace=None):
     return G, c, bb
 
 
+def gram_wide(A, b=None, out=None, accumulate=False, workspace=None):
+    """gram() for up to 415 columns (include/rdyn.h: rdyn_gram_wide, the column-panel Gram kernel at every width).
+    A: (P, R) torch.float64 CUDA tensor = column-major R x P matrix; b: (R,) or None.  Returns (G (P, P), c (P,), bb (1,))."""
+    import torch
+    assert A.is_cuda and A.dtype == torch.float64 and A.dim() == 2 and A.is_contiguous()
+    P, R = A.shape
+    if out is None:
+        out = (torch.empty((P, P), dtype=torch.float64, device=A.device), torch.empty((P,), dtype=torch.float64, device=A.device),
+               torch.empty((1,), dtype=torch.float64, device=A.device))
+        assert not accumulate
+    G, c, bb = out
+    nbytes = lib().rdyn_gram_wide_workspace_bytes(P)
+    if nbytes == 0:
+        raise ValueError("rdyn_gram_wide: 1 to 415 columns")
+    if workspace is None:
+        workspace = torch.empty((nbytes,), dtype=torch.uint8, device=A.device)
+    if b is not None:
+        assert b.is_cuda and b.dtype == torch.float64 and b.numel() == R and b.is_contiguous()
+    check(lib().rdyn_gram_wide(A.data_ptr(), R, R, P, b.data_ptr() if b is not None else None, G.data_ptr(), c.data_ptr(), bb.data_ptr(),
+                               1 if accumulate else 0, workspace.data_ptr(), workspace.numel(),
+                               A.device.index if A.device.index is not None else -1, torch.cuda.current_stream(A.device).cuda_stream))
+    return G, c, bb
+
+
 def pack_normal_equations(G, c, bb, count):
     """[G | c | bb | count] as ONE flat fp64 buffer: the all-reduce payload."""
     import torch
