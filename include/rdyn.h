@@ -56,7 +56,9 @@ extern "C" {
  *      RDYN_ERR_UNSUPPORTED.
  *  - Normal equations: rdyn_gram, rdyn_regressor_gram and rdyn_identification_gram stop at 111 columns (110 + tau_meas, after the
  *    reduction); rdyn_gram_wide, rdyn_regressor_gram_wide and rdyn_identification_gram_wide serve the rest up to
- *    RDYN_MAX_WIDE_COLUMNS columns (any chain above, components included).  The R factors stop at 112 columns with the rhs. */
+ *    RDYN_MAX_WIDE_COLUMNS columns (any chain above, components included).  The R factors: rdyn_tsqr, rdyn_regressor_tsqr and
+ *    rdyn_identification_tsqr stop at 112 columns with the rhs; rdyn_tsqr_wide, rdyn_regressor_tsqr_wide and
+ *    rdyn_identification_tsqr_wide serve up to RDYN_MAX_WIDE_COLUMNS + 1 columns with the rhs. */
 #define RDYN_MAX_JOINTS 32
 #define RDYN_MAX_SWEPT_JOINTS 10
 
@@ -513,6 +515,42 @@ int rdyn_tsqr_last_report(const rdyn_chain* chain, const rdyn_component* comps, 
                           int device, void* stream, rdyn_tsqr_report* out);
 /* the same for the last rdyn_tsqr call (n_cols_with_rhs = n_cols + (b != NULL), rows as in that call) */
 int rdyn_tsqr_rows_last_report(int n_cols_with_rhs, int64_t rows, const void* workspace, int device, void* stream, rdyn_tsqr_report* out);
+/* ---- R factors wider than 112 columns (preconditioned CholeskyQR over column panels: rdyn_panel_trmm.hip, rdyn_panel_gram.hip, the
+ * PANEL dense steps of rdyn_cholqr.hip).  Each call mirrors its narrow counterpart argument for argument (the chain forms + chunk_samples:
+ * samples per chunk image, 0 = default, as rdyn_regressor_gram_wide).  R1 (n1 x n1, column-major, upper triangular, n1 = n_cols + 1 with
+ * the rhs / tau_meas column, n1 <= RDYN_MAX_WIDE_COLUMNS + 1): R1'R1 = [A b]'[A b]; rows of the directions the factor kernel finds null
+ * are exactly zero.  A request the narrow call serves is handed to it, and the workspace query then returns the narrow size.
+ * RDYN_ERR_UNSUPPORTED only past the wide limit (chains with fixed joints: also when their reduced companion is narrower than 113
+ * columns while the chain is wider), RDYN_ERR_INVALID_ARGUMENT for null or undersized arguments before any device work.  accumulate,
+ * N = 0 and tau_meas == NULL as in the narrow calls.  No allocation, no synchronisation: the calls can be captured in a graph.
+ * Round 0 builds W = T^-1 from the Gram matrix of a row subsample (every S-th 16-row group of a matrix; one chunk image of every S-th
+ * sample of a batch), Q = [A b] W runs on the matrix cores one row chunk / chunk image at a time, R = chol(Q'Q) T; rounds 1 and 2
+ * re-precondition with the factor of the round before, started by the device only when that round was not accepted (gamma <= 1e4 and
+ * rho <= 4).  There is no Householder stand-by at these widths: when no round is accepted, round 2's factor stands and the report says
+ * so (stage 3).  Chains go through chunk images of [Y | C | tau_meas]; chains with fixed joints through the reduced companion, expanded
+ * by R = qr(R_red E_aug).  Solve with rdyn_solve_r_factor; fold factors with rdyn_tsqr_combine_host. */
+size_t rdyn_tsqr_wide_workspace_bytes(int n_cols_with_rhs);
+int rdyn_tsqr_wide(const double* A, int64_t rows, int64_t lda, int n_cols, const double* b, double* R1, int accumulate, void* workspace,
+                   size_t workspace_bytes, int device, void* stream);
+size_t rdyn_regressor_tsqr_wide_workspace_bytes(const rdyn_chain* chain, int64_t chunk_samples);
+int rdyn_regressor_tsqr_wide(const rdyn_chain* chain, const rdyn_batch* batch, const double* tau_meas, double* R1, int accumulate,
+                             int64_t chunk_samples, void* workspace, size_t workspace_bytes);
+size_t rdyn_identification_tsqr_wide_workspace_bytes(const rdyn_chain* chain, const rdyn_component* comps, int n_comps, int64_t chunk_samples);
+int rdyn_identification_tsqr_wide(const rdyn_chain* chain, const rdyn_component* comps, int n_comps, const rdyn_batch* batch,
+                                  const double* tau_meas, double* R1, int accumulate, int64_t chunk_samples, void* workspace,
+                                  size_t workspace_bytes);
+typedef struct rdyn_tsqr_wide_report
+{
+  int32_t route;      /* 2: column-panel CholeskyQR; 0: the width is served by the narrow calls (read their report) */
+  int32_t stage;      /* 0, 1, 2: the round whose factor was accepted; 3: none was, round 2's factor stands */
+  int32_t n_deferred; /* columns the last preconditioner did not use for elimination */
+  int32_t reserved;
+  double gamma[3];    /* growth factor of the rounding of A W, rounds 0..2 (0 = round not run); accepted up to 1e4 */
+  double rho[3];      /* |Re^-1|_F / sqrt(k) of the column-equilibrated A W, rounds 0..2; accepted up to 4 */
+} rdyn_tsqr_wide_report;
+/* What the last wide factor call that used `workspace` did; n_cols_with_rhs = the width of its factor (10 joints_number + K + 1 for the
+ * chain forms).  Waits for `stream`. */
+int rdyn_tsqr_wide_last_report(int n_cols_with_rhs, const void* workspace, int device, void* stream, rdyn_tsqr_wide_report* out);
 /* HOST: folds n_factors upper-triangular n x n factors (stacked, each column-major n x n) into one (Householder). */
 int rdyn_tsqr_combine_host(const double* R_stack, int n_factors, int n, double* R_out);
 

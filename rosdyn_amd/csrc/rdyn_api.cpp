@@ -2779,6 +2779,480 @@ int rdyn_identification_gram_wide(const rdyn_chain* c, const rdyn_component* com
   return gram_wide_run(c, comps, n_comps, b, tau_meas, G, cvec, bb, accumulate, chunk_samples, workspace, workspace_bytes, true);
 }
 
+// ---- R factors wider than 112 columns: preconditioned CholeskyQR over column panels (rdyn_panel_trmm.hip, rdyn_panel_gram.hip and
+// the PANEL instantiations of rdyn_cholqr.hip's dense steps).  Round 0: W from the Gram matrix of a row subsample; round r = 1, 2: W from
+// round r - 1's factor, started by the device when the round before was not accepted.  Per round: Q = [A b] W (k_panel_trmm), Q'Q
+// (k_panel_gram over every chunk + finish), R = chol(Q'Q) T.  Nothing falls back to Householder folds: they do not exist beyond 112 columns.
+// Workspace: [flags | slabs | W | T | V | G2 | R_tmp | squares | fold scratch | one row chunk of Q] -- the flags first, so that the
+// report needs nothing but the workspace and the width.
+static const int64_t kPanelQrRowBytes = (int64_t)128 << 20;  // rows region: 128 MiB (rdyn_tsqr_wide: one row chunk of Q)
+static const int64_t kPanelQrMinRows = 16384;
+static const int64_t kPanelQrSubGroups = 4096;     // rdyn_tsqr_wide's subsample: about 4 096 16-row groups
+static const int64_t kPanelQrSubSamples = 16384;   // the chain forms: one chunk image of about 16 384 samples
+static const int kPanelFlagDoubles = 256;          // ints [0..15] flags, [16 .. 16 + n1) deferred columns; doubles [224 + 4 r ..] diagnostics
+
+struct PanelQrLayout
+{
+  size_t flag = 0, slabs = 0, w = 0, t = 0, v = 0, g2 = 0, r_tmp = 0, sq = 0, fold = 0, rows = 0, total_doubles = 0;
+};
+static PanelQrLayout panel_qr_layout(int n1, size_t rows_doubles)
+{
+  PanelQrLayout L;
+  size_t off = 0;
+  auto take = [&](size_t doubles) {
+    const size_t at = off;
+    off = (off + doubles + 31) & ~(size_t)31;
+    return at;
+  };
+  const int nb = (n1 + 15) / 16, nt = nb * (nb + 1) / 2;
+  L.flag = take(kPanelFlagDoubles);
+  L.slabs = take(panel_slab_bytes(n1 - 1) / sizeof(double));
+  L.w = take((size_t)nt * 256);
+  L.t = take((size_t)n1 * n1);
+  L.v = take((size_t)n1 * n1);
+  L.g2 = take((size_t)n1 * n1 + 1);
+  L.r_tmp = take((size_t)n1 * n1);
+  L.sq = take((size_t)2 * n1 * n1);
+  L.fold = take((size_t)n1 * (n1 + 1) / 2);
+  L.rows = take(rows_doubles);
+  L.total_doubles = off;
+  return L;
+}
+static bool panel_qr_width_ok(int n1) { return n1 > rdyn_tsqr_wide_max_cols() && n1 <= RDYN_MAX_WIDE_COLUMNS + 1 && n1 <= rdyn_cholqr_panel_max_cols(); }
+static int64_t panel_qr_q_rows(int n1)
+{
+  const int64_t fit = (kPanelQrRowBytes / ((int64_t)n1 * (int64_t)sizeof(double))) & ~(int64_t)63;
+  return fit > kPanelQrMinRows ? fit : kPanelQrMinRows;
+}
+
+// the three rounds on the subsample Gram matrix in ws + L.g2; pass_b(W, run, round) queues Q = X W and Q'Q into L.g2 for all rows
+typedef std::function<int(const double* W, const int* run, int round)> PanelPassB;
+static int panel_qr_rounds(double* ws, const PanelQrLayout& L, int n1, int has_b, double row_scale, double* R_out, hipStream_t stream,
+                           const PanelPassB& pass_b)
+{
+  int* const flag = (int*)(ws + L.flag);
+  const int P = n1 - 1;
+  double* const G = ws + L.g2;
+  double* const c = G + (size_t)P * P;
+  double* const bb = c + P;
+  const int nb = (n1 + 15) / 16;
+  for (int round = 0; round < 3; ++round)
+  {
+    const int* const run = round == 0 ? nullptr : flag + (round - 1);
+    double* const diag = ws + L.flag + 224 + 4 * round;  // [0] rho, [1] gamma of the preconditioner, [2] gamma of the factor
+    RDYN_HIP_TRY(rdyn_launch_cholqr_precond_panel(round == 0 ? nullptr : R_out, round == 0 ? G : nullptr, c, bb, n1, nb, round == 0 ? row_scale : 1.0,
+                                                  ws + L.t, ws + L.w, ws + L.v, flag + 16, flag, round, run, diag + 1, ws + L.sq, stream));
+    const int st = pass_b(ws + L.w, run, round);
+    if (st != RDYN_OK) return st;
+    RDYN_HIP_TRY(rdyn_launch_cholqr_factor_panel(G, c, bb, n1, has_b, ws + L.t, ws + L.v, flag + 16, R_out, flag, round, run, diag, ws + L.sq, stream));
+  }
+  return RDYN_OK;
+}
+
+static int panel_gram_into(const double* Q, int64_t rows, int64_t ldq, int n1, bool has_b, double* g2, bool acc_slabs, bool finish, void* slabs,
+                           const int* run, hipStream_t st, int64_t row_block = 0, const int* first_col = nullptr, int n_row_blocks = 0)
+{
+  RdynPanelGramArgs a;
+  memset(&a, 0, sizeof a);
+  a.row_block = first_col ? row_block : 0;
+  for (int j = 0; first_col && j < n_row_blocks && j < RDYN_MAX_JOINTS; ++j) a.first_col[j] = first_col[j];
+  a.A = Q;
+  a.b = has_b ? Q + (int64_t)(n1 - 1) * ldq : nullptr;
+  a.rows = rows;
+  a.lda = ldq;
+  a.P = n1 - 1;
+  a.accumulate = acc_slabs ? 1 : 0;
+  a.slabs = (double*)slabs;
+  a.G = g2;
+  a.c = g2 + (size_t)(n1 - 1) * (n1 - 1);
+  a.bb = a.c + (n1 - 1);
+  a.run_flag = run;
+  RDYN_HIP_TRY(rdyn_launch_panel_gram(a, st));
+  if (finish) RDYN_HIP_TRY(rdyn_launch_panel_gram_finish(a, st));
+  return RDYN_OK;
+}
+
+static void read_wide_report(const double* raw, int n1, rdyn_tsqr_wide_report* out)
+{
+  int flags[2 * kPanelFlagDoubles];
+  memcpy(flags, raw, sizeof flags);
+  out->route = 2;
+  out->stage = 3;
+  for (int r = 2; r >= 0; --r)
+    if (flags[4 + r] && !flags[8 + r]) out->stage = r;
+  const int width = (flags[3] > 0 && flags[3] < n1) ? flags[3] : n1;  // (a chain with fixed joints: the companion's factor was computed)
+  for (int k = 0; k < width && 16 + k < 2 * kPanelFlagDoubles; ++k) out->n_deferred += flags[16 + k] ? 1 : 0;
+  for (int r = 0; r < 3; ++r)
+    if (flags[4 + r])
+    {
+      out->rho[r] = raw[224 + 4 * r];
+      out->gamma[r] = raw[224 + 4 * r + 2];
+    }
+}
+
+size_t rdyn_tsqr_wide_workspace_bytes(int n_cols_with_rhs)
+{
+  const int n1 = n_cols_with_rhs;
+  if (n1 >= 1 && n1 <= rdyn_tsqr_wide_max_cols()) return rdyn_tsqr_workspace_bytes(n1);
+  if (!panel_qr_width_ok(n1)) return 0;
+  return panel_qr_layout(n1, (size_t)panel_qr_q_rows(n1) * n1).total_doubles * sizeof(double);
+}
+
+int rdyn_tsqr_wide(const double* A, int64_t rows, int64_t lda, int n_cols, const double* bvec, double* R, int accumulate, void* workspace,
+                   size_t workspace_bytes, int device, void* stream_v)
+{
+  if (!A || !R || rows < 0 || lda < rows || n_cols < 1 || !workspace)
+  {
+    rdyn_set_error("rdyn_tsqr_wide: invalid argument");
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  const int n1 = n_cols + (bvec ? 1 : 0);
+  if (n1 <= rdyn_tsqr_wide_max_cols()) return rdyn_tsqr(A, rows, lda, n_cols, bvec, R, accumulate, workspace, workspace_bytes, device, stream_v);
+  if (!panel_qr_width_ok(n1))
+  {
+    rdyn_set_error("rdyn_tsqr_wide: at most %d columns (right-hand side included) are supported", RDYN_MAX_WIDE_COLUMNS + 1);
+    return RDYN_ERR_UNSUPPORTED;
+  }
+  const int64_t q_rows = panel_qr_q_rows(n1);
+  const PanelQrLayout L = panel_qr_layout(n1, (size_t)q_rows * n1);
+  if (workspace_bytes < L.total_doubles * sizeof(double))
+  {
+    rdyn_set_error("rdyn_tsqr_wide: workspace too small (%zu < %zu bytes)", workspace_bytes, L.total_doubles * sizeof(double));
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  DeviceGuard g;
+  int st = g.enter(device);
+  if (st != RDYN_OK) return st;
+  hipStream_t stream = (hipStream_t)stream_v;
+  if (rows == 0)
+  {
+    if (!accumulate) RDYN_HIP_TRY(hipMemsetAsync(R, 0, sizeof(double) * n1 * n1, stream));
+    return RDYN_OK;
+  }
+  double* const ws = (double*)workspace;
+  double* const Q = ws + L.rows;
+  // [A | b] as ONE matrix of n1 columns (the last one the right-hand side of the dense steps, as in rdyn_tsqr)
+  const int nA = bvec ? n_cols : n_cols - 1;
+  const double* const bcol = bvec ? bvec : A + (int64_t)(n1 - 1) * lda;
+  // pass A: every gs-th 16-row group (odd gs: no lock onto power-of-two periods of the rows), at most one row chunk
+  const int64_t groups = (rows + 15) / 16;
+  int64_t gs = groups / kPanelQrSubGroups > 1 ? groups / kPanelQrSubGroups : 1;
+  if (gs > 1 && gs % 2 == 0) ++gs;
+  while (rdyn_panel_gather_rows(rows, gs) > q_rows) gs += 2;
+  const int64_t sub_rows = rdyn_panel_gather_rows(rows, gs);
+  RDYN_HIP_TRY(rdyn_launch_panel_gather(A, bcol, rows, lda, nA, gs, Q, q_rows, stream));
+  st = panel_gram_into(Q, sub_rows, q_rows, n1, true, ws + L.g2, false, true, ws + L.slabs, nullptr, stream);
+  if (st != RDYN_OK) return st;
+  double* const R_new = accumulate ? ws + L.r_tmp : R;
+  const double row_scale = sqrt((double)groups * 16.0 / (double)sub_rows);
+  st = panel_qr_rounds(ws, L, n1, 1, row_scale, R_new, stream, [&](const double* W, const int* run, int) -> int {
+    for (int64_t r0 = 0; r0 < rows; r0 += q_rows)
+    {
+      const int64_t cnt = rows - r0 < q_rows ? rows - r0 : q_rows;
+      RdynPanelTrmmArgs ta;
+      memset(&ta, 0, sizeof ta);
+      ta.A = A + r0;
+      ta.b = bcol + r0;
+      ta.rows = cnt;
+      ta.lda = lda;
+      ta.n_cols = nA;
+      ta.n1 = n1;
+      ta.Q = Q;
+      ta.ldq = q_rows;
+      ta.W = W;
+      ta.run_flag = run;
+      RDYN_HIP_TRY(rdyn_launch_panel_trmm(ta, stream));
+      const int s2 = panel_gram_into(Q, cnt, q_rows, n1, true, ws + L.g2, r0 > 0, r0 + cnt >= rows, ws + L.slabs, run, stream);
+      if (s2 != RDYN_OK) return s2;
+    }
+    return RDYN_OK;
+  });
+  if (st != RDYN_OK) return st;
+  if (accumulate) RDYN_HIP_TRY(rdyn_launch_cholqr_fold_global(R_new, R, n1, ws + L.fold, stream));
+  return RDYN_OK;
+}
+
+int rdyn_tsqr_wide_last_report(int n_cols_with_rhs, const void* workspace, int device, void* stream, rdyn_tsqr_wide_report* out)
+{
+  if (!workspace || !out || n_cols_with_rhs < 1)
+  {
+    rdyn_set_error("rdyn_tsqr_wide_last_report: invalid argument");
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  if (n_cols_with_rhs > rdyn_tsqr_wide_max_cols() && !panel_qr_width_ok(n_cols_with_rhs))
+  {
+    rdyn_set_error("rdyn_tsqr_wide_last_report: at most %d columns are supported", RDYN_MAX_WIDE_COLUMNS + 1);
+    return RDYN_ERR_UNSUPPORTED;
+  }
+  memset(out, 0, sizeof *out);
+  if (n_cols_with_rhs <= rdyn_tsqr_wide_max_cols()) return RDYN_OK;  // route 0: served by rdyn_tsqr (rdyn_tsqr_rows_last_report)
+  DeviceGuard g;
+  int st = g.enter(device);
+  if (st != RDYN_OK) return st;
+  double raw[kPanelFlagDoubles];
+  RDYN_HIP_TRY(hipMemcpyAsync(raw, workspace, sizeof raw, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  RDYN_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  read_wide_report(raw, n_cols_with_rhs, out);
+  return RDYN_OK;
+}
+
+// chains: served by the narrow call where it serves (its workspace); else by chunk images of the chain itself -- [Y | C | tau_meas]
+// written by the writers of rdyn_regressor_gram_wide, multiplied by W in place (k_panel_trmm), reduced by the panel Gram; a chain with
+// fixed joints through its reduced companion (served by chunk images itself), whose factor is expanded by k_cholqr_expand<true>
+// (R = qr(R_red E_aug)) -- the companion's workspace first (its flags are what the report reads), then R_red, the expansion's square,
+// the expanded factor (accumulate) and the fold's triangle.
+struct PanelQrPlan
+{
+  bool narrow = false, reduced = false;
+  int K = 0, cols = 0, n1 = 0, n1r = 0;
+  int64_t chunk = 0;
+  size_t bytes = 0, sub_bytes = 0;
+  PanelQrLayout L;
+};
+static PanelQrPlan panel_qr_plan(const rdyn_chain* c, const rdyn_component* comps, int n_comps, int64_t chunk_samples, bool ident)
+{
+  PanelQrPlan p;
+  if (!c || c->n_joints() < 1 || n_comps < 0 || n_comps > RDYN_MAX_COMPONENTS || (n_comps > 0 && !comps) || chunk_samples < 0) return p;
+  const size_t narrow = ident ? rdyn_identification_tsqr_workspace_bytes(c, comps, n_comps) : rdyn_regressor_tsqr_workspace_bytes(c);
+  if (narrow > 0)
+  {
+    p.narrow = true;
+    p.bytes = narrow;
+    return p;
+  }
+  p.K = n_comps > 0 ? rdyn_components_columns(comps, n_comps) : 0;
+  p.cols = 10 * c->n_joints() + p.K;
+  p.n1 = p.cols + 1;
+  if (!panel_qr_width_ok(p.n1)) return p;
+  if (c->reduced)
+  {
+    const PanelQrPlan r = panel_qr_plan(c->reduced.get(), comps, n_comps, chunk_samples, ident);
+    if (r.narrow || r.reduced || r.bytes == 0) return p;  // (a companion the narrow call serves: the narrow call serves the chain)
+    p.reduced = true;
+    p.n1r = r.n1;
+    p.sub_bytes = (r.bytes + 255) & ~(size_t)255;
+    const size_t tail = (size_t)p.n1r * p.n1r + (size_t)p.n1 * p.n1r + (size_t)p.n1 * p.n1 + (size_t)p.n1 * (p.n1 + 1) / 2 + 128;
+    p.bytes = p.sub_bytes + tail * sizeof(double);
+    return p;
+  }
+  const int64_t per_sample = (int64_t)c->n_active() * p.n1 * (int64_t)sizeof(double);
+  const int64_t fit = (kWideImageBytes / per_sample) & ~(int64_t)63;
+  p.chunk = chunk_samples > 0 ? chunk_samples : (fit > kWideMinChunk ? fit : kWideMinChunk);
+  p.L = panel_qr_layout(p.n1, (size_t)p.chunk * c->n_active() * p.n1);
+  p.bytes = p.L.total_doubles * sizeof(double);
+  return p;
+}
+
+static int panel_qr_chain_run(const rdyn_chain* c, const rdyn_component* comps, int n_comps, const rdyn_batch* b, const double* tau_meas, double* R,
+                              int accumulate, int64_t chunk_samples, void* workspace, size_t workspace_bytes, bool ident)
+{
+  const char* fn = ident ? "rdyn_identification_tsqr_wide" : "rdyn_regressor_tsqr_wide";
+  int st = check_batch(c, b, true, true, fn, LONG_KERNELS);
+  if (st != RDYN_OK) return st;
+  if (!R || !workspace || n_comps < 0 || n_comps > RDYN_MAX_COMPONENTS || (n_comps > 0 && !comps) || chunk_samples < 0)
+  {
+    rdyn_set_error("%s: null output / workspace, negative chunk, or more than %d components", fn, RDYN_MAX_COMPONENTS);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  const int n = c->n_active();
+  RdynComponentArgs ca;
+  memset(&ca, 0, sizeof ca);
+  st = fill_components(comps, n_comps, n, &ca);
+  if (st != RDYN_OK) return st;
+  const PanelQrPlan p = panel_qr_plan(c, comps, n_comps, chunk_samples, ident);
+  if (p.bytes == 0)
+  {
+    rdyn_set_error("%s: this chain is not served (at most %d columns with the rhs; chains with fixed joints: the narrow limit)", fn,
+                   RDYN_MAX_WIDE_COLUMNS + 1);
+    return RDYN_ERR_UNSUPPORTED;
+  }
+  if (workspace_bytes < p.bytes)
+  {
+    rdyn_set_error("%s: workspace too small (%zu < %zu bytes)", fn, workspace_bytes, p.bytes);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  if (p.narrow)
+    return ident ? rdyn_identification_tsqr(c, comps, n_comps, b, tau_meas, R, accumulate, workspace, workspace_bytes)
+                 : rdyn_regressor_tsqr(c, b, tau_meas, R, accumulate, workspace, workspace_bytes);
+  DeviceGuard g;
+  st = g.enter(b->device);
+  if (st != RDYN_OK) return st;
+  hipStream_t stream = (hipStream_t)b->stream;
+  const int cols = p.cols, K = p.K, n1 = p.n1;
+  const int64_t N = b->n_samples;
+  if (N == 0)
+  {
+    if (!accumulate) RDYN_HIP_TRY(hipMemsetAsync(R, 0, sizeof(double) * n1 * n1, stream));
+    return RDYN_OK;
+  }
+  if (p.reduced)
+  {
+    double* const R_red = (double*)((char*)workspace + p.sub_bytes);
+    double* const B = R_red + (size_t)p.n1r * p.n1r;
+    double* const R_exp = B + (size_t)n1 * p.n1r;
+    double* const fold = R_exp + (size_t)n1 * n1;
+    st = panel_qr_chain_run(c->reduced.get(), comps, n_comps, b, tau_meas, R_red, 0, chunk_samples, workspace, p.sub_bytes, ident);
+    if (st != RDYN_OK) return st;
+    RdynGramExpandArgs ea;
+    memset(&ea, 0, sizeof ea);
+    st = device_expand(c, &ea.X);
+    if (st != RDYN_OK) return st;
+    for (int f = 0; f < c->n_joints(); ++f) ea.red_of[f] = c->red_of[f];
+    ea.n_joints = c->n_joints();
+    ea.n_red = c->reduced->n_joints();
+    ea.n_comp_cols = K;
+    double* const R_out = accumulate ? R_exp : R;
+    RDYN_HIP_TRY(rdyn_launch_cholqr_expand_global(ea, R_red, R_out, B, stream));
+    if (accumulate) RDYN_HIP_TRY(rdyn_launch_cholqr_fold_global(R_exp, R, n1, fold, stream));
+    return RDYN_OK;
+  }
+  const RdynChainConst* dc = nullptr;
+  const RdynLongChainConst* dl = nullptr;
+  const bool long_images = c->long_chain();
+  st = long_images ? device_const_long(c, &dl) : device_const(c, &dc);
+  if (st != RDYN_OK) return st;
+  const int P = 10 * c->n_joints();
+  int first_col[RDYN_MAX_JOINTS];
+  for (int j = 0; j < n; ++j) first_col[j] = 10 * c->active[j];
+  double* const ws = (double*)workspace;
+  const PanelQrLayout& L = p.L;
+  double* const image = ws + L.rows;
+  const int64_t in_step = (b->layout == RDYN_LAYOUT_SAMPLE_MAJOR) ? n : 1;
+  int64_t prev_cnt = -1;
+  // the image of cnt samples s0, s0 + S, s0 + 2 S, ...: [Y | C | tau_meas] element-major, rows j * cnt + s (as rdyn_regressor_gram_wide)
+  auto write_image = [&](int64_t s0, int64_t cnt, int64_t S) -> int {
+    if (cnt != prev_cnt)
+    {
+      // the writers do not store the zero band (k_panel_trmm keeps it zero for the next chunk of the same length)
+      RDYN_HIP_TRY(hipMemsetAsync(image, 0, sizeof(double) * (size_t)cnt * n * n1, stream));
+      prev_cnt = cnt;
+    }
+    else if (!tau_meas)
+      RDYN_HIP_TRY(hipMemsetAsync(image + (int64_t)cols * n * cnt, 0, sizeof(double) * (size_t)cnt * n, stream));
+    const double* q = b->q + s0 * in_step;
+    const double* dq = b->dq + s0 * in_step;
+    const double* bcol = tau_meas ? tau_meas + s0 * in_step : nullptr;
+    int64_t in_ss, in_sj;
+    rec_strides(b, n, &in_ss, &in_sj);  // element-major: the joint stride stays the FULL batch's N
+    in_ss *= S;
+    if (long_images)
+    {
+      RdynLongLocalArgs a;
+      memset(&a, 0, sizeof a);
+      a.chain_long = dl;
+      a.q = q;
+      a.dq = dq;
+      a.ddq = b->ddq + s0 * in_step;
+      a.bcol = bcol;
+      a.bcol_col = cols;
+      a.n_samples = cnt;
+      a.in_ss = in_ss;
+      a.in_sj = in_sj;
+      a.Y = image;
+      a.y_ss = 1;
+      a.y_sr = cnt;
+      a.y_sc = (int64_t)n * cnt;
+      RDYN_HIP_TRY(rdyn_launch_long_local(RDYN_MODE_REGRESSOR, c->n_joints(), a, stream));
+    }
+    else
+    {
+      RdynSweepArgs a;
+      memset(&a, 0, sizeof a);
+      a.chain = dc;
+      a.q = q;
+      a.dq = dq;
+      a.ddq = b->ddq + s0 * in_step;
+      a.bcol = bcol;
+      a.bcol_col = cols;
+      a.n_samples = cnt;
+      a.in_ss = in_ss;
+      a.in_sj = in_sj;
+      a.Y = image;
+      a.y_ss = 1;
+      a.y_sr = cnt;
+      a.y_sc = (int64_t)n * cnt;
+      RDYN_HIP_TRY(rdyn_launch_local_sweep(c->n_joints(), RDYN_MODE_REGRESSOR_GRAM, a, stream));
+    }
+    if (K > 0)
+    {
+      ca.q = q;
+      ca.dq = dq;
+      ca.n_samples = cnt;
+      ca.in_ss = in_ss;
+      ca.in_sj = in_sj;
+      ca.n_active = n;
+      ca.n_comps = n_comps;
+      ca.C = image + (int64_t)P * n * cnt;
+      ca.c_ss = 1;
+      ca.c_sr = cnt;
+      ca.c_sc = (int64_t)n * cnt;
+      ca.tau = nullptr;
+      RDYN_HIP_TRY(rdyn_launch_components(ca, stream));
+    }
+    return RDYN_OK;
+  };
+  // pass A: one image of every S-th sample (about kPanelQrSubSamples of them, at most one chunk)
+  const int64_t sub_cap = p.chunk < kPanelQrSubSamples ? p.chunk : kPanelQrSubSamples;
+  const int64_t S = (N + sub_cap - 1) / sub_cap;
+  const int64_t sub_cnt = (N + S - 1) / S;
+  st = write_image(0, sub_cnt, S);
+  if (st != RDYN_OK) return st;
+  st = panel_gram_into(image, (int64_t)n * sub_cnt, (int64_t)n * sub_cnt, n1, true, ws + L.g2, false, true, ws + L.slabs, nullptr, stream, sub_cnt,
+                       first_col, n);
+  if (st != RDYN_OK) return st;
+  double* const R_new = accumulate ? ws + L.r_tmp : R;
+  st = panel_qr_rounds(ws, L, n1, tau_meas ? 1 : 0, sqrt((double)N / (double)sub_cnt), R_new, stream, [&](const double* W, const int* run, int) -> int {
+    for (int64_t s0 = 0; s0 < N; s0 += p.chunk)
+    {
+      const int64_t cnt = (N - s0 < p.chunk) ? (N - s0) : p.chunk;
+      int s2 = write_image(s0, cnt, 1);
+      if (s2 != RDYN_OK) return s2;
+      RdynPanelTrmmArgs ta;
+      memset(&ta, 0, sizeof ta);
+      ta.A = image;
+      ta.b = nullptr;
+      ta.rows = (int64_t)n * cnt;
+      ta.lda = (int64_t)n * cnt;
+      ta.n_cols = n1;
+      ta.n1 = n1;
+      ta.Q = image;
+      ta.ldq = (int64_t)n * cnt;
+      ta.W = W;
+      ta.run_flag = run;
+      ta.row_block = cnt;
+      for (int j = 0; j < n; ++j) ta.first_col[j] = first_col[j];
+      for (int j = n; j < RDYN_MAX_JOINTS; ++j) ta.first_col[j] = 0;
+      RDYN_HIP_TRY(rdyn_launch_panel_trmm(ta, stream));
+      s2 = panel_gram_into(image, (int64_t)n * cnt, (int64_t)n * cnt, n1, true, ws + L.g2, s0 > 0, s0 + cnt >= N, ws + L.slabs, run, stream, cnt,
+                           first_col, n);
+      if (s2 != RDYN_OK) return s2;
+    }
+    return RDYN_OK;
+  });
+  if (st != RDYN_OK) return st;
+  if (accumulate) RDYN_HIP_TRY(rdyn_launch_cholqr_fold_global(R_new, R, n1, ws + L.fold, stream));
+  return RDYN_OK;
+}
+
+size_t rdyn_regressor_tsqr_wide_workspace_bytes(const rdyn_chain* c, int64_t chunk_samples) { return panel_qr_plan(c, nullptr, 0, chunk_samples, false).bytes; }
+
+int rdyn_regressor_tsqr_wide(const rdyn_chain* c, const rdyn_batch* b, const double* tau_meas, double* R, int accumulate, int64_t chunk_samples,
+                             void* workspace, size_t workspace_bytes)
+{
+  return panel_qr_chain_run(c, nullptr, 0, b, tau_meas, R, accumulate, chunk_samples, workspace, workspace_bytes, false);
+}
+
+size_t rdyn_identification_tsqr_wide_workspace_bytes(const rdyn_chain* c, const rdyn_component* comps, int n_comps, int64_t chunk_samples)
+{
+  return panel_qr_plan(c, comps, n_comps, chunk_samples, true).bytes;
+}
+
+int rdyn_identification_tsqr_wide(const rdyn_chain* c, const rdyn_component* comps, int n_comps, const rdyn_batch* b, const double* tau_meas,
+                                  double* R, int accumulate, int64_t chunk_samples, void* workspace, size_t workspace_bytes)
+{
+  return panel_qr_chain_run(c, comps, n_comps, b, tau_meas, R, accumulate, chunk_samples, workspace, workspace_bytes, true);
+}
+
 int rdyn_evaluate_all(const rdyn_chain* c, const rdyn_batch* b, const rdyn_all_outputs* o)
 {
   // (a long chain goes through the single-purpose calls below: each one decides for itself what it serves, so that a request for

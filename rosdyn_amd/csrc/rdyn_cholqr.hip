@@ -481,6 +481,7 @@ __global__ __launch_bounds__(256) void k_pgram_rows(const double* __restrict__ A
 constexpr int kMaxN1 = 112;    // widest factor of the dense kernels
 constexpr int kMaxN1Lds = 96;  // ... with their two n1 x n1 squares in LDS (147 KB); wider: the squares live in the workspace (WIDE)
 constexpr int kMaxFoldN1 = 136;  // k_cholqr_fold: two packed triangles in LDS (136 * 137 * 8 = 149 KB)
+constexpr int kMaxPanelN1 = 416;  // the column-panel route (rdyn_tsqr_wide, PANEL instantiations): squares in the workspace
 #ifndef RDYN_CHOLQR_DENSE_THREADS
 #define RDYN_CHOLQR_DENSE_THREADS 1024
 #endif
@@ -845,7 +846,10 @@ constexpr double kCholqrGammaMax = 1e4;
 // WIDE (97 .. 112 columns): the two squares do not fit the LDS -- they live in `wide_sq` (2 n1^2 doubles of the workspace: L1 / L2
 // resident; one workgroup, so its barriers order the accesses).  The factorisation itself works in registers as before (the squares are
 // only where it starts from and where it parks its rows); the element-wise passes around it run at global-memory latency.
-template <bool WIDE>
+// PANEL (the column-panel route, up to kMaxPanelN1 columns): the squares in `wide_sq` as WIDE, the factorisation of chol_with_inverse_lds
+// on them (the register form holds seven 16-wide blocks), and no round is called off -- there is no Householder stand-by to hand over to
+// at these widths: round 0 always runs, rounds 1 and 2 run when the factor kernel of the round before did not accept its result.
+template <bool WIDE, bool PANEL = false>
 __global__ __launch_bounds__(NTD) void k_cholqr_precond(const double* __restrict__ R1, const double* __restrict__ Gs, const double* __restrict__ cs,
                                                         const double* __restrict__ bbs, int n1, int col_shift, int nb_w, double row_scale,
                                                         double* __restrict__ Tout, double* __restrict__ W, double* __restrict__ Vout, int* __restrict__ zmask,
@@ -854,10 +858,11 @@ __global__ __launch_bounds__(NTD) void k_cholqr_precond(const double* __restrict
 {
   if (run_flag && *run_flag == 0) return;
   extern __shared__ __attribute__((aligned(16))) double sh[];
-  double* const A0 = WIDE ? wide_sq : sh;  // [n1][n1] column-major: R1, then T
+  constexpr int kN = PANEL ? kMaxPanelN1 : kMaxN1;
+  double* const A0 = (WIDE || PANEL) ? wide_sq : sh;  // [n1][n1] column-major: R1, then T
   double* const B = A0 + n1 * n1;          // [nc][n1]: the kept columns (or the Gram matrix being factorised), then V = T^-1
-  __shared__ double s_part[kMaxN1], s_norm[kMaxN1], s_lift[kMaxN1], s_g[kMaxN1];
-  __shared__ int s_z[kMaxN1], s_cmap[kMaxN1], s_rend[kMaxN1], s_nc;
+  __shared__ double s_part[kN], s_norm[kN], s_lift[kN], s_g[kN];
+  __shared__ int s_z[kN], s_cmap[kN], s_rend[kN], s_nc;
   const int tid = threadIdx.x;
   STAMP_P(0);
   if (Gs)
@@ -890,7 +895,8 @@ __global__ __launch_bounds__(NTD) void k_cholqr_precond(const double* __restrict
     __syncthreads();
     STAMP_P(1);
     auto chol = [&](auto... args) {
-      if constexpr (WIDE) RDYN_CHOL_WITH_INVERSE<7>(args...);
+      if constexpr (PANEL) chol_with_inverse_lds<7>(args...);
+      else if constexpr (WIDE) RDYN_CHOL_WITH_INVERSE<7>(args...);
       else RDYN_CHOL_WITH_INVERSE<6>(args...);
     };
     chol(B, A0, n1, tid, s_part, s_g, [&](int k, double d) {
@@ -1017,11 +1023,24 @@ __global__ __launch_bounds__(NTD) void k_cholqr_precond(const double* __restrict
     // factor kernel rejects it as a result by the same figure on all rows): called off when even that is hopeless
     const bool safe = gamma <= (round == 0 ? 1e10 : kCholqrGammaMax);  // (false for NaN)
     if (gamma_out) *gamma_out = gamma;
+    if constexpr (PANEL)
+    {
+      // flags [3] the width, [4 + r] round r ran, [8 + r] round r was not accepted (rounds 1 and 2 start from flags [0] and [1], which
+      // the factor kernels write; round 0 always runs)
+      if (round == 0)
+      {
+        flags[3] = n1;
+        for (int r = 0; r < 3; ++r) flags[4 + r] = flags[8 + r] = 0;
+      }
+    }
+    else
+    {
     if (round == 0) flags[2] = safe ? 1 : 0;
     if (!safe)
     {
       flags[0] = 0;  // the kernels of this round (round 1: flags[0]; round 0: flags[2]) and of the next leave at once
       flags[1] = 1;  // the stand-by runs
+    }
     }
   }
   STAMP_P(5);
@@ -1050,7 +1069,9 @@ __global__ __launch_bounds__(NTD) void k_cholqr_precond(const double* __restrict
 //   Re of the equilibrated Gram of the k pivoted columns (1 for orthogonal columns; |Re^-1|_2 <= rho sqrt(k)); rho > 4, or a kept
 //   column that turns out dependent on its left neighbours, and the round is not accepted: flags[round] = 1 (flags[0] starts round 1,
 //   flags[1] starts the stand-by Householder factorisation).  Round 0 also clears flags[1].
-template <bool WIDE>
+// PANEL: as in k_cholqr_precond; round 2 exists (started by flags[1]), T is copied from T_in after the factorisation, and the kernel
+// records flags [4 + round] (ran) and [8 + round] (not accepted) for the report.
+template <bool WIDE, bool PANEL = false>
 __global__ __launch_bounds__(NTD) void k_cholqr_factor(const double* __restrict__ G, const double* __restrict__ cvec, const double* __restrict__ bb, int n1,
                                                        int has_b, const double* __restrict__ T_in, const double* __restrict__ V, const int* __restrict__ zmask,
                                                        double* __restrict__ Rout, int* __restrict__ flags, int round, const int* __restrict__ run_flag,
@@ -1058,11 +1079,12 @@ __global__ __launch_bounds__(NTD) void k_cholqr_factor(const double* __restrict_
 {
   if (run_flag && *run_flag == 0) return;
   extern __shared__ __attribute__((aligned(16))) double sh[];
-  double* const M = WIDE ? wide_sq : sh;  // [n1][n1] column-major, upper triangle = the running Cholesky factor
+  constexpr int kN = PANEL ? kMaxPanelN1 : kMaxN1;
+  double* const M = (WIDE || PANEL) ? wide_sq : sh;  // [n1][n1] column-major, upper triangle = the running Cholesky factor
   STAMP(0);
   double* const T = M + n1 * n1;          // the identity that becomes the inverse of the Cholesky factor, then T
-  __shared__ double s_g0[kMaxN1], s_sc[kMaxN1], s_xd[kMaxN1], s_part[kMaxN1], s_gam[kMaxN1], s_wave[NTD / 64];
-  __shared__ int s_flag, s_z[kMaxN1], s_skip[kMaxN1];
+  __shared__ double s_g0[kN], s_sc[kN], s_xd[kN], s_part[kN], s_gam[kN], s_wave[NTD / 64];
+  __shared__ int s_flag, s_z[kN], s_skip[kN];
   const int tid = threadIdx.x, P = n1 - 1;
   for (int i = tid; i < n1 * n1; i += NTD)
   {
@@ -1081,13 +1103,14 @@ __global__ __launch_bounds__(NTD) void k_cholqr_factor(const double* __restrict_
   // T (global, written by the preconditioner kernel) is needed after the factorisation: the waves that only keep the barrier count
   // during it fetch their share then and hold it in registers (loaded afterwards, the dependent misses cost 8 us)
   static_assert(NTD > 384, "the waves behind the four computing and two parking ones prefetch T");
-  constexpr int kWidth = WIDE ? kMaxN1 : kMaxN1Lds;
-  constexpr int kTPre = (kWidth * kWidth + (NTD - 384) - 1) / (NTD - 384);
+  constexpr int kWidth = PANEL ? kMaxPanelN1 : (WIDE ? kMaxN1 : kMaxN1Lds);
+  constexpr int kTPre = PANEL ? 1 : (kWidth * kWidth + (NTD - 384) - 1) / (NTD - 384);  // (PANEL: unused, T is copied afterwards)
   double tpre[kTPre];
   __syncthreads();
   STAMP(1);
   auto chol = [&](auto... args) {
-    if constexpr (WIDE) RDYN_CHOL_WITH_INVERSE<7>(args...);
+    if constexpr (PANEL) chol_with_inverse_lds<7>(args...);
+    else if constexpr (WIDE) RDYN_CHOL_WITH_INVERSE<7>(args...);
     else RDYN_CHOL_WITH_INVERSE<6>(args...);
   };
   chol(M, T, n1, tid, s_sc, s_xd, [&](int k, double d) {
@@ -1112,6 +1135,7 @@ __global__ __launch_bounds__(NTD) void k_cholqr_factor(const double* __restrict_
     // a skipped pivot: null direction, its Schur complement is rounding residue -- row k of the factor is zero, nothing is eliminated
     return !skip;
   }, [&](int, double d, bool elim) { return elim ? sqrt(d > 1e-30 ? d : 1e-30) : 0.0; }, [&] {
+    if constexpr (!PANEL)
 #pragma unroll
     for (int m = 0; m < kTPre; ++m)
     {
@@ -1136,6 +1160,18 @@ __global__ __launch_bounds__(NTD) void k_cholqr_factor(const double* __restrict_
   __syncthreads();
   // the factor back into the upper triangle: M(i, j) <- row i parked in column i (the lower triangle keeps the parked rows: masked
   // below); T into its place
+  if constexpr (PANEL)
+  {
+    // (every row: the 128 row lanes of the narrow form below reach n1 <= 128 only)
+    for (int e = tid; e < n1 * n1; e += NTD)
+    {
+      const int i = e % n1, j = e / n1;
+      if (i < j) M[e] = M[i * n1 + j];
+      else if (i == j) M[e] = s_sc[i];
+      T[e] = T_in[e];
+    }
+  }
+  else
   {
     const int i = tid & 127;
     if (i < n1)
@@ -1145,13 +1181,16 @@ __global__ __launch_bounds__(NTD) void k_cholqr_factor(const double* __restrict_
         else if (i == j) M[j * n1 + i] = s_sc[i];
       }
   }
-  if (tid >= 384)
+  if constexpr (!PANEL)
   {
-#pragma unroll
-    for (int m = 0; m < kTPre; ++m)
+    if (tid >= 384)
     {
-      const int e = tid - 384 + (NTD - 384) * m;
-      if (e < n1 * n1) T[e] = tpre[m];
+#pragma unroll
+      for (int m = 0; m < kTPre; ++m)
+      {
+        const int e = tid - 384 + (NTD - 384) * m;
+        if (e < n1 * n1) T[e] = tpre[m];
+      }
     }
   }
   __syncthreads();
@@ -1233,7 +1272,14 @@ __global__ __launch_bounds__(NTD) void k_cholqr_factor(const double* __restrict_
       rho_out[0] = rho;
       rho_out[2] = gamma;
     }
-    flags[round] = s_flag;
+    if constexpr (PANEL)
+    {
+      flags[4 + round] = 1;
+      flags[8 + round] = s_flag;
+      if (round < 2) flags[round] = s_flag;  // round 0: [0] starts round 1; round 1: [1] starts round 2
+    }
+    else
+      flags[round] = s_flag;
     if (round == 0) flags[1] = 0;
   }
 }
@@ -1242,9 +1288,12 @@ __global__ __launch_bounds__(NTD) void k_cholqr_factor(const double* __restrict_
 // R = qr(R_red E_aug) by Householder reflections in LDS, one workgroup.  The product has nr = 10 n_red + K + 1 rows and
 // n1 = 10 n_joints + K + 1 columns; rows beyond the rank stay zero.  The K component columns (friction_polynomial1.h:126,
 // ideal_spring.h:64) belong to INPUT joints, which the reduced chain keeps: they pass through unchanged, like the measured torque.
-__global__ __launch_bounds__(NTD) void k_cholqr_expand(const RdynGramExpandArgs a, const double* __restrict__ R_red, double* __restrict__ Rout)
+// GLOBAL_B (the column-panel route: up to 416 x 416, far beyond the LDS): B in `bg`, n1 m doubles of workspace.
+template <bool GLOBAL_B = false>
+__global__ __launch_bounds__(NTD) void k_cholqr_expand(const RdynGramExpandArgs a, const double* __restrict__ R_red, double* __restrict__ Rout, double* bg)
 {
-  extern __shared__ __attribute__((aligned(16))) double sh[];
+  extern __shared__ __attribute__((aligned(16))) double lds_sh[];
+  double* const sh = GLOBAL_B ? bg : lds_sh;
   const int K = a.n_comp_cols, P = 10 * a.n_joints, n1 = P + K + 1, Pr = 10 * a.n_red, nr = Pr + K + 1;
   const int m = nr;
   double* const B = sh;            // [n1][m] column-major (leading dimension m)
@@ -1286,11 +1335,13 @@ __global__ __launch_bounds__(NTD) void k_cholqr_expand(const RdynGramExpandArgs 
 // the column norm by itself, the same sum in the same order), four threads per column.
 // R_new is PACKED in LDS (column j holds its min(j + 1, rows_new) entries).  R: packed in LDS too (A_GLOBAL = false, n1 <= 136), or
 // left where it is and updated in place (A_GLOBAL = true, long chains: every entry of R is read once and written once, by the same
-// thread, so nothing travels between threads through it).
-template <bool A_GLOBAL>
-__global__ __launch_bounds__(NTD) void k_cholqr_fold(const double* __restrict__ R_new, double* R, int n1, int rows_new)
+// thread, so nothing travels between threads through it).  B_GLOBAL (with A_GLOBAL; the column-panel route, where the packed R_new
+// alone exceeds the LDS): R_new packed into `bg`, workspace of n1 (n1 + 1) / 2 doubles (one workgroup: its barriers order the accesses).
+template <bool A_GLOBAL, bool B_GLOBAL = false>
+__global__ __launch_bounds__(NTD) void k_cholqr_fold(const double* __restrict__ R_new, double* R, int n1, int rows_new, double* bg)
 {
-  extern __shared__ __attribute__((aligned(16))) double sh[];
+  extern __shared__ __attribute__((aligned(16))) double lds_sh[];
+  double* const sh = B_GLOBAL ? bg : lds_sh;
   const int rn = rows_new < n1 ? rows_new : n1;
   const int tri = n1 * (n1 + 1) / 2;
   auto boff = [&](int j) { return j < rn ? j * (j + 1) / 2 : rn * (rn + 1) / 2 + (j - rn) * rn; };
@@ -1561,9 +1612,9 @@ hipError_t rdyn_launch_cholqr_expand(const RdynGramExpandArgs& a, const double* 
   const size_t lds = ((size_t)n1 * nr + nr) * sizeof(double);
   if (lds > 156 * 1024) return hipErrorInvalidValue;
   static std::atomic<uint64_t> attr{0};
-  hipError_t e = opt_in_lds_once(k_cholqr_expand, attr, 156 * 1024);
+  hipError_t e = opt_in_lds_once(k_cholqr_expand<false>, attr, 156 * 1024);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_cholqr_expand, dim3(1), dim3(NTD), lds, st, a, R_red, R);
+  hipLaunchKernelGGL(k_cholqr_expand<false>, dim3(1), dim3(NTD), lds, st, a, R_red, R, nullptr);
   return hipGetLastError();
 }
 
@@ -1583,14 +1634,53 @@ hipError_t rdyn_launch_cholqr_fold(const double* R_new, double* R, int n1, hipSt
     static std::atomic<uint64_t> attr{0};
     hipError_t e = opt_in_lds_once(k_cholqr_fold<false>, attr, 156 * 1024);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_cholqr_fold<false>, dim3(1), dim3(NTD), both, st, R_new, R, n1, rn);
+    hipLaunchKernelGGL(k_cholqr_fold<false>, dim3(1), dim3(NTD), both, st, R_new, R, n1, rn, nullptr);
     return hipGetLastError();
   }
   if (b_doubles * sizeof(double) > 156 * 1024) return hipErrorInvalidValue;
   static std::atomic<uint64_t> attr_g{0};
   hipError_t e = opt_in_lds_once(k_cholqr_fold<true>, attr_g, 156 * 1024);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_cholqr_fold<true>, dim3(1), dim3(NTD), b_doubles * sizeof(double), st, R_new, R, n1, rn);
+  hipLaunchKernelGGL(k_cholqr_fold<true>, dim3(1), dim3(NTD), b_doubles * sizeof(double), st, R_new, R, n1, rn, nullptr);
+  return hipGetLastError();
+}
+
+// ---- the column-panel route (rdyn_tsqr_wide): the dense steps up to kMaxPanelN1 columns, their squares in the workspace
+int rdyn_cholqr_panel_max_cols() { return kMaxPanelN1; }
+
+hipError_t rdyn_launch_cholqr_precond_panel(const double* R1, const double* Gs, const double* cs, const double* bbs, int n1, int nb_w, double row_scale,
+                                            double* T, double* W, double* V, int* zmask, int* flags, int round, const int* run_flag,
+                                            double* gamma_out, double* wide_sq, hipStream_t st)
+{
+  if (n1 < 2 || n1 > kMaxPanelN1 || 16 * nb_w < n1 || !wide_sq || round < 0 || round > 2) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((k_cholqr_precond<true, true>), dim3(1), dim3(NTD), 0, st, R1, Gs, cs, bbs, n1, 0, nb_w, row_scale, T, W, V, zmask, flags, round,
+                     run_flag, gamma_out, wide_sq);
+  return hipGetLastError();
+}
+
+hipError_t rdyn_launch_cholqr_factor_panel(const double* G, const double* c, const double* bb, int n1, int has_b, const double* T, const double* V,
+                                           const int* zmask, double* R, int* flags, int round, const int* run_flag, double* rho_out, double* wide_sq,
+                                           hipStream_t st)
+{
+  if (n1 < 2 || n1 > kMaxPanelN1 || !wide_sq || round < 0 || round > 2) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((k_cholqr_factor<true, true>), dim3(1), dim3(NTD), 0, st, G, c, bb, n1, has_b, T, V, zmask, R, flags, round, run_flag, rho_out,
+                     wide_sq);
+  return hipGetLastError();
+}
+
+// k_cholqr_expand with B in the workspace (scratch: (10 n_joints + K + 1) (10 n_red + K + 1) doubles)
+hipError_t rdyn_launch_cholqr_expand_global(const RdynGramExpandArgs& a, const double* R_red, double* R, double* scratch, hipStream_t st)
+{
+  if (!scratch) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_cholqr_expand<true>, dim3(1), dim3(NTD), 0, st, a, R_red, R, scratch);
+  return hipGetLastError();
+}
+
+// R <- qr([R ; R_new]) with both triangles in global memory (scratch: n1 (n1 + 1) / 2 doubles)
+hipError_t rdyn_launch_cholqr_fold_global(const double* R_new, double* R, int n1, double* scratch, hipStream_t st)
+{
+  if (n1 < 1 || !scratch) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((k_cholqr_fold<true, true>), dim3(1), dim3(NTD), 0, st, R_new, R, n1, n1, scratch);
   return hipGetLastError();
 }
 

@@ -311,6 +311,39 @@ hipError_t rdyn_launch_cholqr_factor(const double* G, const double* c, const dou
 // factor of the reduced chain -> factor of the chain: R = qr(R_red diag(E, I_K, 1)) (a.X, a.red_of, a.n_joints, a.n_red, a.n_comp_cols used)
 hipError_t rdyn_launch_cholqr_expand(const RdynGramExpandArgs& a, const double* R_red, double* R, hipStream_t st);
 size_t rdyn_cholqr_expand_lds_bytes(int n_joints, int n_red, int n_comp_cols);  // dynamic LDS of that launch (limit: 156 KB)
+// the column-panel route (rdyn_tsqr_wide): the same dense steps up to rdyn_cholqr_panel_max_cols() columns, their two squares in
+// wide_sq (2 n1^2 doubles of workspace), rounds 0..2 (round r > 0 started by flags[r - 1]); flags [3] n1, [4 + r] round r ran, [8 + r] not accepted
+int rdyn_cholqr_panel_max_cols();
+hipError_t rdyn_launch_cholqr_precond_panel(const double* R1, const double* Gs, const double* cs, const double* bbs, int n1, int nb_w, double row_scale,
+                                            double* T, double* W, double* V, int* zmask, int* flags, int round, const int* run_flag,
+                                            double* gamma_out, double* wide_sq, hipStream_t st);
+hipError_t rdyn_launch_cholqr_factor_panel(const double* G, const double* c, const double* bb, int n1, int has_b, const double* T, const double* V,
+                                           const int* zmask, double* R, int* flags, int round, const int* run_flag, double* rho_out, double* wide_sq,
+                                           hipStream_t st);
+hipError_t rdyn_launch_cholqr_expand_global(const RdynGramExpandArgs& a, const double* R_red, double* R, double* scratch, hipStream_t st);
+hipError_t rdyn_launch_cholqr_fold_global(const double* R_new, double* R, int n1, double* scratch, hipStream_t st);
+// Q = X W for an upper-triangular W in the operand order of k_cholqr_precond (nb_w = ceil(n1 / 16) blocks), 64 rows per workgroup
+// (rdyn_panel_trmm.hip).  X: rows x n1 column-major ([A | b]: columns < n_cols from A (lda), column n_cols from b if b != null); Q (ldq)
+// may BE A (in place, ldq == lda, b null) -- every workgroup reads its rows whole before it writes them.  The zero band of a chunk image:
+// rows [j row_block, (j + 1) row_block) are zero left of column first_col[j] (row_block 0: none).
+struct RdynPanelTrmmArgs
+{
+  const double* A;
+  const double* b;
+  int64_t rows, lda;
+  int n_cols, n1;
+  double* Q;
+  int64_t ldq;
+  const double* W;
+  const int* run_flag;  // null, or a device word: 0 = leave at once
+  int64_t row_block;
+  int first_col[RDYN_MAX_JOINTS];
+};
+hipError_t rdyn_launch_panel_trmm(const RdynPanelTrmmArgs& a, hipStream_t st);
+// the row subsample of a preconditioner: every group_stride-th 16-row group of [A | b] (b may be null) into Q (ldq >= its rows)
+hipError_t rdyn_launch_panel_gather(const double* A, const double* b, int64_t rows, int64_t lda, int n_cols, int64_t group_stride, double* Q,
+                                    int64_t ldq, hipStream_t st);
+int64_t rdyn_panel_gather_rows(int64_t rows, int64_t group_stride);  // rows of that subsample
 // tall-skinny QR (rdyn_tsqr.hip): R factor of [A | b] without forming A'A
 int rdyn_tsqr_padded_cols(int n_cols_with_rhs);              // 16 / 32 / 48 / 64, 0 = unsupported
 size_t rdyn_tsqr_workspace_doubles(int nc, int blocks);
@@ -354,6 +387,7 @@ struct RdynPanelGramArgs
   // rows [j * row_block, (j + 1) * row_block) are zero in the columns < first_col[j] (any order); row_block == 0: no structure
   int64_t row_block;
   int first_col[RDYN_MAX_JOINTS];
+  const int* run_flag;  // null, or a device word: 0 = both kernels leave at once (the rounds of rdyn_tsqr_wide)
 };
 int rdyn_panel_gram_pairs(int P);
 int rdyn_panel_gram_blocks(int P);  // row-slice workgroups per pair

@@ -170,9 +170,11 @@ __device__ __forceinline__ void pair_of(int pair, int& I, int& J)
   I = pair - J * (J + 1) / 2;
 }
 
-template <bool BANDS>
+// GATED: the pass of a CholeskyQR round that may not be needed (rdyn_tsqr_wide): leaves at once when *run_flag == 0
+template <bool BANDS, bool GATED = false>
 __global__ __launch_bounds__(256) void k_panel_gram(const RdynPanelGramArgs a)
 {
+  if (GATED && *a.run_flag == 0) return;
   __shared__ double red[PB * PB * 256];
   const int pair = blockIdx.y;
   int I, J;
@@ -186,8 +188,10 @@ __global__ __launch_bounds__(256) void k_panel_gram(const RdynPanelGramArgs a)
 // sums the slabs of every pair (fixed order) and scatters the tiles into G (P x P, both triangles), c, bb: one workgroup per 32 slab
 // elements, FG groups of 32 threads split the row-slice workgroups, the groups summed through LDS in fixed order (as k_gram_finish)
 constexpr int FG = 32;
+template <bool GATED = false>
 __global__ __launch_bounds__(32 * FG) void k_panel_gram_finish(const RdynPanelGramArgs a, int pairs, int gx)
 {
+  if (GATED && *a.run_flag == 0) return;
   const int e_loc = threadIdx.x & 31, grp = threadIdx.x >> 5;
   const int64_t i = (int64_t)blockIdx.x * 32 + e_loc;
   const int pair = (int)(i / SLAB), loc = (int)(i % SLAB);
@@ -258,7 +262,14 @@ size_t rdyn_panel_gram_slab_bytes(int P) { return (size_t)rdyn_panel_gram_pairs(
 hipError_t rdyn_launch_panel_gram(const RdynPanelGramArgs& a, hipStream_t st)
 {
   const dim3 grid(rdyn_panel_gram_blocks(a.P), rdyn_panel_gram_pairs(a.P));
-  if (a.row_block > 0)
+  if (a.run_flag)
+  {
+    if (a.row_block > 0)
+      hipLaunchKernelGGL((k_panel_gram<true, true>), grid, dim3(256), 0, st, a);
+    else
+      hipLaunchKernelGGL((k_panel_gram<false, true>), grid, dim3(256), 0, st, a);
+  }
+  else if (a.row_block > 0)
     hipLaunchKernelGGL(k_panel_gram<true>, grid, dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL(k_panel_gram<false>, grid, dim3(256), 0, st, a);
@@ -268,6 +279,10 @@ hipError_t rdyn_launch_panel_gram(const RdynPanelGramArgs& a, hipStream_t st)
 hipError_t rdyn_launch_panel_gram_finish(const RdynPanelGramArgs& a, hipStream_t st)
 {
   const int pairs = rdyn_panel_gram_pairs(a.P);
-  hipLaunchKernelGGL(k_panel_gram_finish, dim3((unsigned)((int64_t)pairs * SLAB / 32)), dim3(32 * FG), 0, st, a, pairs, rdyn_panel_gram_blocks(a.P));
+  const dim3 grid((unsigned)((int64_t)pairs * SLAB / 32));
+  if (a.run_flag)
+    hipLaunchKernelGGL(k_panel_gram_finish<true>, grid, dim3(32 * FG), 0, st, a, pairs, rdyn_panel_gram_blocks(a.P));
+  else
+    hipLaunchKernelGGL(k_panel_gram_finish<false>, grid, dim3(32 * FG), 0, st, a, pairs, rdyn_panel_gram_blocks(a.P));
   return hipGetLastError();
 }

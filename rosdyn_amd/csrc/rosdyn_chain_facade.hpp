@@ -679,6 +679,33 @@ public:
     chk(rdyn_identification_gram_wide(m_h, comps.data(), (int)comps.size(), &b, tau_meas, G, c, bb, accumulate ? 1 : 0, chunk_samples,
                                       workspace, workspace_bytes));
   }
+  // the R factors beyond 112 columns (column-panel CholeskyQR; include/rdyn.h: rdyn_regressor_tsqr_wide / rdyn_identification_tsqr_wide);
+  // shapes the narrow calls serve are handed to them; chunk_samples = 0: the default chunk
+  size_t getRegressorTsqrWideWorkspaceBytes(int64_t chunk_samples = 0) const { return rdyn_regressor_tsqr_wide_workspace_bytes(m_h, chunk_samples); }
+  void getRegressorTsqrWideBatch(const rdyn_batch& b, const double* tau_meas, double* R1, bool accumulate, void* workspace, size_t workspace_bytes,
+                                 int64_t chunk_samples = 0) const
+  {
+    chk(rdyn_regressor_tsqr_wide(m_h, &b, tau_meas, R1, accumulate ? 1 : 0, chunk_samples, workspace, workspace_bytes));
+  }
+  size_t getIdentificationTsqrWideWorkspaceBytes(const std::vector<rdyn_component>& comps, int64_t chunk_samples = 0) const
+  {
+    return rdyn_identification_tsqr_wide_workspace_bytes(m_h, comps.data(), (int)comps.size(), chunk_samples);
+  }
+  void getIdentificationTsqrWideBatch(const std::vector<rdyn_component>& comps, const rdyn_batch& b, const double* tau_meas, double* R1,
+                                      bool accumulate, void* workspace, size_t workspace_bytes, int64_t chunk_samples = 0) const
+  {
+    chk(rdyn_identification_tsqr_wide(m_h, comps.data(), (int)comps.size(), &b, tau_meas, R1, accumulate ? 1 : 0, chunk_samples, workspace,
+                                      workspace_bytes));
+  }
+  // what the last wide factor call on `workspace` did (rdyn_tsqr_wide_last_report): route 2, the accepted round (3: none), gamma / rho
+  rdyn_tsqr_wide_report getTsqrWideReport(const void* workspace, int device = -1, void* stream = nullptr,
+                                          const std::vector<rdyn_component>& comps = std::vector<rdyn_component>()) const
+  {
+    rdyn_tsqr_wide_report rep;
+    const int n1 = 10 * rdyn_chain_joints_number(m_h) + (comps.empty() ? 0 : rdyn_components_columns(comps.data(), (int)comps.size())) + 1;
+    chk(rdyn_tsqr_wide_last_report(n1, workspace, device, stream, &rep));
+    return rep;
+  }
   // the same identification step WITHOUT forming the normal equations: R1 = [R d; 0 rho] of [Y | C | tau_meas] by tall-skinny QR
   // (condition number not squared; include/rdyn.h: rdyn_regressor_tsqr / rdyn_identification_tsqr), solved by solveRFactor
   size_t getIdentificationTsqrWorkspaceBytes(const std::vector<rdyn_component>& comps) const

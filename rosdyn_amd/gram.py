@@ -232,6 +232,43 @@ def tsqr_last_report(n1, rows, workspace):
     return dict(route=rep.route, stage=rep.stage, n_deferred=rep.n_deferred, gamma=tuple(rep.gamma), rho=tuple(rep.rho))
 
 
+def tsqr_wide(A, b=None, out=None, accumulate=False, workspace=None, rows=None):
+    """rdyn_tsqr_wide: tsqr() for up to 416 columns with the right-hand side (column-panel CholeskyQR; narrower shapes go to rdyn_tsqr).
+    A: (P, lda) torch.float64 CUDA tensor = column-major lda x P matrix of which the first `rows` rows (default: all) are factored;
+    b: (rows,) or None.  Returns R1 as a (n1, n1) tensor in MATH layout, n1 = P + (b is not None)."""
+    import torch
+    assert A.is_cuda and A.dtype == torch.float64 and A.dim() == 2 and A.is_contiguous()
+    P, lda = A.shape
+    rows = lda if rows is None else int(rows)
+    n1 = P + (1 if b is not None else 0)
+    buf = torch.zeros((n1, n1), dtype=torch.float64, device=A.device) if out is None else out.t().contiguous()
+    nbytes = lib().rdyn_tsqr_wide_workspace_bytes(n1)
+    if nbytes == 0:
+        raise ValueError("rdyn_tsqr_wide: at most 416 columns (right-hand side included)")
+    if workspace is None:
+        workspace = torch.empty((nbytes,), dtype=torch.uint8, device=A.device)
+    if b is not None:
+        assert b.is_cuda and b.dtype == torch.float64 and b.numel() >= rows and b.is_contiguous()
+    check(lib().rdyn_tsqr_wide(A.data_ptr(), rows, lda, P, b.data_ptr() if b is not None else None, buf.data_ptr(), 1 if accumulate else 0,
+                               workspace.data_ptr(), workspace.numel(), A.device.index if A.device.index is not None else -1,
+                               torch.cuda.current_stream(A.device).cuda_stream))
+    if out is not None:
+        out.copy_(buf.t())
+        return out
+    return buf.t()
+
+
+def tsqr_wide_last_report(n1, workspace):
+    """rdyn_tsqr_wide_last_report: what the last wide factor call of width n1 that used `workspace` did; synchronises.
+    route 2 = column-panel CholeskyQR (0: the width is served by the narrow calls); stage 0..2 = the accepted round, 3 = none."""
+    import torch
+    from ._lib import RdynTsqrWideReport
+    rep = RdynTsqrWideReport()
+    check(lib().rdyn_tsqr_wide_last_report(int(n1), workspace.data_ptr(), workspace.device.index or 0,
+                                           torch.cuda.current_stream(workspace.device).cuda_stream, C.byref(rep)))
+    return dict(route=rep.route, stage=rep.stage, n_deferred=rep.n_deferred, gamma=tuple(rep.gamma), rho=tuple(rep.rho))
+
+
 def tsqr_combine_host(factors):
     """rdyn_tsqr_combine_host: folds upper-triangular factors (list of (n, n) numpy arrays in math layout) into one."""
     n = factors[0].shape[0]
