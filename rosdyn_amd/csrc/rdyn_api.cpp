@@ -1143,30 +1143,49 @@ size_t rdyn_regressor_gram_workspace_bytes(const rdyn_chain* c, int64_t chunk_sa
   return base + (c->reduced ? reduce_tmp_bytes(10 * c->reduced->n_joints()) : 0);
 }
 
-// Chains with non-input joints (default paths, chunk_samples <= 0): the regressor -> Gram kernels run on the reduced companion
-// (rdyn_chain.hpp: every joint an input joint -- the fastest instantiations, 10 n instead of 10 nJ columns), then G = E' G_red E.
-// chunk_samples > 0 keeps the chain as it is (the reference ordering of the two-kernel path).
-static int gram_through_reduced(const rdyn_chain* c, const rdyn_component* comps, int n_comps, int K, const rdyn_batch* b, const double* tau_meas,
-                                double* G, double* cvec, double* bb, int accumulate, void* workspace, size_t need_bytes)
+// the expansion of the reduced companion (n_red joints, K component columns riding along) back onto chain c: everything of
+// RdynGramExpandArgs but the matrices it reads and writes
+static int fill_expand_args(const rdyn_chain* c, int n_red, int K, RdynGramExpandArgs* ea)
+{
+  memset(ea, 0, sizeof *ea);
+  int st = device_expand(c, &ea->X);
+  if (st != RDYN_OK) return st;
+  for (int f = 0; f < c->n_joints(); ++f) ea->red_of[f] = c->red_of[f];
+  ea->n_joints = c->n_joints();
+  ea->n_red = n_red;
+  ea->n_comp_cols = K;
+  return RDYN_OK;
+}
+
+// the normal equations of no samples: zeros, or nothing when accumulating
+static int zero_normal_equations(double* G, double* cvec, double* bb, int cols, int accumulate, hipStream_t stream)
+{
+  if (accumulate) return RDYN_OK;
+  RDYN_HIP_TRY(hipMemsetAsync(G, 0, sizeof(double) * cols * cols, stream));
+  if (cvec) RDYN_HIP_TRY(hipMemsetAsync(cvec, 0, sizeof(double) * cols, stream));
+  if (bb) RDYN_HIP_TRY(hipMemsetAsync(bb, 0, sizeof(double), stream));
+  return RDYN_OK;
+}
+
+// Chains with non-input joints: the normal equations of the reduced companion (rdyn_chain.hpp: every joint an input joint -- the
+// fastest instantiations, 10 n instead of 10 nJ columns) into the tail of the workspace, then G = E' G_red E (k_gram_expand).
+// companion(G_red, c_red, bb_red, workspace, bytes) is the narrow or the wide call on c->reduced; it gets the workspace in front of the tail.
+typedef std::function<int(double* G_red, double* c_red, double* bb_red, void* workspace, size_t workspace_bytes)> CompanionGram;
+static int gram_through_reduced(const rdyn_chain* c, int K, const rdyn_batch* b, double* G, double* cvec, double* bb, int accumulate, void* workspace,
+                                size_t need_bytes, const CompanionGram& companion)
 {
   const rdyn_chain* r = c->reduced.get();
   const int Cr = 10 * r->n_joints() + K;
   const size_t tmp = reduce_tmp_bytes(Cr);
   double* Gr = (double*)((char*)workspace + need_bytes - tmp);
-  int st = n_comps > 0 ? rdyn_identification_gram(r, comps, n_comps, b, tau_meas, Gr, Gr + (size_t)Cr * Cr, Gr + (size_t)Cr * Cr + Cr, 0, workspace, need_bytes - tmp)
-                       : rdyn_regressor_gram(r, b, tau_meas, Gr, Gr + (size_t)Cr * Cr, Gr + (size_t)Cr * Cr + Cr, 0, 0, workspace, need_bytes - tmp);
+  int st = companion(Gr, Gr + (size_t)Cr * Cr, Gr + (size_t)Cr * Cr + Cr, workspace, need_bytes - tmp);
   if (st != RDYN_OK) return st;
   RdynGramExpandArgs ea;
-  memset(&ea, 0, sizeof ea);
-  st = device_expand(c, &ea.X);
+  st = fill_expand_args(c, r->n_joints(), K, &ea);
   if (st != RDYN_OK) return st;
   ea.G_red = Gr;
   ea.c_red = Gr + (size_t)Cr * Cr;
   ea.bb_red = Gr + (size_t)Cr * Cr + Cr;
-  for (int f = 0; f < c->n_joints(); ++f) ea.red_of[f] = c->red_of[f];
-  ea.n_joints = c->n_joints();
-  ea.n_red = r->n_joints();
-  ea.n_comp_cols = K;
   ea.add_to_output = accumulate ? 1 : 0;
   ea.G = G;
   ea.c = cvec;
@@ -1174,6 +1193,109 @@ static int gram_through_reduced(const rdyn_chain* c, const rdyn_component* comps
   RDYN_HIP_TRY(rdyn_launch_gram_expand(ea, (hipStream_t)b->stream));
   return RDYN_OK;
 }
+
+// The element-major chunk image [Y (10 nJ) | C (K) | tau_meas] of cnt samples s0, s0 + S, s0 + 2 S, ... (S = sample_stride): rows
+// j * cnt + s, lda = n * cnt, tau_meas in column `cols` (without tau_meas that column is not written).  Y by k_long_regressor
+// (rdyn_long_local.hip) when dl is set -- more input joints than the unrolled kernels sweep --, by the element-major regressor sweep
+// otherwise; the component columns behind it.  The sweep does not store the structural zeros (rows of input joint j left of column
+// 10 * its chain index), and 16-row groups that straddle two row blocks read a few of them: unless `clear` is off, write() zeroes the
+// whole image first wherever its layout changes (first chunk, shorter last chunk).
+struct ChunkImage
+{
+  const rdyn_chain* c;
+  const rdyn_batch* b;
+  const double* tau_meas;
+  double* image;
+  int cols;
+  const RdynComponentArgs* ca;  // filled by fill_components: n_comps of them, K columns
+  int n_comps, K;
+  const RdynChainConst* dc = nullptr;
+  const RdynLongChainConst* dl = nullptr;
+  bool clear = true;
+  int64_t cleared_cnt = -1;  // the chunk length the image was last zeroed for
+
+  ChunkImage(const rdyn_chain* c, const rdyn_batch* b, const double* tau_meas, double* image, int cols, const RdynComponentArgs* ca = nullptr,
+             int n_comps = 0, int K = 0)
+      : c(c), b(b), tau_meas(tau_meas), image(image), cols(cols), ca(ca), n_comps(n_comps), K(K)
+  {
+  }
+  // the chain constants of the writer, looked up once per call
+  int bind(bool long_kernel) { return long_kernel ? device_const_long(c, &dl) : device_const(c, &dc); }
+  int write(int64_t s0, int64_t cnt, int64_t sample_stride, hipStream_t stream)
+  {
+    const int n = c->n_active();
+    if (clear && cnt != cleared_cnt)
+    {
+      RDYN_HIP_TRY(hipMemsetAsync(image, 0, sizeof(double) * (size_t)cnt * n * (cols + 1), stream));
+      cleared_cnt = cnt;
+    }
+    const int64_t in_step = (b->layout == RDYN_LAYOUT_SAMPLE_MAJOR) ? n : 1;  // pointer advance per sample
+    const double* const q = b->q + s0 * in_step;
+    const double* const dq = b->dq + s0 * in_step;
+    const double* const ddq = b->ddq + s0 * in_step;
+    const double* const bcol = tau_meas ? tau_meas + s0 * in_step : nullptr;
+    int64_t in_ss, in_sj;
+    rec_strides(b, n, &in_ss, &in_sj);  // element-major: the joint stride stays the FULL batch's N
+    in_ss *= sample_stride;
+    if (dl)
+    {
+      RdynLongLocalArgs a;
+      memset(&a, 0, sizeof a);
+      a.chain_long = dl;
+      a.q = q;
+      a.dq = dq;
+      a.ddq = ddq;
+      a.bcol = bcol;
+      a.bcol_col = cols;
+      a.n_samples = cnt;
+      a.in_ss = in_ss;
+      a.in_sj = in_sj;
+      a.Y = image;
+      a.y_ss = 1;
+      a.y_sr = cnt;
+      a.y_sc = (int64_t)n * cnt;
+      a.n_active = n;
+      RDYN_HIP_TRY(rdyn_launch_long_local(RDYN_MODE_REGRESSOR, c->n_joints(), a, stream));
+    }
+    else
+    {
+      RdynSweepArgs a;
+      memset(&a, 0, sizeof a);
+      a.chain = dc;
+      a.q = q;
+      a.dq = dq;
+      a.ddq = ddq;
+      a.bcol = bcol;
+      a.bcol_col = cols;
+      a.n_samples = cnt;
+      a.in_ss = in_ss;
+      a.in_sj = in_sj;
+      a.Y = image;
+      a.y_ss = 1;
+      a.y_sr = cnt;
+      a.y_sc = (int64_t)n * cnt;
+      RDYN_HIP_TRY(rdyn_launch_local_sweep(c->n_joints(), RDYN_MODE_REGRESSOR_GRAM, a, stream));
+    }
+    if (K > 0)
+    {
+      RdynComponentArgs cc = *ca;
+      cc.q = q;
+      cc.dq = dq;
+      cc.n_samples = cnt;
+      cc.in_ss = in_ss;
+      cc.in_sj = in_sj;
+      cc.n_active = n;
+      cc.n_comps = n_comps;
+      cc.C = image + (int64_t)10 * c->n_joints() * n * cnt;
+      cc.c_ss = 1;
+      cc.c_sr = cnt;
+      cc.c_sc = (int64_t)n * cnt;
+      cc.tau = nullptr;
+      RDYN_HIP_TRY(rdyn_launch_components(cc, stream));
+    }
+    return RDYN_OK;
+  }
+};
 
 // the chain the tile kernels sweep: the sorted view when the input joints were listed out of chain order (rdyn_chain.hpp)
 static const rdyn_chain* ordered(const rdyn_chain* c) { return c->sorted ? c->sorted.get() : c; }
@@ -1260,6 +1382,10 @@ int rdyn_regressor_gram(const rdyn_chain* c, const rdyn_batch* b, const double* 
     return RDYN_ERR_INVALID_ARGUMENT;
   }
   const int n = c->n_active(), P = 10 * c->n_joints();
+  // chains with non-input joints: the companion's normal equations (default chunking)
+  auto companion = [&](double* Gr, double* cr, double* bbr, void* ws, size_t ws_bytes) {
+    return rdyn_regressor_gram(c->reduced.get(), b, tau_meas, Gr, cr, bbr, 0, 0, ws, ws_bytes);
+  };
   if (long_images)
   {
     const int64_t chunk = default_chunk(chunk_samples), N = b->n_samples;
@@ -1272,40 +1398,19 @@ int rdyn_regressor_gram(const rdyn_chain* c, const rdyn_batch* b, const double* 
     st = g.enter(b->device);
     if (st != RDYN_OK) return st;
     hipStream_t stream = (hipStream_t)b->stream;
-    if (N == 0)
-    {
-      if (!accumulate)
-      {
-        RDYN_HIP_TRY(hipMemsetAsync(G, 0, sizeof(double) * P * P, stream));
-        if (cvec) RDYN_HIP_TRY(hipMemsetAsync(cvec, 0, sizeof(double) * P, stream));
-        if (bb) RDYN_HIP_TRY(hipMemsetAsync(bb, 0, sizeof(double), stream));
-      }
-      return RDYN_OK;
-    }
+    if (N == 0) return zero_normal_equations(G, cvec, bb, P, accumulate, stream);
     double* const slabs = (double*)workspace;
-    double* const image = (double*)((char*)workspace + gram_slab_bytes(P));
-    const int64_t in_step = (b->layout == RDYN_LAYOUT_SAMPLE_MAJOR) ? n : 1;
+    ChunkImage im(c, b, tau_meas, (double*)((char*)workspace + gram_slab_bytes(P)), P);
+    im.clear = false;  // k_long_regressor stores the structural zeros, and without tau_meas k_gram reads no column P
+    st = im.bind(true);
+    if (st != RDYN_OK) return st;
     for (int64_t s0 = 0; s0 < N; s0 += chunk)
     {
       const int64_t cnt = (N - s0 < chunk) ? (N - s0) : chunk;
-      RdynLongLocalArgs a;
-      memset(&a, 0, sizeof a);
-      st = device_const_long(c, &a.chain_long);
+      st = im.write(s0, cnt, 1, stream);
       if (st != RDYN_OK) return st;
-      a.q = b->q + s0 * in_step;
-      a.dq = b->dq + s0 * in_step;
-      a.ddq = b->ddq + s0 * in_step;
-      a.bcol = tau_meas ? tau_meas + s0 * in_step : nullptr;
-      a.bcol_col = P;
-      a.n_samples = cnt;
-      rec_strides(b, n, &a.in_ss, &a.in_sj);  // element-major: the joint stride stays the FULL batch's N
-      a.Y = image;                             // dense element-major image of this chunk: rows j * cnt + s, lda = n * cnt
-      a.y_ss = 1;
-      a.y_sr = cnt;
-      a.y_sc = (int64_t)n * cnt;
-      RDYN_HIP_TRY(rdyn_launch_long_local(RDYN_MODE_REGRESSOR, c->n_joints(), a, stream));
-      st = gram_launch(image, (int64_t)n * cnt, (int64_t)n * cnt, P, tau_meas ? image + (int64_t)P * n * cnt : nullptr, G, cvec, bb, s0 > 0 ? 1 : 0,
-                       s0 + cnt >= N, accumulate ? 1 : 0, slabs, stream);
+      st = gram_launch(im.image, (int64_t)n * cnt, (int64_t)n * cnt, P, tau_meas ? im.image + (int64_t)P * n * cnt : nullptr, G, cvec, bb,
+                       s0 > 0 ? 1 : 0, s0 + cnt >= N, accumulate ? 1 : 0, slabs, stream);
       if (st != RDYN_OK) return st;
     }
     return RDYN_OK;
@@ -1321,17 +1426,8 @@ int rdyn_regressor_gram(const rdyn_chain* c, const rdyn_batch* b, const double* 
     DeviceGuard g;
     st = g.enter(b->device);
     if (st != RDYN_OK) return st;
-    if (b->n_samples == 0)
-    {
-      if (!accumulate)
-      {
-        RDYN_HIP_TRY(hipMemsetAsync(G, 0, sizeof(double) * P * P, (hipStream_t)b->stream));
-        if (cvec) RDYN_HIP_TRY(hipMemsetAsync(cvec, 0, sizeof(double) * P, (hipStream_t)b->stream));
-        if (bb) RDYN_HIP_TRY(hipMemsetAsync(bb, 0, sizeof(double), (hipStream_t)b->stream));
-      }
-      return RDYN_OK;
-    }
-    return gram_through_reduced(c, nullptr, 0, 0, b, tau_meas, G, cvec, bb, accumulate, workspace, need);
+    if (b->n_samples == 0) return zero_normal_equations(G, cvec, bb, P, accumulate, (hipStream_t)b->stream);
+    return gram_through_reduced(c, 0, b, G, cvec, bb, accumulate, workspace, need, companion);
   }
   if (rdyn_gram_blocks_for(P) > 7)
   {
@@ -1354,19 +1450,10 @@ int rdyn_regressor_gram(const rdyn_chain* c, const rdyn_batch* b, const double* 
   double* slabs = (double*)workspace;
   double* scratch = (double*)((char*)workspace + gram_slab_bytes(P));
   const int64_t N = b->n_samples;
-  const int64_t in_step = (b->layout == RDYN_LAYOUT_SAMPLE_MAJOR) ? n : 1;  // pointer advance per sample
-  if (N == 0)
-  {
-    if (!accumulate)
-    {
-      RDYN_HIP_TRY(hipMemsetAsync(G, 0, sizeof(double) * P * P, stream));
-      if (cvec) RDYN_HIP_TRY(hipMemsetAsync(cvec, 0, sizeof(double) * P, stream));
-      if (bb) RDYN_HIP_TRY(hipMemsetAsync(bb, 0, sizeof(double), stream));
-    }
-    return RDYN_OK;
-  }
+  if (N == 0) return zero_normal_equations(G, cvec, bb, P, accumulate, stream);
+  // (chunk_samples > 0 keeps the chain as it is: the reference ordering of the two-kernel path)
   if (c->reduced && chunk_samples <= 0 && !probe_env("RDYN_GRAM_NO_REDUCE"))
-    return gram_through_reduced(c, nullptr, 0, 0, b, tau_meas, G, cvec, bb, accumulate, workspace, rdyn_regressor_gram_workspace_bytes(c, chunk));
+    return gram_through_reduced(c, 0, b, G, cvec, bb, accumulate, workspace, rdyn_regressor_gram_workspace_bytes(c, chunk), companion);
   // structural zero band of every row block (input joint j): columns < 10 * chain index of joint j
   int first_col[RDYN_MAX_SWEPT_JOINTS];
   for (int j = 0; j < n; ++j) first_col[j] = 10 * c->active[j];
@@ -1461,32 +1548,13 @@ int rdyn_regressor_gram(const rdyn_chain* c, const rdyn_batch* b, const double* 
     RDYN_HIP_TRY(rdyn_launch_gram_finish(ga, blocks, stream));
     return RDYN_OK;
   }
-  int64_t prev_cnt = -1;
+  ChunkImage im(c, b, tau_meas, scratch, P);
+  im.dc = dc;
   for (int64_t s0 = 0; s0 < N; s0 += chunk)
   {
     const int64_t cnt = (N - s0 < chunk) ? (N - s0) : chunk;
-    if (cnt != prev_cnt)
-    {
-      // The sweep kernel does not store the zeros that k_gram never loads; where the image layout changes (first
-      // chunk, shorter last chunk) positions that are unwritten zeros must not hold stale data (16-row groups that
-      // straddle two row blocks read a few of them).
-      RDYN_HIP_TRY(hipMemsetAsync(scratch, 0, sizeof(double) * (size_t)cnt * n * (P + 1), stream));
-      prev_cnt = cnt;
-    }
-    RdynSweepArgs a;
-    memset(&a, 0, sizeof a);
-    a.chain = dc;
-    a.q = b->q + s0 * in_step;
-    a.dq = b->dq + s0 * in_step;
-    a.ddq = b->ddq + s0 * in_step;
-    a.bcol = tau_meas ? tau_meas + s0 * in_step : nullptr;
-    a.n_samples = cnt;
-    rec_strides(b, n, &a.in_ss, &a.in_sj);  // element-major: joint stride stays the FULL batch's N
-    a.Y = scratch;                          // element-major image of this chunk: rows j * cnt + s, lda = n * cnt
-    a.y_ss = 1;
-    a.y_sr = cnt;
-    a.y_sc = (int64_t)n * cnt;
-    RDYN_HIP_TRY(rdyn_launch_local_sweep(c->n_joints(), RDYN_MODE_REGRESSOR_GRAM, a, stream));
+    st = im.write(s0, cnt, 1, stream);
+    if (st != RDYN_OK) return st;
     const bool last = (s0 + cnt >= N);
     st = gram_launch(scratch, (int64_t)n * cnt, (int64_t)n * cnt, P, tau_meas ? scratch + (int64_t)P * n * cnt : nullptr, G, cvec, bb,
                      s0 > 0 ? 1 : 0, last, accumulate ? 1 : 0, slabs, stream, cnt, first_col, n);
@@ -1933,6 +2001,19 @@ static bool tsqr_plan(const rdyn_chain* c, const rdyn_component* comps, int n_co
   return true;
 }
 
+// [A C b] = [A_red C b] diag(E, I_K, 1): R = qr(R_swept diag(E, I_K, 1)), folded into the caller's factor through `scratch` (n1 x n1
+// doubles) when accumulating
+static int expand_factor(const rdyn_chain* c, const TsqrPlan& p, const double* R_swept, double* R, int accumulate, double* scratch, hipStream_t stream)
+{
+  RdynGramExpandArgs ea;
+  int st = fill_expand_args(c, p.nJ, p.K, &ea);
+  if (st != RDYN_OK) return st;
+  double* const R_exp = accumulate ? scratch : R;
+  RDYN_HIP_TRY(rdyn_launch_cholqr_expand(ea, R_swept, R_exp, stream));
+  if (accumulate) RDYN_HIP_TRY(rdyn_launch_cholqr_fold(R_exp, R, p.n1, stream, p.n1s));
+  return RDYN_OK;
+}
+
 // swept_only: stop at the factor of the SWEPT chain (n1s x n1s into R, no expansion, no accumulation): the multi-device form gathers
 // and folds these -- the smaller payload, and no limit on the width of the expanded factor -- and expands once per device
 static int regressor_tsqr_run(const rdyn_chain* c, const rdyn_component* comps, int n_comps, const rdyn_batch* b, const double* tau_meas, double* R,
@@ -1990,91 +2071,21 @@ static int regressor_tsqr_run(const rdyn_chain* c, const rdyn_component* comps, 
     double* const img = ws + p.img_off;
     double* const R_swept = expand ? ws + L.r_swept : R;
     const int cols = n1s - 1;  // columns in front of the right-hand side
-    const int64_t in_step = (b->layout == RDYN_LAYOUT_SAMPLE_MAJOR) ? n : 1;
-    int64_t prev_cnt = -1;
+    // (11 input joints: the image by the run-time-length kernel)
+    ChunkImage im(cs, b, tau_meas, img, cols, &ca, n_comps, K);
+    im.dc = dc;
+    im.dl = dcl;
     for (int64_t s0 = 0; s0 < b->n_samples; s0 += kTsqrImageChunk)
     {
       const int64_t cnt = (b->n_samples - s0 < kTsqrImageChunk) ? (b->n_samples - s0) : kTsqrImageChunk;
-      if (cnt != prev_cnt)
-      {
-        // the sweep does not store the structural zeros of the image: they must read as zeros
-        RDYN_HIP_TRY(hipMemsetAsync(img, 0, sizeof(double) * (size_t)cnt * n * n1s, stream));
-        prev_cnt = cnt;
-      }
-      RdynSweepArgs a;
-      memset(&a, 0, sizeof a);
-      a.chain = dc;
-      a.q = b->q + s0 * in_step;
-      a.dq = b->dq + s0 * in_step;
-      a.ddq = b->ddq + s0 * in_step;
-      a.bcol = tau_meas ? tau_meas + s0 * in_step : nullptr;
-      a.bcol_col = cols;
-      a.n_samples = cnt;
-      rec_strides(b, n, &a.in_ss, &a.in_sj);
-      a.Y = img;
-      a.y_ss = 1;
-      a.y_sr = cnt;
-      a.y_sc = (int64_t)n * cnt;
-      if (p.long_image)
-      {
-        // 11 input joints: the dense image by the run-time-length kernel (rdyn_long_local.hip), the measured torque behind it
-        RdynLongLocalArgs la;
-        memset(&la, 0, sizeof la);
-        la.chain_long = dcl;
-        la.q = a.q;
-        la.dq = a.dq;
-        la.ddq = a.ddq;
-        la.bcol = a.bcol;
-        la.bcol_col = cols;
-        la.n_samples = cnt;
-        la.in_ss = a.in_ss;
-        la.in_sj = a.in_sj;
-        la.Y = img;
-        la.y_ss = 1;
-        la.y_sr = cnt;
-        la.y_sc = (int64_t)n * cnt;
-        la.n_active = n;
-        RDYN_HIP_TRY(rdyn_launch_long_local(RDYN_MODE_REGRESSOR, nJ, la, stream));
-      }
-      else
-        RDYN_HIP_TRY(rdyn_launch_local_sweep(nJ, RDYN_MODE_REGRESSOR_GRAM, a, stream));
-      if (K > 0)
-      {
-        RdynComponentArgs cc = ca;
-        cc.q = a.q;
-        cc.dq = a.dq;
-        cc.n_samples = cnt;
-        cc.in_ss = a.in_ss;
-        cc.in_sj = a.in_sj;
-        cc.n_active = n;
-        cc.n_comps = n_comps;
-        cc.C = img + (int64_t)10 * nJ * n * cnt;
-        cc.c_ss = 1;
-        cc.c_sr = cnt;
-        cc.c_sc = (int64_t)n * cnt;
-        cc.tau = nullptr;
-        RDYN_HIP_TRY(rdyn_launch_components(cc, stream));
-      }
+      st = im.write(s0, cnt, 1, stream);
+      if (st != RDYN_OK) return st;
       // (without measured torques the image's last column stays zero: the factor of [A | 0])
       st = rdyn_tsqr(img, (int64_t)n * cnt, (int64_t)n * cnt, cols, img + (int64_t)cols * n * cnt, R_swept, (s0 > 0 || (accumulate && !expand)) ? 1 : 0,
                      ws + p.rows_off, rdyn_tsqr_workspace_bytes(n1s), -1, stream);
       if (st != RDYN_OK) return st;
     }
-    if (expand)
-    {
-      RdynGramExpandArgs ea;
-      memset(&ea, 0, sizeof ea);
-      st = device_expand(c, &ea.X);
-      if (st != RDYN_OK) return st;
-      for (int f = 0; f < c->n_joints(); ++f) ea.red_of[f] = c->red_of[f];
-      ea.n_joints = c->n_joints();
-      ea.n_red = nJ;
-      ea.n_comp_cols = K;
-      double* const R_exp = accumulate ? ws + L.r_full : R;
-      RDYN_HIP_TRY(rdyn_launch_cholqr_expand(ea, R_swept, R_exp, stream));
-      if (accumulate) RDYN_HIP_TRY(rdyn_launch_cholqr_fold(R_exp, R, n1, stream, n1s));
-    }
-    return RDYN_OK;
+    return expand ? expand_factor(c, p, R_swept, R, accumulate, ws + L.r_full, stream) : RDYN_OK;
   }
   auto bind = [&](RdynLdsGramArgs& la) {
     la.chain = dc;
@@ -2184,22 +2195,7 @@ static int regressor_tsqr_run(const rdyn_chain* c, const rdyn_component* comps, 
     st = householder(R_swept, (accumulate && !expand) ? 1 : 0, nullptr, 2);
     if (st != RDYN_OK) return st;
   }
-  if (expand)
-  {
-    // [A C b] = [A_red C b] diag(E, I_K, 1): R = qr(R_red diag(E, I_K, 1)), folded into the caller's factor when accumulating
-    RdynGramExpandArgs ea;
-    memset(&ea, 0, sizeof ea);
-    st = device_expand(c, &ea.X);
-    if (st != RDYN_OK) return st;
-    for (int f = 0; f < c->n_joints(); ++f) ea.red_of[f] = c->red_of[f];
-    ea.n_joints = c->n_joints();
-    ea.n_red = nJ;
-    ea.n_comp_cols = K;
-    double* const R_exp = accumulate ? ws + L.r_full : R;
-    RDYN_HIP_TRY(rdyn_launch_cholqr_expand(ea, R_swept, R_exp, stream));
-    if (accumulate) RDYN_HIP_TRY(rdyn_launch_cholqr_fold(R_exp, R, n1, stream, n1s));
-  }
-  return RDYN_OK;
+  return expand ? expand_factor(c, p, R_swept, R, accumulate, ws + L.r_full, stream) : RDYN_OK;
 }
 
 }  // extern "C"
@@ -2224,19 +2220,7 @@ __attribute__((visibility("hidden"))) int rdyn_internal_tsqr_expand(const rdyn_c
 {
   TsqrPlan p;
   if (!tsqr_plan(c, comps, n_comps, &p) || !p.expand) return RDYN_ERR_UNSUPPORTED;
-  hipStream_t stream = (hipStream_t)stream_v;
-  RdynGramExpandArgs ea;
-  memset(&ea, 0, sizeof ea);
-  int st = device_expand(c, &ea.X);
-  if (st != RDYN_OK) return st;
-  for (int f = 0; f < c->n_joints(); ++f) ea.red_of[f] = c->red_of[f];
-  ea.n_joints = c->n_joints();
-  ea.n_red = p.nJ;
-  ea.n_comp_cols = p.K;
-  double* const R_exp = accumulate ? scratch : R;
-  RDYN_HIP_TRY(rdyn_launch_cholqr_expand(ea, R_swept, R_exp, stream));
-  if (accumulate) RDYN_HIP_TRY(rdyn_launch_cholqr_fold(R_exp, R, p.n1, stream, p.n1s));
-  return RDYN_OK;
+  return expand_factor(c, p, R_swept, R, accumulate, scratch, (hipStream_t)stream_v);
 }
 extern "C"
 {
@@ -2324,6 +2308,11 @@ int rdyn_identification_gram(const rdyn_chain* c, const rdyn_component* comps, i
   const int n = c->n_active(), P = 10 * c->n_joints();
   const int K = n_comps > 0 ? rdyn_components_columns(comps, n_comps) : 0;
   const int cols = P + K;
+  auto companion = [&](double* Gr, double* cr, double* bbr, void* ws, size_t ws_bytes) {
+    const rdyn_chain* r = c->reduced.get();
+    return n_comps > 0 ? rdyn_identification_gram(r, comps, n_comps, b, tau_meas, Gr, cr, bbr, 0, ws, ws_bytes)
+                       : rdyn_regressor_gram(r, b, tau_meas, Gr, cr, bbr, 0, 0, ws, ws_bytes);
+  };
   if (K >= 0 && gram_only_through_reduced(c, K))
   {
     const size_t need = rdyn_identification_gram_workspace_bytes(c, comps, n_comps);
@@ -2335,17 +2324,8 @@ int rdyn_identification_gram(const rdyn_chain* c, const rdyn_component* comps, i
     DeviceGuard g;
     st = g.enter(b->device);
     if (st != RDYN_OK) return st;
-    if (b->n_samples == 0)
-    {
-      if (!accumulate)
-      {
-        RDYN_HIP_TRY(hipMemsetAsync(G, 0, sizeof(double) * cols * cols, (hipStream_t)b->stream));
-        if (cvec) RDYN_HIP_TRY(hipMemsetAsync(cvec, 0, sizeof(double) * cols, (hipStream_t)b->stream));
-        if (bb) RDYN_HIP_TRY(hipMemsetAsync(bb, 0, sizeof(double), (hipStream_t)b->stream));
-      }
-      return RDYN_OK;
-    }
-    return gram_through_reduced(c, comps, n_comps, K, b, tau_meas, G, cvec, bb, accumulate, workspace, need);
+    if (b->n_samples == 0) return zero_normal_equations(G, cvec, bb, cols, accumulate, (hipStream_t)b->stream);
+    return gram_through_reduced(c, K, b, G, cvec, bb, accumulate, workspace, need, companion);
   }
   if (rdyn_gram_blocks_for(cols) > 7)
   {
@@ -2371,19 +2351,9 @@ int rdyn_identification_gram(const rdyn_chain* c, const rdyn_component* comps, i
   double* slabs = (double*)workspace;
   double* scratch = (double*)((char*)workspace + gram_slab_bytes(cols));
   const int64_t N = b->n_samples;
-  if (N == 0)
-  {
-    if (!accumulate)
-    {
-      RDYN_HIP_TRY(hipMemsetAsync(G, 0, sizeof(double) * cols * cols, stream));
-      if (cvec) RDYN_HIP_TRY(hipMemsetAsync(cvec, 0, sizeof(double) * cols, stream));
-      if (bb) RDYN_HIP_TRY(hipMemsetAsync(bb, 0, sizeof(double), stream));
-    }
-    return RDYN_OK;
-  }
+  if (N == 0) return zero_normal_equations(G, cvec, bb, cols, accumulate, stream);
   if (c->reduced && !probe_env("RDYN_GRAM_NO_REDUCE"))
-    return gram_through_reduced(c, comps, n_comps, K, b, tau_meas, G, cvec, bb, accumulate, workspace,
-                                rdyn_identification_gram_workspace_bytes(c, comps, n_comps));
+    return gram_through_reduced(c, K, b, G, cvec, bb, accumulate, workspace, rdyn_identification_gram_workspace_bytes(c, comps, n_comps), companion);
   // ---- fused: regressor rows AND component columns stay in LDS (rdyn_duo_gram.hip); else the chunk image below
   if (n >= 2 && n <= 8 && rdyn_regressor_gram_duo_supports_components(P, K) && !probe_env("RDYN_IDENT_UNFUSED"))
   {
@@ -2440,50 +2410,15 @@ int rdyn_identification_gram(const rdyn_chain* c, const rdyn_component* comps, i
       return RDYN_OK;
     }
   }
-  const int64_t in_step = (b->layout == RDYN_LAYOUT_SAMPLE_MAJOR) ? n : 1;
   int first_col[RDYN_MAX_SWEPT_JOINTS];
   for (int j = 0; j < n; ++j) first_col[j] = 10 * c->active[j];  // the component columns lie to the right: always loaded
-  int64_t prev_cnt = -1;
+  ChunkImage im(c, b, tau_meas, scratch, cols, &ca, n_comps, K);
+  im.dc = dc;
   for (int64_t s0 = 0; s0 < N; s0 += kIdentChunk)
   {
     const int64_t cnt = (N - s0 < kIdentChunk) ? (N - s0) : kIdentChunk;
-    if (cnt != prev_cnt)
-    {
-      RDYN_HIP_TRY(hipMemsetAsync(scratch, 0, sizeof(double) * (size_t)cnt * n * (cols + 1), stream));  // see rdyn_regressor_gram
-      prev_cnt = cnt;
-    }
-    // element-major image of the chunk: rows j * cnt + s, lda = n * cnt; columns [Y (P) | C (K) | tau_meas]
-    RdynSweepArgs a;
-    memset(&a, 0, sizeof a);
-    a.chain = dc;
-    a.q = b->q + s0 * in_step;
-    a.dq = b->dq + s0 * in_step;
-    a.ddq = b->ddq + s0 * in_step;
-    a.bcol = tau_meas ? tau_meas + s0 * in_step : nullptr;
-    a.bcol_col = cols;
-    a.n_samples = cnt;
-    rec_strides(b, n, &a.in_ss, &a.in_sj);
-    a.Y = scratch;
-    a.y_ss = 1;
-    a.y_sr = cnt;
-    a.y_sc = (int64_t)n * cnt;
-    RDYN_HIP_TRY(rdyn_launch_local_sweep(c->n_joints(), RDYN_MODE_REGRESSOR_GRAM, a, stream));
-    if (K > 0)
-    {
-      ca.q = a.q;
-      ca.dq = a.dq;
-      ca.n_samples = cnt;
-      ca.in_ss = a.in_ss;
-      ca.in_sj = a.in_sj;
-      ca.n_active = n;
-      ca.n_comps = n_comps;
-      ca.C = scratch + (int64_t)P * n * cnt;
-      ca.c_ss = 1;
-      ca.c_sr = cnt;
-      ca.c_sc = (int64_t)n * cnt;
-      ca.tau = nullptr;
-      RDYN_HIP_TRY(rdyn_launch_components(ca, stream));
-    }
+    st = im.write(s0, cnt, 1, stream);
+    if (st != RDYN_OK) return st;
     const bool last = (s0 + cnt >= N);
     st = gram_launch(scratch, (int64_t)n * cnt, (int64_t)n * cnt, cols, tau_meas ? scratch + (int64_t)cols * n * cnt : nullptr, G, cvec, bb,
                      s0 > 0 ? 1 : 0, last, accumulate ? 1 : 0, slabs, stream, cnt, first_col, n);
@@ -2501,15 +2436,22 @@ static const int64_t kWideImageBytes = (int64_t)128 << 20;
 static const int64_t kWideMinChunk = 16384;
 
 static size_t panel_slab_bytes(int n_cols) { return (rdyn_panel_gram_slab_bytes(n_cols) + 255) & ~(size_t)255; }
+// samples per chunk image [Y | C | tau_meas] (`cols` columns in front of tau_meas) of the wide normal equations and the wide R factors
+static int64_t wide_chunk(const rdyn_chain* c, int cols, int64_t chunk_samples)
+{
+  const int64_t fit = (kWideImageBytes / ((int64_t)c->n_active() * (cols + 1) * (int64_t)sizeof(double))) & ~(int64_t)63;
+  return chunk_samples > 0 ? chunk_samples : (fit > kWideMinChunk ? fit : kWideMinChunk);
+}
 
 size_t rdyn_gram_wide_workspace_bytes(int n_cols)
 {
   return (n_cols < 1 || n_cols > RDYN_MAX_WIDE_COLUMNS) ? 0 : panel_slab_bytes(n_cols);
 }
 
+// run_flag: null, or a device word that lets both kernels leave at once (the rounds of the panel QR)
 static int panel_gram_launch(const double* A, int64_t rows, int64_t lda, int n_cols, const double* bvec, double* G, double* cvec, double* bb,
-                             int slab_accumulate, bool finish, int add_to_output, void* slabs, hipStream_t st, int64_t row_block = 0,
-                             const int* first_col = nullptr, int n_row_blocks = 0)
+                             int slab_accumulate, bool finish, int add_to_output, void* slabs, const int* run_flag, hipStream_t st,
+                             int64_t row_block = 0, const int* first_col = nullptr, int n_row_blocks = 0)
 {
   RdynPanelGramArgs a;
   memset(&a, 0, sizeof a);
@@ -2526,6 +2468,7 @@ static int panel_gram_launch(const double* A, int64_t rows, int64_t lda, int n_c
   a.G = G;
   a.c = cvec;
   a.bb = bb;
+  a.run_flag = run_flag;
   RDYN_HIP_TRY(rdyn_launch_panel_gram(a, st));
   if (finish) RDYN_HIP_TRY(rdyn_launch_panel_gram_finish(a, st));
   return RDYN_OK;
@@ -2552,7 +2495,7 @@ int rdyn_gram_wide(const double* A, int64_t rows, int64_t lda, int n_cols, const
   DeviceGuard g;
   int st = g.enter(device);
   if (st != RDYN_OK) return st;
-  return panel_gram_launch(A, rows, lda, n_cols, bvec, G, cvec, bb, 0, true, accumulate ? 1 : 0, workspace, (hipStream_t)stream);
+  return panel_gram_launch(A, rows, lda, n_cols, bvec, G, cvec, bb, 0, true, accumulate ? 1 : 0, workspace, nullptr, (hipStream_t)stream);
 }
 
 // How a wide request is served: by the narrow call (it already serves it), through the reduced companion (the wide normal equations
@@ -2590,10 +2533,8 @@ static WidePlan wide_plan(const rdyn_chain* c, const rdyn_component* comps, int 
     return p;
   }
   p.route = c->long_chain() ? WIDE_LONG_IMAGES : WIDE_SWEEP_IMAGES;
-  const int64_t per_sample = (int64_t)c->n_active() * (p.cols + 1) * (int64_t)sizeof(double);
-  const int64_t fit = (kWideImageBytes / per_sample) & ~(int64_t)63;
-  p.chunk = chunk_samples > 0 ? chunk_samples : (fit > kWideMinChunk ? fit : kWideMinChunk);
-  p.bytes = panel_slab_bytes(p.cols) + (((size_t)p.chunk * per_sample + 255) & ~(size_t)255);
+  p.chunk = wide_chunk(c, p.cols, chunk_samples);
+  p.bytes = panel_slab_bytes(p.cols) + (((size_t)p.chunk * c->n_active() * (p.cols + 1) * sizeof(double) + 255) & ~(size_t)255);
   return p;
 }
 
@@ -2633,127 +2574,27 @@ static int gram_wide_run(const rdyn_chain* c, const rdyn_component* comps, int n
   hipStream_t stream = (hipStream_t)b->stream;
   const int cols = p.cols, K = p.K;
   const int64_t N = b->n_samples;
-  if (N == 0)
-  {
-    if (!accumulate)
-    {
-      RDYN_HIP_TRY(hipMemsetAsync(G, 0, sizeof(double) * cols * cols, stream));
-      if (cvec) RDYN_HIP_TRY(hipMemsetAsync(cvec, 0, sizeof(double) * cols, stream));
-      if (bb) RDYN_HIP_TRY(hipMemsetAsync(bb, 0, sizeof(double), stream));
-    }
-    return RDYN_OK;
-  }
+  if (N == 0) return zero_normal_equations(G, cvec, bb, cols, accumulate, stream);
   if (p.route == WIDE_REDUCED)
-  {
-    // G = E' G_red E (rdyn_chain.hpp): the companion's wide normal equations into the tail of the workspace, then k_gram_expand
-    const rdyn_chain* r = c->reduced.get();
-    const int Cr = 10 * r->n_joints() + K;
-    const size_t tmp = reduce_tmp_bytes(Cr);
-    double* Gr = (double*)((char*)workspace + p.bytes - tmp);
-    st = gram_wide_run(r, comps, n_comps, b, tau_meas, Gr, Gr + (size_t)Cr * Cr, Gr + (size_t)Cr * Cr + Cr, 0, chunk_samples, workspace,
-                       p.bytes - tmp, ident);
-    if (st != RDYN_OK) return st;
-    RdynGramExpandArgs ea;
-    memset(&ea, 0, sizeof ea);
-    st = device_expand(c, &ea.X);
-    if (st != RDYN_OK) return st;
-    ea.G_red = Gr;
-    ea.c_red = Gr + (size_t)Cr * Cr;
-    ea.bb_red = Gr + (size_t)Cr * Cr + Cr;
-    for (int f = 0; f < c->n_joints(); ++f) ea.red_of[f] = c->red_of[f];
-    ea.n_joints = c->n_joints();
-    ea.n_red = r->n_joints();
-    ea.n_comp_cols = K;
-    ea.add_to_output = accumulate ? 1 : 0;
-    ea.G = G;
-    ea.c = cvec;
-    ea.bb = bb;
-    RDYN_HIP_TRY(rdyn_launch_gram_expand(ea, stream));
-    return RDYN_OK;
-  }
-  // chunk images: element-major [Y (P) | C (K) | tau_meas], rows j * cnt + s, lda = n * cnt; row block j is zero left of column
-  // 10 * (chain index of input joint j) -- the component columns lie to the right of every band
-  const RdynChainConst* dc = nullptr;
-  const RdynLongChainConst* dl = nullptr;
-  st = p.route == WIDE_LONG_IMAGES ? device_const_long(c, &dl) : device_const(c, &dc);
+    return gram_through_reduced(c, K, b, G, cvec, bb, accumulate, workspace, p.bytes,
+                                [&](double* Gr, double* cr, double* bbr, void* ws, size_t ws_bytes) {
+                                  return gram_wide_run(c->reduced.get(), comps, n_comps, b, tau_meas, Gr, cr, bbr, 0, chunk_samples, ws, ws_bytes, ident);
+                                });
+  // chunk images (ChunkImage); row block j is zero left of column 10 * (chain index of input joint j) -- the component columns lie to
+  // the right of every band
+  ChunkImage im(c, b, tau_meas, (double*)((char*)workspace + panel_slab_bytes(cols)), cols, &ca, n_comps, K);
+  st = im.bind(p.route == WIDE_LONG_IMAGES);
   if (st != RDYN_OK) return st;
-  const int P = 10 * c->n_joints();
   int first_col[RDYN_MAX_JOINTS];
   for (int j = 0; j < n; ++j) first_col[j] = 10 * c->active[j];
   double* const slabs = (double*)workspace;
-  double* const image = (double*)((char*)workspace + panel_slab_bytes(cols));
-  const int64_t in_step = (b->layout == RDYN_LAYOUT_SAMPLE_MAJOR) ? n : 1;
-  int64_t prev_cnt = -1;
   for (int64_t s0 = 0; s0 < N; s0 += p.chunk)
   {
     const int64_t cnt = (N - s0 < p.chunk) ? (N - s0) : p.chunk;
-    if (cnt != prev_cnt)
-    {
-      // the sweep does not store the zero band; 16-row groups that straddle two row blocks read a little of it (see rdyn_regressor_gram)
-      RDYN_HIP_TRY(hipMemsetAsync(image, 0, sizeof(double) * (size_t)cnt * n * (cols + 1), stream));
-      prev_cnt = cnt;
-    }
-    const double* q = b->q + s0 * in_step;
-    const double* dq = b->dq + s0 * in_step;
-    const double* bcol = tau_meas ? tau_meas + s0 * in_step : nullptr;
-    int64_t in_ss, in_sj;
-    rec_strides(b, n, &in_ss, &in_sj);  // element-major: the joint stride stays the FULL batch's N
-    if (p.route == WIDE_LONG_IMAGES)
-    {
-      RdynLongLocalArgs a;
-      memset(&a, 0, sizeof a);
-      a.chain_long = dl;
-      a.q = q;
-      a.dq = dq;
-      a.ddq = b->ddq + s0 * in_step;
-      a.bcol = bcol;
-      a.bcol_col = cols;
-      a.n_samples = cnt;
-      a.in_ss = in_ss;
-      a.in_sj = in_sj;
-      a.Y = image;
-      a.y_ss = 1;
-      a.y_sr = cnt;
-      a.y_sc = (int64_t)n * cnt;
-      RDYN_HIP_TRY(rdyn_launch_long_local(RDYN_MODE_REGRESSOR, c->n_joints(), a, stream));
-    }
-    else
-    {
-      RdynSweepArgs a;
-      memset(&a, 0, sizeof a);
-      a.chain = dc;
-      a.q = q;
-      a.dq = dq;
-      a.ddq = b->ddq + s0 * in_step;
-      a.bcol = bcol;
-      a.bcol_col = cols;
-      a.n_samples = cnt;
-      a.in_ss = in_ss;
-      a.in_sj = in_sj;
-      a.Y = image;
-      a.y_ss = 1;
-      a.y_sr = cnt;
-      a.y_sc = (int64_t)n * cnt;
-      RDYN_HIP_TRY(rdyn_launch_local_sweep(c->n_joints(), RDYN_MODE_REGRESSOR_GRAM, a, stream));
-    }
-    if (K > 0)
-    {
-      ca.q = q;
-      ca.dq = dq;
-      ca.n_samples = cnt;
-      ca.in_ss = in_ss;
-      ca.in_sj = in_sj;
-      ca.n_active = n;
-      ca.n_comps = n_comps;
-      ca.C = image + (int64_t)P * n * cnt;
-      ca.c_ss = 1;
-      ca.c_sr = cnt;
-      ca.c_sc = (int64_t)n * cnt;
-      ca.tau = nullptr;
-      RDYN_HIP_TRY(rdyn_launch_components(ca, stream));
-    }
-    st = panel_gram_launch(image, (int64_t)n * cnt, (int64_t)n * cnt, cols, tau_meas ? image + (int64_t)cols * n * cnt : nullptr, G, cvec, bb,
-                           s0 > 0 ? 1 : 0, s0 + cnt >= N, accumulate ? 1 : 0, slabs, stream, cnt, first_col, n);
+    st = im.write(s0, cnt, 1, stream);
+    if (st != RDYN_OK) return st;
+    st = panel_gram_launch(im.image, (int64_t)n * cnt, (int64_t)n * cnt, cols, tau_meas ? im.image + (int64_t)cols * n * cnt : nullptr, G, cvec, bb,
+                           s0 > 0 ? 1 : 0, s0 + cnt >= N, accumulate ? 1 : 0, slabs, nullptr, stream, cnt, first_col, n);
     if (st != RDYN_OK) return st;
   }
   return RDYN_OK;
@@ -2849,29 +2690,6 @@ static int panel_qr_rounds(double* ws, const PanelQrLayout& L, int n1, int has_b
   return RDYN_OK;
 }
 
-static int panel_gram_into(const double* Q, int64_t rows, int64_t ldq, int n1, bool has_b, double* g2, bool acc_slabs, bool finish, void* slabs,
-                           const int* run, hipStream_t st, int64_t row_block = 0, const int* first_col = nullptr, int n_row_blocks = 0)
-{
-  RdynPanelGramArgs a;
-  memset(&a, 0, sizeof a);
-  a.row_block = first_col ? row_block : 0;
-  for (int j = 0; first_col && j < n_row_blocks && j < RDYN_MAX_JOINTS; ++j) a.first_col[j] = first_col[j];
-  a.A = Q;
-  a.b = has_b ? Q + (int64_t)(n1 - 1) * ldq : nullptr;
-  a.rows = rows;
-  a.lda = ldq;
-  a.P = n1 - 1;
-  a.accumulate = acc_slabs ? 1 : 0;
-  a.slabs = (double*)slabs;
-  a.G = g2;
-  a.c = g2 + (size_t)(n1 - 1) * (n1 - 1);
-  a.bb = a.c + (n1 - 1);
-  a.run_flag = run;
-  RDYN_HIP_TRY(rdyn_launch_panel_gram(a, st));
-  if (finish) RDYN_HIP_TRY(rdyn_launch_panel_gram_finish(a, st));
-  return RDYN_OK;
-}
-
 static void read_wide_report(const double* raw, int n1, rdyn_tsqr_wide_report* out)
 {
   int flags[2 * kPanelFlagDoubles];
@@ -2940,8 +2758,11 @@ int rdyn_tsqr_wide(const double* A, int64_t rows, int64_t lda, int n_cols, const
   if (gs > 1 && gs % 2 == 0) ++gs;
   while (rdyn_panel_gather_rows(rows, gs) > q_rows) gs += 2;
   const int64_t sub_rows = rdyn_panel_gather_rows(rows, gs);
+  const int P = n1 - 1;  // Q'Q of [Q | b] goes to L.g2: G (P x P) | c | bb
+  double* const G2 = ws + L.g2;
+  double* const c2 = G2 + (size_t)P * P;
   RDYN_HIP_TRY(rdyn_launch_panel_gather(A, bcol, rows, lda, nA, gs, Q, q_rows, stream));
-  st = panel_gram_into(Q, sub_rows, q_rows, n1, true, ws + L.g2, false, true, ws + L.slabs, nullptr, stream);
+  st = panel_gram_launch(Q, sub_rows, q_rows, P, Q + (int64_t)P * q_rows, G2, c2, c2 + P, 0, true, 0, ws + L.slabs, nullptr, stream);
   if (st != RDYN_OK) return st;
   double* const R_new = accumulate ? ws + L.r_tmp : R;
   const double row_scale = sqrt((double)groups * 16.0 / (double)sub_rows);
@@ -2962,7 +2783,7 @@ int rdyn_tsqr_wide(const double* A, int64_t rows, int64_t lda, int n_cols, const
       ta.W = W;
       ta.run_flag = run;
       RDYN_HIP_TRY(rdyn_launch_panel_trmm(ta, stream));
-      const int s2 = panel_gram_into(Q, cnt, q_rows, n1, true, ws + L.g2, r0 > 0, r0 + cnt >= rows, ws + L.slabs, run, stream);
+      const int s2 = panel_gram_launch(Q, cnt, q_rows, P, Q + (int64_t)P * q_rows, G2, c2, c2 + P, r0 > 0, r0 + cnt >= rows, 0, ws + L.slabs, run, stream);
       if (s2 != RDYN_OK) return s2;
     }
     return RDYN_OK;
@@ -2997,7 +2818,7 @@ int rdyn_tsqr_wide_last_report(int n_cols_with_rhs, const void* workspace, int d
 }
 
 // chains: served by the narrow call where it serves (its workspace); else by chunk images of the chain itself -- [Y | C | tau_meas]
-// written by the writers of rdyn_regressor_gram_wide, multiplied by W in place (k_panel_trmm), reduced by the panel Gram; a chain with
+// written by ChunkImage, multiplied by W in place (k_panel_trmm), reduced by the panel Gram; a chain with
 // fixed joints through its reduced companion (served by chunk images itself), whose factor is expanded by k_cholqr_expand<true>
 // (R = qr(R_red E_aug)) -- the companion's workspace first (its flags are what the report reads), then R_red, the expansion's square,
 // the expanded factor (accumulate) and the fold's triangle.
@@ -3035,9 +2856,7 @@ static PanelQrPlan panel_qr_plan(const rdyn_chain* c, const rdyn_component* comp
     p.bytes = p.sub_bytes + tail * sizeof(double);
     return p;
   }
-  const int64_t per_sample = (int64_t)c->n_active() * p.n1 * (int64_t)sizeof(double);
-  const int64_t fit = (kWideImageBytes / per_sample) & ~(int64_t)63;
-  p.chunk = chunk_samples > 0 ? chunk_samples : (fit > kWideMinChunk ? fit : kWideMinChunk);
+  p.chunk = wide_chunk(c, p.cols, chunk_samples);
   p.L = panel_qr_layout(p.n1, (size_t)p.chunk * c->n_active() * p.n1);
   p.bytes = p.L.total_doubles * sizeof(double);
   return p;
@@ -3094,102 +2913,29 @@ static int panel_qr_chain_run(const rdyn_chain* c, const rdyn_component* comps, 
     st = panel_qr_chain_run(c->reduced.get(), comps, n_comps, b, tau_meas, R_red, 0, chunk_samples, workspace, p.sub_bytes, ident);
     if (st != RDYN_OK) return st;
     RdynGramExpandArgs ea;
-    memset(&ea, 0, sizeof ea);
-    st = device_expand(c, &ea.X);
+    st = fill_expand_args(c, c->reduced->n_joints(), K, &ea);
     if (st != RDYN_OK) return st;
-    for (int f = 0; f < c->n_joints(); ++f) ea.red_of[f] = c->red_of[f];
-    ea.n_joints = c->n_joints();
-    ea.n_red = c->reduced->n_joints();
-    ea.n_comp_cols = K;
     double* const R_out = accumulate ? R_exp : R;
     RDYN_HIP_TRY(rdyn_launch_cholqr_expand_global(ea, R_red, R_out, B, stream));
     if (accumulate) RDYN_HIP_TRY(rdyn_launch_cholqr_fold_global(R_exp, R, n1, fold, stream));
     return RDYN_OK;
   }
-  const RdynChainConst* dc = nullptr;
-  const RdynLongChainConst* dl = nullptr;
-  const bool long_images = c->long_chain();
-  st = long_images ? device_const_long(c, &dl) : device_const(c, &dc);
-  if (st != RDYN_OK) return st;
-  const int P = 10 * c->n_joints();
   int first_col[RDYN_MAX_JOINTS];
   for (int j = 0; j < n; ++j) first_col[j] = 10 * c->active[j];
   double* const ws = (double*)workspace;
   const PanelQrLayout& L = p.L;
   double* const image = ws + L.rows;
-  const int64_t in_step = (b->layout == RDYN_LAYOUT_SAMPLE_MAJOR) ? n : 1;
-  int64_t prev_cnt = -1;
-  // the image of cnt samples s0, s0 + S, s0 + 2 S, ...: [Y | C | tau_meas] element-major, rows j * cnt + s (as rdyn_regressor_gram_wide)
+  double* const G2 = ws + L.g2;  // Q'Q of [Q | b]: G (cols x cols) | c | bb
+  double* const c2 = G2 + (size_t)cols * cols;
+  ChunkImage im(c, b, tau_meas, image, cols, &ca, n_comps, K);
+  st = im.bind(c->long_chain());
+  if (st != RDYN_OK) return st;
+  // the chunk images of the ChunkImage writer; k_panel_trmm turns one into Q in place and keeps its zero band zero for the next chunk of
+  // the same length, but the right-hand side column is then Q's: without tau_meas (which no writer stores) it has to be zeroed again
   auto write_image = [&](int64_t s0, int64_t cnt, int64_t S) -> int {
-    if (cnt != prev_cnt)
-    {
-      // the writers do not store the zero band (k_panel_trmm keeps it zero for the next chunk of the same length)
-      RDYN_HIP_TRY(hipMemsetAsync(image, 0, sizeof(double) * (size_t)cnt * n * n1, stream));
-      prev_cnt = cnt;
-    }
-    else if (!tau_meas)
+    if (cnt == im.cleared_cnt && !tau_meas)
       RDYN_HIP_TRY(hipMemsetAsync(image + (int64_t)cols * n * cnt, 0, sizeof(double) * (size_t)cnt * n, stream));
-    const double* q = b->q + s0 * in_step;
-    const double* dq = b->dq + s0 * in_step;
-    const double* bcol = tau_meas ? tau_meas + s0 * in_step : nullptr;
-    int64_t in_ss, in_sj;
-    rec_strides(b, n, &in_ss, &in_sj);  // element-major: the joint stride stays the FULL batch's N
-    in_ss *= S;
-    if (long_images)
-    {
-      RdynLongLocalArgs a;
-      memset(&a, 0, sizeof a);
-      a.chain_long = dl;
-      a.q = q;
-      a.dq = dq;
-      a.ddq = b->ddq + s0 * in_step;
-      a.bcol = bcol;
-      a.bcol_col = cols;
-      a.n_samples = cnt;
-      a.in_ss = in_ss;
-      a.in_sj = in_sj;
-      a.Y = image;
-      a.y_ss = 1;
-      a.y_sr = cnt;
-      a.y_sc = (int64_t)n * cnt;
-      RDYN_HIP_TRY(rdyn_launch_long_local(RDYN_MODE_REGRESSOR, c->n_joints(), a, stream));
-    }
-    else
-    {
-      RdynSweepArgs a;
-      memset(&a, 0, sizeof a);
-      a.chain = dc;
-      a.q = q;
-      a.dq = dq;
-      a.ddq = b->ddq + s0 * in_step;
-      a.bcol = bcol;
-      a.bcol_col = cols;
-      a.n_samples = cnt;
-      a.in_ss = in_ss;
-      a.in_sj = in_sj;
-      a.Y = image;
-      a.y_ss = 1;
-      a.y_sr = cnt;
-      a.y_sc = (int64_t)n * cnt;
-      RDYN_HIP_TRY(rdyn_launch_local_sweep(c->n_joints(), RDYN_MODE_REGRESSOR_GRAM, a, stream));
-    }
-    if (K > 0)
-    {
-      ca.q = q;
-      ca.dq = dq;
-      ca.n_samples = cnt;
-      ca.in_ss = in_ss;
-      ca.in_sj = in_sj;
-      ca.n_active = n;
-      ca.n_comps = n_comps;
-      ca.C = image + (int64_t)P * n * cnt;
-      ca.c_ss = 1;
-      ca.c_sr = cnt;
-      ca.c_sc = (int64_t)n * cnt;
-      ca.tau = nullptr;
-      RDYN_HIP_TRY(rdyn_launch_components(ca, stream));
-    }
-    return RDYN_OK;
+    return im.write(s0, cnt, S, stream);
   };
   // pass A: one image of every S-th sample (about kPanelQrSubSamples of them, at most one chunk)
   const int64_t sub_cap = p.chunk < kPanelQrSubSamples ? p.chunk : kPanelQrSubSamples;
@@ -3197,8 +2943,8 @@ static int panel_qr_chain_run(const rdyn_chain* c, const rdyn_component* comps, 
   const int64_t sub_cnt = (N + S - 1) / S;
   st = write_image(0, sub_cnt, S);
   if (st != RDYN_OK) return st;
-  st = panel_gram_into(image, (int64_t)n * sub_cnt, (int64_t)n * sub_cnt, n1, true, ws + L.g2, false, true, ws + L.slabs, nullptr, stream, sub_cnt,
-                       first_col, n);
+  st = panel_gram_launch(image, (int64_t)n * sub_cnt, (int64_t)n * sub_cnt, cols, image + (int64_t)cols * n * sub_cnt, G2, c2, c2 + cols, 0, true, 0,
+                         ws + L.slabs, nullptr, stream, sub_cnt, first_col, n);
   if (st != RDYN_OK) return st;
   double* const R_new = accumulate ? ws + L.r_tmp : R;
   st = panel_qr_rounds(ws, L, n1, tau_meas ? 1 : 0, sqrt((double)N / (double)sub_cnt), R_new, stream, [&](const double* W, const int* run, int) -> int {
@@ -3223,8 +2969,8 @@ static int panel_qr_chain_run(const rdyn_chain* c, const rdyn_component* comps, 
       for (int j = 0; j < n; ++j) ta.first_col[j] = first_col[j];
       for (int j = n; j < RDYN_MAX_JOINTS; ++j) ta.first_col[j] = 0;
       RDYN_HIP_TRY(rdyn_launch_panel_trmm(ta, stream));
-      s2 = panel_gram_into(image, (int64_t)n * cnt, (int64_t)n * cnt, n1, true, ws + L.g2, s0 > 0, s0 + cnt >= N, ws + L.slabs, run, stream, cnt,
-                           first_col, n);
+      s2 = panel_gram_launch(image, (int64_t)n * cnt, (int64_t)n * cnt, cols, image + (int64_t)cols * n * cnt, G2, c2, c2 + cols, s0 > 0, s0 + cnt >= N,
+                             0, ws + L.slabs, run, stream, cnt, first_col, n);
       if (s2 != RDYN_OK) return s2;
     }
     return RDYN_OK;
