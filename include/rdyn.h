@@ -52,8 +52,8 @@ extern "C" {
  *      with MORE input joints than that (up to RDYN_MAX_JOINTS of them; rdyn_long_local.hip: rolled link and row loops, the per-joint
  *      state in wave-private LDS) rdyn_regressor (+ its fused torque), rdyn_joint_inertia, the joint torques (read off the wrench
  *      recursion) and every kinematic output are served, rdyn_regressor_gram and rdyn_regressor_tsqr for 11 input joints (110 + 1 columns:
- *      what the Gram kernel and the widest R factor hold; chunk images); rdyn_local_ik, component columns and wider factors answer
- *      RDYN_ERR_UNSUPPORTED.
+ *      what the Gram kernel and the widest R factor hold; chunk images; wider: the _wide calls below) and rdyn_local_ik(_damped)
+ *      (rdyn_long_ik.hip: up to RDYN_MAX_JOINTS input joints; see rdyn_local_ik_damped for its undamped and negative-weight cases).
  *  - Normal equations: rdyn_gram, rdyn_regressor_gram and rdyn_identification_gram stop at 111 columns (110 + tau_meas, after the
  *    reduction); rdyn_gram_wide, rdyn_regressor_gram_wide and rdyn_identification_gram_wide serve the rest up to
  *    RDYN_MAX_WIDE_COLUMNS columns (any chain above, components included).  The R factors: rdyn_tsqr, rdyn_regressor_tsqr and
@@ -301,7 +301,13 @@ int rdyn_frame_distance(int64_t n_pairs, const double* T_wa, const double* T_wb,
                         double* jacobian, int device, void* stream);
 /* The same iteration with a Levenberg term: damping^2 is added to the diagonal of J'WJ before the QP (damping = 0 is
  * rdyn_local_ik).  No counterpart in the reference; it is what makes the loop usable where the reference's QP is singular
- * (7-DOF arms: J'J is 7 x 7 of rank 6) and near singular poses. */
+ * (7-DOF arms: J'J is 7 x 7 of rank 6) and near singular poses.
+ * Chains of more than RDYN_MAX_SWEPT_JOINTS input joints (up to RDYN_MAX_JOINTS, any order; rdyn_long_ik.hip) solve the same
+ * QP through a 6 x 6 system per working set.  There the pivot rule reads damping^2 <= 1e-10 trace(J'WJ + damping^2 I) -> -1:
+ * with damping = 0 every pose that is not converged at its seed gets status -1 with 0 updates; a negative weight entry gives
+ * -1 for every such pose too (J'WJ indefinite).  Fixed joints listed as inputs leave 6 or fewer moving joints possible on this
+ * route: an update with fewer than six free moving joints (not held at a bound) whose damping^2 is at most 1e-10 trace of the 6 x 6
+ * system is -1 as well (rdyn_local_ik solves that undamped case).  The statuses and `iterations` are those above. */
 int rdyn_local_ik_damped(const rdyn_chain* chain, const rdyn_batch* batch, const double* T_target, const double* weight, double toll,
                          double damping, int max_iterations, double* sol, int32_t* status, int32_t* iterations);
 

@@ -589,7 +589,9 @@ int rdyn_local_ik(const rdyn_chain* c, const rdyn_batch* b, const double* T_targ
 int rdyn_local_ik_damped(const rdyn_chain* c, const rdyn_batch* b, const double* T_target, const double* weight, double toll,
                          double damping, int max_iterations, double* sol, int32_t* status, int32_t* iterations)
 {
-  int st = check_batch(c, b, false, false, "rdyn_local_ik", LONG_COMPANION);  // batch->q = the seeds
+  // a long chain with more input joints than its reduced companion holds (no companion) runs on the rolled kernel, rdyn_long_ik.hip
+  const bool long_route = c && c->long_chain() && !c->reduced;
+  int st = check_batch(c, b, false, false, "rdyn_local_ik", long_route ? LONG_KERNELS : LONG_COMPANION);  // batch->q = the seeds
   if (st != RDYN_OK) return st;
   if (b->n_samples > 0 && (!T_target || !sol))
   {
@@ -605,6 +607,37 @@ int rdyn_local_ik_damped(const rdyn_chain* c, const rdyn_batch* b, const double*
   DeviceGuard g;
   st = g.enter(b->device);
   if (st != RDYN_OK) return st;
+  if (long_route)
+  {
+    RdynLongIkArgs a;
+    memset(&a, 0, sizeof a);
+    st = device_const_long(c, &a.chain_long);
+    if (st != RDYN_OK) return st;
+    a.T_target = T_target;
+    rec_strides(b, 12, &a.tt_ss, &a.tt_se);
+    a.seed = b->q;
+    a.sol = sol;
+    a.n_samples = b->n_samples;
+    rec_strides(b, c->n_active(), &a.in_ss, &a.in_sj);
+    for (int i = 0; i < 6; ++i) a.weight[i] = weight ? weight[i] : 1.0;
+    // the QP variables: the moving input joints in chain order
+    for (int j = 0; j < c->n_joints(); ++j)
+    {
+      const RdynJointConst& J = c->host_long.j[j];
+      if (J.in_idx < 0 || J.type == RDYN_FIXED) continue;
+      a.var_in[a.n_var] = J.in_idx;
+      a.q_min[a.n_var] = c->q_min[j];
+      a.q_max[a.n_var] = c->q_max[j];
+      ++a.n_var;
+    }
+    a.toll = toll;
+    a.damping = damping;
+    a.max_iter = max_iterations;
+    a.status = status;
+    a.iterations = iterations;
+    RDYN_HIP_TRY(rdyn_launch_long_ik(a, (hipStream_t)b->stream));
+    return RDYN_OK;
+  }
   RdynIkArgs a;
   memset(&a, 0, sizeof a);
   if (c->long_chain())

@@ -101,6 +101,31 @@ struct RdynIkArgs
 };
 hipError_t rdyn_launch_local_ik(int n_joints, const RdynIkArgs& a, hipStream_t st);
 
+// the same loop for a chain of more than RDYN_MAX_SWEPT_JOINTS joints with more input joints than its reduced companion holds
+// (rdyn_long_ik.hip: rolled link loop, the Jacobian columns in wave-private LDS, the QP through a 6 x 6 system).  The QP variables are
+// the moving input joints in CHAIN order.
+struct RdynLongIkArgs
+{
+  const RdynLongChainConst* chain_long;
+  const double* T_target;            // as in RdynIkArgs
+  int64_t tt_ss, tt_se;
+  const double* seed;
+  double* sol;                       // may alias seed
+  int64_t n_samples, in_ss, in_sj;
+  double weight[6];
+  int n_var;                         // QP variables (<= RDYN_MAX_JOINTS)
+  int var_in[RDYN_MAX_JOINTS];       // per variable: its index in the input vectors
+  double q_min[RDYN_MAX_JOINTS];     // per variable
+  double q_max[RDYN_MAX_JOINTS];
+  double toll;
+  double damping;
+  int max_iter;
+  int* status;                       // may be null
+  int* iterations;                   // may be null
+};
+size_t rdyn_long_ik_lds_bytes(int n_var);  // dynamic LDS of one 64-lane workgroup
+hipError_t rdyn_launch_long_ik(const RdynLongIkArgs& a, hipStream_t st);
+
 // getFrameDistance family (frame_distance.h) on pairs of frames; element e of record s at base[s * X_ss + e * X_se]
 struct RdynFrameDistanceArgs
 {
