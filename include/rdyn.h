@@ -247,6 +247,27 @@ int rdyn_regressor(const rdyn_chain* chain, const rdyn_batch* batch, double* tau
 /* getJointInertia primitives.h:547 -> n x n column-major per sample */
 int rdyn_joint_inertia(const rdyn_chain* chain, const rdyn_batch* batch, double* M);
 
+/* Forward dynamics (no reference counterpart; defined by the two reference quantities it is built from): per sample ddq solves
+ *     M ddq = tau - h
+ * with M exactly what rdyn_joint_inertia returns for this chain AS CONFIGURED (input-joint selection and order included: joints that
+ * are not input joints stay locked at 0) and h what rdyn_joint_torque_nonlinear returns (Coriolis, centrifugal and gravity terms).
+ * batch->q, batch->dq required, batch->ddq ignored.  tau: n per sample, layout of batch->q; ddq: same shape and layout, may alias tau.
+ * External wrenches and component (friction / spring) torques are additive in tau and are NOT parameters of this call; a caller folds
+ * them in first:  tau - tau_add  with tau_add from rdyn_components_regressor(..., tau_add), and
+ * tau - (rdyn_joint_torque_ext(q, 0, 0, ext) - rdyn_joint_torque(q, 0, 0))  for external wrenches.
+ * status (device int32 per sample, may be NULL): 1 solved; -1 = M not positive definite by the rule of rdyn_local_ik (a Cholesky pivot
+ * <= 1e-10 trace(M)): what a fixed joint listed as an input joint, or a tail of links without <inertial>, produces.  A -1 sample gets
+ * quiet NaN in all its ddq entries; no sample's failure affects another sample.
+ * Chains swept in registers (at most RDYN_MAX_SWEPT_JOINTS input joints; longer chains through their rigid-body reduction): one kernel
+ * launch -- forward sweep, composite-rigid-body M and h, Cholesky and both triangular solves in registers; the workspace query returns
+ * 0 and workspace may be NULL.  More input joints (up to RDYN_MAX_JOINTS, any order): element-major chunk images [M | h] of
+ * chunk_samples samples in the workspace, factorised and solved in place (chunk_samples = 0: as many as keep an image within 128 MiB,
+ * at least 16 384; results do not depend on the chunk size).  No allocation and no synchronisation: capturable into a graph once the
+ * chain has been used on the device (first call outside capture, as for the other entry points). */
+size_t rdyn_forward_dynamics_workspace_bytes(const rdyn_chain* chain, int64_t chunk_samples);
+int rdyn_forward_dynamics(const rdyn_chain* chain, const rdyn_batch* batch, const double* tau, double* ddq, int32_t* status,
+                          int64_t chunk_samples, void* workspace, size_t workspace_bytes);
+
 /* Every getter of a sample in ONE call (no reference counterpart: the reference caches what a call computed on the way, m_last_q,
  * primitives_impl.h:886, 985, 1088, so its harness rosdyn_speed_test.cpp:109-185 pays for the frames once per sample).  Outputs as the
  * single-purpose entry points write them, record layout = batch->layout; any of them may be NULL:

@@ -356,6 +356,23 @@ class Chain(object):
         check(lib().rdyn_joint_inertia(self._h, C.byref(b), M.data_ptr()))
         return M
 
+    def getJointAcceleration(self, q, Dq, tau, layout="sample", out=None, chunk_samples=0, workspace=None):
+        """Forward dynamics (include/rdyn.h: rdyn_forward_dynamics; no reference counterpart): DDq solves
+        getJointInertia(q) DDq = tau - getJointTorqueNonLinearPart(q, Dq) per sample.  Returns (DDq, status): status (N,) int32, 1 solved,
+        -1 the inertia matrix is not positive definite (that sample's DDq is NaN).  out may be tau itself."""
+        torch = _torch()
+        b, N, lay = self._batch(layout, q, Dq, tau)
+        b.ddq = None
+        DDq = self._out(q, N, lay, (self.getActiveJointsNumber(),), out)
+        status = torch.empty((N,), dtype=torch.int32, device=q.device)
+        nbytes = lib().rdyn_forward_dynamics_workspace_bytes(self._h, chunk_samples)
+        if workspace is None and nbytes > 0:
+            workspace = torch.empty((nbytes,), dtype=torch.uint8, device=q.device)
+        check(lib().rdyn_forward_dynamics(self._h, C.byref(b), tau.data_ptr(), DDq.data_ptr(), status.data_ptr(), chunk_samples,
+                                          workspace.data_ptr() if workspace is not None else None,
+                                          workspace.numel() if workspace is not None else 0))
+        return DDq, status
+
     def getRegressor(self, q, Dq, DDq, layout="sample", y_layout=None, out=None, tau_out=None, with_torque=False):
         """Regressor (and optionally the fused joint torque).
 

@@ -537,6 +537,120 @@ int rdyn_joint_inertia(const rdyn_chain* c, const rdyn_batch* b, double* M)
   return run_local(c, b, RDYN_MODE_INERTIA, nullptr, nullptr, nullptr, M, false, false);
 }
 
+// ---- forward dynamics: ddq = M^-1 (tau - h) (rdyn_fwd_dyn.hip) -------------------------------------------------
+// Chains the unrolled kernels sweep (long ones through their reduced companion, which has the same input joints, M and h): one launch,
+// no workspace.  More than RDYN_MAX_SWEPT_JOINTS input joints: element-major chunk images [M | h] ((n n + n) doubles per sample)
+// written by k_long_inertia and the wrench recursion, factorised and solved in place by k_fwd_solve; the default chunk is the rule of
+// rdyn_regressor_gram_wide (an image within 128 MiB, at least 16 384 samples).
+static bool fwd_dyn_by_chunks(const rdyn_chain* c) { return c->long_chain() && !c->reduced; }
+static int64_t fwd_dyn_chunk(const rdyn_chain* c, int64_t chunk_samples)
+{
+  const int64_t n = c->n_active();
+  const int64_t fit = ((int64_t)128 << 20) / ((n * n + n) * (int64_t)sizeof(double)) & ~(int64_t)63;
+  return chunk_samples > 0 ? chunk_samples : (fit > 16384 ? fit : 16384);
+}
+
+size_t rdyn_forward_dynamics_workspace_bytes(const rdyn_chain* c, int64_t chunk_samples)
+{
+  if (!c || c->n_active() < 1 || chunk_samples < 0 || !fwd_dyn_by_chunks(c)) return 0;
+  const size_t n = (size_t)c->n_active();
+  return ((size_t)fwd_dyn_chunk(c, chunk_samples) * (n * n + n) * sizeof(double) + 255) & ~(size_t)255;
+}
+
+int rdyn_forward_dynamics(const rdyn_chain* c, const rdyn_batch* b, const double* tau, double* ddq, int32_t* status, int64_t chunk_samples,
+                          void* workspace, size_t workspace_bytes)
+{
+  int st = check_batch(c, b, true, false, "rdyn_forward_dynamics", LONG_KERNELS);
+  if (st != RDYN_OK) return st;
+  if (b->n_samples > 0 && (!tau || !ddq))
+  {
+    rdyn_set_error("rdyn_forward_dynamics: null torque or acceleration pointer");
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  if (chunk_samples < 0)
+  {
+    rdyn_set_error("rdyn_forward_dynamics: negative chunk_samples");
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  const size_t need = rdyn_forward_dynamics_workspace_bytes(c, chunk_samples);
+  if (b->n_samples > 0 && need > 0 && (!workspace || workspace_bytes < need))
+  {
+    rdyn_set_error("rdyn_forward_dynamics: workspace too small (%zu < %zu bytes)", workspace ? workspace_bytes : (size_t)0, need);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  if (b->n_samples == 0 || c->n_active() < 1) return RDYN_OK;
+  DeviceGuard g;
+  st = g.enter(b->device);
+  if (st != RDYN_OK) return st;
+  hipStream_t stream = (hipStream_t)b->stream;
+  const int n = c->n_active();
+  int64_t in_ss, in_sj;
+  rec_strides(b, n, &in_ss, &in_sj);
+  if (!fwd_dyn_by_chunks(c))
+  {
+    const rdyn_chain* const sw = c->long_chain() ? c->reduced.get() : c;
+    RdynFwdDynArgs a;
+    memset(&a, 0, sizeof a);
+    st = device_const(sw, &a.chain);
+    if (st != RDYN_OK) return st;
+    a.q = b->q;
+    a.dq = b->dq;
+    a.tau = tau;
+    a.ddq = ddq;
+    a.status = status;
+    a.n_samples = b->n_samples;
+    a.in_ss = in_ss;
+    a.in_sj = in_sj;
+    a.staged = (b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(ddq) && !probe_env("RDYN_NO_RECORD_STAGING")) ? n : 0;
+    RDYN_HIP_TRY(rdyn_launch_forward_dynamics(sw->n_joints(), a, stream));
+    return RDYN_OK;
+  }
+  const int64_t chunk = fwd_dyn_chunk(c, chunk_samples);
+  double* const image = (double*)workspace;
+  RdynLongLocalArgs ia;
+  memset(&ia, 0, sizeof ia);
+  st = device_const_long(c, &ia.chain_long);
+  if (st != RDYN_OK) return st;
+  RdynKinExtArgs ha;
+  memset(&ha, 0, sizeof ha);
+  ha.chain_long = ia.chain_long;
+  for (int64_t s0 = 0; s0 < b->n_samples; s0 += chunk)
+  {
+    const int64_t cnt = (b->n_samples - s0 < chunk) ? b->n_samples - s0 : chunk;
+    ia.q = b->q + s0 * in_ss;
+    ia.n_samples = cnt;
+    ia.in_ss = in_ss;
+    ia.in_sj = in_sj;
+    ia.n_active = n;
+    ia.M = image;
+    ia.m_ss = 1;
+    ia.m_se = cnt;
+    RDYN_HIP_TRY(rdyn_launch_long_local(RDYN_MODE_INERTIA, c->n_joints(), ia, stream));
+    ha.q = ia.q;
+    ha.dq = b->dq + s0 * in_ss;
+    ha.n_samples = cnt;
+    ha.in_ss = in_ss;
+    ha.in_sj = in_sj;
+    ha.tau = image + (int64_t)n * n * cnt;
+    ha.tau_ss = 1;
+    ha.tau_sj = cnt;
+    RDYN_HIP_TRY(rdyn_launch_long_ext(c->n_joints(), ha, stream));
+    RdynFwdSolveArgs sa;
+    memset(&sa, 0, sizeof sa);
+    sa.image = image;
+    sa.ld = cnt;
+    sa.n = n;
+    sa.tau = tau + s0 * in_ss;
+    sa.ddq = ddq + s0 * in_ss;
+    sa.status = status ? status + s0 : nullptr;
+    sa.n_samples = cnt;
+    sa.in_ss = in_ss;
+    sa.in_sj = in_sj;
+    RDYN_HIP_TRY(rdyn_launch_forward_solve(sa, stream));
+  }
+  return RDYN_OK;
+}
+
 static int run_base(const rdyn_chain* c, const rdyn_batch* b, double* T_bt, double* T_links, double* J, double* tw, double* dtw,
                     int j_link = -1)
 {

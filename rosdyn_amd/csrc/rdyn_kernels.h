@@ -188,6 +188,31 @@ struct RdynLongLocalArgs
 size_t rdyn_long_local_lds_bytes(int mode, int n_joints);
 hipError_t rdyn_launch_long_local(int mode, int n_joints, const RdynLongLocalArgs& a, hipStream_t st);  // mode: RDYN_MODE_REGRESSOR / RDYN_MODE_INERTIA
 
+// forward dynamics (rdyn_fwd_dyn.hip): ddq = M^-1 (tau - h); tau, ddq addressed like q (ddq may alias tau)
+struct RdynFwdDynArgs
+{
+  const RdynChainConst* chain;
+  const double *q, *dq, *tau;
+  double* ddq;
+  int32_t* status;  // may be null: 1 solved, -1 M not positive definite (the sample's ddq is NaN)
+  int64_t n_samples, in_ss, in_sj;
+  int staged;       // doubles per record (n_active): sample-major records through the wave's LDS tile (natural strides, line-aligned ddq); 0 = 8-byte stores
+};
+hipError_t rdyn_launch_forward_dynamics(int n_joints, const RdynFwdDynArgs& a, hipStream_t st);
+// ... of a chain with more input joints than the unrolled kernels sweep: in-place Cholesky of one element-major chunk image [M | h]
+// (element (i, j) of sample s of the chunk at image[(i n + j) ld + s], h_i at image[(n n + i) ld + s]) and the two triangular solves
+struct RdynFwdSolveArgs
+{
+  double* image;
+  int64_t ld;
+  int n;
+  const double* tau;  // the chunk's first sample
+  double* ddq;
+  int32_t* status;    // may be null
+  int64_t n_samples, in_ss, in_sj;  // samples of the chunk (<= ld)
+};
+hipError_t rdyn_launch_forward_solve(const RdynFwdSolveArgs& a, hipStream_t st);
+
 // Gram / normal equations of a column-major rows x P matrix (rdyn_gram.hip)
 struct RdynGramArgs
 {

@@ -588,6 +588,28 @@ public:
     std::memcpy(m_joint_inertia.data(), m_host.data(), sizeof(double) * n * n);
     return m_joint_inertia;
   }
+  // Forward dynamics (no reference counterpart; include/rdyn.h: rdyn_forward_dynamics): DDq with
+  // getJointInertia(q) DDq = tau - getJointTorqueNonLinearPart(q, Dq).  Throws std::runtime_error when the inertia matrix is not
+  // positive definite (a fixed joint among the input joints, links without <inertial> at the end of the chain).
+  VectorXd getJointAcceleration(const VectorXd& q, const VectorXd& Dq, const VectorXd& tau)
+  {
+    const size_t n = m_active_joints_number;
+    stage(&q, &Dq, &tau);  // tau rides in the DDq slot of the staging buffer
+    // device record after the inputs: DDq (n) | status (int32 in one double) | the one-sample chunk image of the chunked route
+    const size_t ws_bytes = rdyn_forward_dynamics_workspace_bytes(m_h, 1);
+    if (n + 1 + (ws_bytes + 7) / 8 > m_host.size()) throw std::runtime_error("getJointAcceleration: staging buffer too small");
+    int32_t* const flag = reinterpret_cast<int32_t*>(out(n));
+    const double* const d_tau = m_b.ddq;
+    m_b.ddq = nullptr;
+    chk(rdyn_forward_dynamics(m_h, &m_b, d_tau, out(0), flag, 1, ws_bytes ? out(n + 1) : nullptr, ws_bytes));
+    wait_done();
+    int32_t st;
+    std::memcpy(&st, hout(n), sizeof st);
+    if (st != 1) throw std::runtime_error("getJointAcceleration: the joint inertia matrix is not positive definite");
+    VectorXd ddq((int)n);
+    for (size_t i = 0; i < n; ++i) ddq((int)i) = hout(0)[i];
+    return ddq;
+  }
 
   // ---- local inverse kinematics (primitives.h:510, 526).  The reference's wall-clock budget `max_time` becomes an
   // iteration cap; returns the reference's bool (false also when the QP of an iterate is not positive definite).
@@ -775,6 +797,13 @@ public:
     chk(rdyn_regressor(m_h, &b, tau, Y, &yl));
   }
   void getJointInertiaBatch(const rdyn_batch& b, double* M) const { chk(rdyn_joint_inertia(m_h, &b, M)); }
+  // forward dynamics of a batch (b.q, b.dq; tau, ddq in the layout of b.q, ddq may alias tau; status may be null): rdyn_forward_dynamics
+  size_t getJointAccelerationWorkspaceBytes(int64_t chunk_samples = 0) const { return rdyn_forward_dynamics_workspace_bytes(m_h, chunk_samples); }
+  void getJointAccelerationBatch(const rdyn_batch& b, const double* tau, double* ddq, int32_t* status, int64_t chunk_samples, void* workspace,
+                                 size_t workspace_bytes) const
+  {
+    chk(rdyn_forward_dynamics(m_h, &b, tau, ddq, status, chunk_samples, workspace, workspace_bytes));
+  }
   void getTransformationBatch(const rdyn_batch& b, double* T_bt, double* T_links) const { chk(rdyn_transformation(m_h, &b, T_bt, T_links)); }
   void getJacobianBatch(const rdyn_batch& b, double* J) const { chk(rdyn_jacobian(m_h, &b, J)); }
   void getTwistBatch(const rdyn_batch& b, double* twists, double* dtwists) const { chk(rdyn_twist(m_h, &b, twists, dtwists)); }
