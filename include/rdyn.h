@@ -268,6 +268,26 @@ size_t rdyn_forward_dynamics_workspace_bytes(const rdyn_chain* chain, int64_t ch
 int rdyn_forward_dynamics(const rdyn_chain* chain, const rdyn_batch* batch, const double* tau, double* ddq, int32_t* status,
                           int64_t chunk_samples, void* workspace, size_t workspace_bytes);
 
+/* Derivatives of the inverse dynamics (no reference counterpart).  With tau(q, Dq, DDq) exactly the function rdyn_joint_torque
+ * evaluates for this chain AS CONFIGURED (input-joint selection and order, joints that are not input joints locked at 0, fixed joints,
+ * gravity), per sample
+ *     dtau_dq[i][k] = d tau_i / d q_k,   dtau_dv[i][k] = d tau_i / d Dq_k,   M[i][k] = d tau_i / d DDq_k (= rdyn_joint_inertia).
+ * Each output: n x n column-major per sample in RDYN_LAYOUT_SAMPLE_MAJOR, x[e][s] with e = i + n k in RDYN_LAYOUT_ELEMENT_MAJOR (the
+ * shape rules of rdyn_joint_inertia); rows and columns in input-joint order.  batch->q, dq and ddq are required.  Any output may be
+ * NULL and is then not computed; all three NULL with n_samples > 0 is RDYN_ERR_INVALID_ARGUMENT.
+ * External wrenches and component (friction / spring) torques are NOT parameters: both are additive in tau, so their derivatives are
+ * the caller's to add -- in particular the Dq-derivative of a friction component (diagonal) goes on dtau_dv.
+ * Derivatives of the forward dynamics DDq = FD(q, Dq, tau) follow without a second entry point: evaluate this call at
+ * DDq = FD(q, Dq, tau) (rdyn_forward_dynamics), then
+ *     d DDq / d q = -M^-1 dtau_dq,     d DDq / d Dq = -M^-1 dtau_dv,     d DDq / d tau = M^-1.
+ * Up to RDYN_MAX_SWEPT_JOINTS input joints (longer chains through their rigid-body reduction): one launch, a forward-mode tangent of
+ * the recursive Newton-Euler sweep per input joint, O(n^2) per sample.  More input joints (up to RDYN_MAX_JOINTS, any order): one
+ * launch with the per-joint state in LDS for the two derivative matrices, plus the launch of the inertia kernel when M is requested (two
+ * launches then); RDYN_ERR_UNSUPPORTED if that state does not fit the LDS the device grants one workgroup (160 KB on gfx950, where
+ * every chain up to RDYN_MAX_JOINTS fits; the figure is the runtime's, asked once per device).  No workspace, no allocation, no synchronisation: capturable into a graph once the chain
+ * has been used on the device. */
+int rdyn_joint_torque_derivatives(const rdyn_chain* chain, const rdyn_batch* batch, double* dtau_dq, double* dtau_dv, double* M);
+
 /* Every getter of a sample in ONE call (no reference counterpart: the reference caches what a call computed on the way, m_last_q,
  * primitives_impl.h:886, 985, 1088, so its harness rosdyn_speed_test.cpp:109-185 pays for the frames once per sample).  Outputs as the
  * single-purpose entry points write them, record layout = batch->layout; any of them may be NULL:

@@ -373,6 +373,23 @@ class Chain(object):
                                           workspace.numel() if workspace is not None else 0))
         return DDq, status
 
+    def getJointTorqueDerivatives(self, q, Dq, DDq, layout="sample", want=("dq", "dv"), out=None):
+        """Derivatives of getJointTorque (include/rdyn.h: rdyn_joint_torque_derivatives; no reference counterpart).  want: any non-empty
+        selection of "dq" (d tau / d q), "dv" (d tau / d Dq) and "M" (d tau / d DDq = getJointInertia); returns the tensors in the order of
+        `want` (a single tensor when one name is given as a string).  Records as getJointInertia's: (N, n, n) with t[s, k, i] = d tau_i / d x_k
+        (the transpose of the column-major n x n matrix) for layout="sample", (n, n, N) with t[k, i, s] for "element".
+        out: None, or a dict name -> preallocated tensor."""
+        single = isinstance(want, str)
+        names = (want,) if single else tuple(want)
+        if not names or len(set(names)) != len(names) or any(k not in ("dq", "dv", "M") for k in names):
+            raise ValueError('want must be a non-empty selection of "dq", "dv", "M"')
+        b, N, lay = self._batch(layout, q, Dq, DDq)
+        n = self.getActiveJointsNumber()
+        res = {k: self._out(q, N, lay, (n, n), (out or {}).get(k)) for k in names}
+        ptr = [res[k].data_ptr() if k in res else None for k in ("dq", "dv", "M")]
+        check(lib().rdyn_joint_torque_derivatives(self._h, C.byref(b), *ptr))
+        return res[names[0]] if single else tuple(res[k] for k in names)
+
     def getRegressor(self, q, Dq, DDq, layout="sample", y_layout=None, out=None, tau_out=None, with_torque=False):
         """Regressor (and optionally the fused joint torque).
 

@@ -651,6 +651,64 @@ int rdyn_forward_dynamics(const rdyn_chain* c, const rdyn_batch* b, const double
   return RDYN_OK;
 }
 
+// ---- derivatives of the joint torque: dtau/dq, dtau/dDq, M (rdyn_torque_deriv.hip) ------------------------------
+// Chains the unrolled kernels sweep (long ones through their reduced companion: the same function of the inputs): one launch.  More than
+// RDYN_MAX_SWEPT_JOINTS input joints: the rolled kernel for the two derivative matrices, k_long_inertia for M.
+int rdyn_joint_torque_derivatives(const rdyn_chain* c, const rdyn_batch* b, double* dtau_dq, double* dtau_dv, double* M)
+{
+  int st = check_batch(c, b, true, true, "rdyn_joint_torque_derivatives", LONG_KERNELS);
+  if (st != RDYN_OK) return st;
+  if (b->n_samples > 0 && !dtau_dq && !dtau_dv && !M)
+  {
+    rdyn_set_error("rdyn_joint_torque_derivatives: every output is null");
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  if (b->n_samples == 0 || c->n_active() < 1) return RDYN_OK;
+  const int n = c->n_active();
+  const bool by_long = c->long_chain() && !c->reduced;
+  DeviceGuard g;
+  st = g.enter(b->device);
+  if (st != RDYN_OK) return st;
+  if (by_long && (dtau_dq || dtau_dv) && rdyn_long_torque_deriv_lanes(c->n_joints()) == 0)
+  {
+    // the per-joint state of a workgroup's samples must fit the LDS the batch's device grants one workgroup (the runtime's figure, read once
+    // per device): a launch that asks for more fails without a trace.  gfx950 grants 160 KB and RDYN_MAX_JOINTS joints ask for 108 KB, so this
+    // answer is for devices with less (64 KB: chains beyond 18 joints)
+    rdyn_set_error("rdyn_joint_torque_derivatives: the per-joint state of a chain of %d joints (%zu bytes for 16 samples) exceeds the LDS a "
+                   "workgroup may use on this device",
+                   c->n_joints(), rdyn_long_torque_deriv_lds_bytes(c->n_joints(), 16));
+    return RDYN_ERR_UNSUPPORTED;
+  }
+  RdynTorqueDerivArgs a;
+  memset(&a, 0, sizeof a);
+  a.q = b->q;
+  a.dq = b->dq;
+  a.ddq = b->ddq;
+  a.n_samples = b->n_samples;
+  rec_strides(b, n, &a.in_ss, &a.in_sj);
+  rec_strides(b, (int64_t)n * n, &a.m_ss, &a.m_se);
+  a.dtau_dq = dtau_dq;
+  a.dtau_dv = dtau_dv;
+  a.M = M;
+  if (!by_long)
+  {
+    const rdyn_chain* const sw = c->long_chain() ? c->reduced.get() : c;
+    st = device_const(sw, &a.chain);
+    if (st != RDYN_OK) return st;
+    a.staged = (b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(dtau_dq, dtau_dv, M) && !probe_env("RDYN_NO_RECORD_STAGING")) ? n * n : 0;
+    RDYN_HIP_TRY(rdyn_launch_torque_derivatives(sw->n_joints(), a, (hipStream_t)b->stream));
+    return RDYN_OK;
+  }
+  if (dtau_dq || dtau_dv)
+  {
+    st = device_const_long(c, &a.chain_long);
+    if (st != RDYN_OK) return st;
+    RDYN_HIP_TRY(rdyn_launch_long_torque_derivatives(c->n_joints(), a, (hipStream_t)b->stream));
+  }
+  if (M) return run_long_local(c, b, RDYN_MODE_INERTIA, nullptr, nullptr, nullptr, M);
+  return RDYN_OK;
+}
+
 static int run_base(const rdyn_chain* c, const rdyn_batch* b, double* T_bt, double* T_links, double* J, double* tw, double* dtw,
                     int j_link = -1)
 {

@@ -213,6 +213,25 @@ struct RdynFwdSolveArgs
 };
 hipError_t rdyn_launch_forward_solve(const RdynFwdSolveArgs& a, hipStream_t st);
 
+// derivatives of the joint torque (rdyn_torque_deriv.hip): dtau/dq, dtau/dDq, M = dtau/dDDq; every output n x n per sample, element
+// e = i + n k of sample s at X[s * m_ss + e * m_se]; any output may be null (not all three)
+struct RdynTorqueDerivArgs
+{
+  const RdynChainConst* chain;           // rdyn_launch_torque_derivatives
+  const RdynLongChainConst* chain_long;  // rdyn_launch_long_torque_derivatives
+  const double *q, *dq, *ddq;
+  int64_t n_samples, in_ss, in_sj;
+  double *dtau_dq, *dtau_dv, *M;
+  int64_t m_ss, m_se;
+  int staged;  // doubles per record (n n): sample-major records through the wave's LDS tile (natural strides, every output line-aligned); 0 = 8-byte stores
+};
+hipError_t rdyn_launch_torque_derivatives(int n_joints, const RdynTorqueDerivArgs& a, hipStream_t st);
+// ... of a chain with more input joints than the unrolled kernels sweep (dtau_dq, dtau_dv only; M: rdyn_launch_long_local).  The per-joint
+// state of a workgroup's samples lives in LDS: rdyn_long_torque_deriv_lanes = samples per workgroup (64, 32 or 16; 0: no width fits)
+int rdyn_long_torque_deriv_lanes(int n_joints);
+size_t rdyn_long_torque_deriv_lds_bytes(int n_joints, int lanes);
+hipError_t rdyn_launch_long_torque_derivatives(int n_joints, const RdynTorqueDerivArgs& a, hipStream_t st);
+
 // Gram / normal equations of a column-major rows x P matrix (rdyn_gram.hip)
 struct RdynGramArgs
 {

@@ -611,6 +611,21 @@ public:
     return ddq;
   }
 
+  // Derivatives of getJointTorque (no reference counterpart; include/rdyn.h: rdyn_joint_torque_derivatives):
+  // dtau_dq(i, k) = d tau_i / d q_k, dtau_dDq(i, k) = d tau_i / d Dq_k for the chain as configured; d tau / d DDq is getJointInertia(q).
+  void getJointTorqueDerivatives(const VectorXd& q, const VectorXd& Dq, const VectorXd& DDq, MatrixXd& dtau_dq, MatrixXd& dtau_dDq)
+  {
+    if (q.rows() != Dq.rows() || Dq.rows() != DDq.rows()) throw std::invalid_argument("Input data dimensions mismatch");
+    const int n = (int)m_active_joints_number;
+    stage(&q, &Dq, &DDq);
+    if (2 * (size_t)n * n > m_host.size()) throw std::runtime_error("getJointTorqueDerivatives: staging buffer too small");
+    run(rdyn_joint_torque_derivatives(m_h, &m_b, out(0), out((size_t)n * n), nullptr), 2 * (size_t)n * n);
+    dtau_dq.resize(n, n);
+    dtau_dDq.resize(n, n);
+    std::memcpy(dtau_dq.data(), m_host.data(), sizeof(double) * n * n);
+    std::memcpy(dtau_dDq.data(), m_host.data() + (size_t)n * n, sizeof(double) * n * n);
+  }
+
   // ---- local inverse kinematics (primitives.h:510, 526).  The reference's wall-clock budget `max_time` becomes an
   // iteration cap; returns the reference's bool (false also when the QP of an iterate is not positive definite).
   bool computeLocalIk(VectorXd& sol, const Affine3d& T_b_t, const VectorXd& seed, const double& toll = 1e-4, int max_iterations = 100)
@@ -803,6 +818,11 @@ public:
                                  size_t workspace_bytes) const
   {
     chk(rdyn_forward_dynamics(m_h, &b, tau, ddq, status, chunk_samples, workspace, workspace_bytes));
+  }
+  // derivatives of the joint torque of a batch (b.q, b.dq, b.ddq; every output n x n per sample, any may be null): rdyn_joint_torque_derivatives
+  void getJointTorqueDerivativesBatch(const rdyn_batch& b, double* dtau_dq, double* dtau_dDq, double* M = nullptr) const
+  {
+    chk(rdyn_joint_torque_derivatives(m_h, &b, dtau_dq, dtau_dDq, M));
   }
   void getTransformationBatch(const rdyn_batch& b, double* T_bt, double* T_links) const { chk(rdyn_transformation(m_h, &b, T_bt, T_links)); }
   void getJacobianBatch(const rdyn_batch& b, double* J) const { chk(rdyn_jacobian(m_h, &b, J)); }
