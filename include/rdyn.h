@@ -268,6 +268,56 @@ size_t rdyn_forward_dynamics_workspace_bytes(const rdyn_chain* chain, int64_t ch
 int rdyn_forward_dynamics(const rdyn_chain* chain, const rdyn_batch* batch, const double* tau, double* ddq, int32_t* status,
                           int64_t chunk_samples, void* workspace, size_t workspace_bytes);
 
+/* Rollouts (no reference counterpart: the reference has no integrator): per sample, n_steps steps of size dt of
+ *     x' = f(x),  x = (q, Dq),  f(x) = (Dq, FD(q, Dq, tau_t))
+ * from the initial state batch->q, batch->dq (batch->ddq is ignored).  FD is exactly what rdyn_forward_dynamics defines for this chain AS
+ * CONFIGURED (input-joint selection and order, joints that are not input joints locked at 0, the reduced companion of a long chain with at
+ * most RDYN_MAX_SWEPT_JOINTS input joints, gravity).  The torques are held over a step (zero-order hold): step t uses the n values per
+ * sample at tau + t * tau_step_stride, addressed like batch->q; tau_step_stride = 0 applies the same torques at every step.
+ *   RDYN_INTEGRATOR_SEMI_IMPLICIT_EULER   DDq = FD(q_t, Dq_t, tau_t);  Dq_{t+1} = Dq_t + dt DDq;  q_{t+1} = q_t + dt Dq_{t+1}
+ *   RDYN_INTEGRATOR_RK4                   the classical four-stage scheme (stage states x, x + dt/2 k1, x + dt/2 k2, x + dt k3; weights
+ *                                         1/6, 1/3, 1/3, 1/6): four evaluations of FD per step, all with tau_t
+ * dt is finite and not 0; a negative dt integrates backwards.
+ * Outputs, each in the layout of batch->q and each optional (not all four NULL when n_samples > 0): q_end, dq_end = the state after
+ * n_steps steps (q_end may alias batch->q and dq_end batch->dq); q_traj, dq_traj = a decimated trajectory: record k, at
+ * + k * traj_step_stride doubles, is the state after step (k + 1) * traj_every; floor(n_steps / traj_every) records are written, so
+ * traj_step_stride >= n * n_samples and traj_every >= 1 are required when either pointer is given.  n_steps = 0 copies the initial
+ * state to the end state.
+ * status (device int32 per sample, may be NULL): 1 if every evaluation of the sample solved, -1 if one did not by the pivot rule of
+ * rdyn_forward_dynamics.  From the failing step on every state of that sample -- the end state and all later trajectory records -- is
+ * quiet NaN; the failure is sticky and no sample affects another.
+ * Friction and spring components and external wrenches are NOT parameters of this call: they depend on the state, so unlike in
+ * rdyn_forward_dynamics a caller cannot fold them into tau across steps (left for a follow-up).  No joint limits, no adaptive steps.
+ * Chains swept in registers (at most RDYN_MAX_SWEPT_JOINTS input joints; longer chains through their rigid-body reduction): ONE kernel
+ * launch for the whole horizon, the state in registers between the steps; a step reads n torques per sample and writes only the
+ * trajectory record that is due; the workspace query returns 0 and workspace may be NULL.  More input joints (up to RDYN_MAX_JOINTS, any
+ * order): the chunked route of rdyn_forward_dynamics once per stage on the batch's stream plus one element-wise update launch; state and
+ * stage buffers live in the workspace behind the forward-dynamics images (chunk_samples as in rdyn_forward_dynamics; results do not
+ * depend on it).  A horizon split anywhere into chained calls gives bitwise the state of the single call.
+ * Errors, all RDYN_ERR_INVALID_ARGUMENT before any device work: NULL desc; NULL tau with n_steps > 0; all four outputs NULL with
+ * n_samples > 0; n_steps < 0; dt zero or not finite; an unknown integrator; a trajectory pointer with traj_every < 1 or
+ * traj_step_stride < n * n_samples; negative chunk_samples; a workspace smaller than the query's answer.  n_samples = 0 is RDYN_OK.
+ * No allocation and no synchronisation: capturable into a graph once the chain has been used on the device. */
+typedef enum rdyn_integrator { RDYN_INTEGRATOR_SEMI_IMPLICIT_EULER = 0, RDYN_INTEGRATOR_RK4 = 1 } rdyn_integrator;
+typedef struct rdyn_rollout_desc
+{
+  int32_t n_steps;           /* T >= 0 */
+  int32_t integrator;        /* rdyn_integrator */
+  double dt;                 /* finite, != 0 */
+  const double* tau;         /* step t at tau + t * tau_step_stride, addressed like batch->q */
+  int64_t tau_step_stride;   /* in doubles; 0 = the same torques at every step */
+  double* q_end;             /* state after T steps, layout of batch->q; may alias batch->q / batch->dq; each may be NULL */
+  double* dq_end;
+  double* q_traj;            /* optional: record k = the state after step (k + 1) * traj_every, at + k * traj_step_stride */
+  double* dq_traj;
+  int64_t traj_step_stride;  /* in doubles, >= n * N when a trajectory is requested */
+  int32_t traj_every;        /* >= 1 when a trajectory is requested; floor(T / traj_every) records are written */
+  int32_t* status;           /* per sample, may be NULL */
+} rdyn_rollout_desc;
+size_t rdyn_rollout_workspace_bytes(const rdyn_chain* chain, const rdyn_rollout_desc* desc, int64_t n_samples, int64_t chunk_samples);
+int rdyn_rollout(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_rollout_desc* desc, int64_t chunk_samples, void* workspace,
+                 size_t workspace_bytes);
+
 /* Derivatives of the inverse dynamics (no reference counterpart).  With tau(q, Dq, DDq) exactly the function rdyn_joint_torque
  * evaluates for this chain AS CONFIGURED (input-joint selection and order, joints that are not input joints locked at 0, fixed joints,
  * gravity), per sample

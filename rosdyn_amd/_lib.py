@@ -26,6 +26,15 @@ class RegressorLayout(C.Structure):
     _fields_ = [("stride_sample", C.c_int64), ("stride_row", C.c_int64), ("stride_col", C.c_int64)]
 
 
+class RolloutDesc(C.Structure):
+    _fields_ = [("n_steps", C.c_int32), ("integrator", C.c_int32), ("dt", C.c_double), ("tau", C.c_void_p), ("tau_step_stride", C.c_int64),
+                ("q_end", C.c_void_p), ("dq_end", C.c_void_p), ("q_traj", C.c_void_p), ("dq_traj", C.c_void_p),
+                ("traj_step_stride", C.c_int64), ("traj_every", C.c_int32), ("status", C.c_void_p)]
+
+
+INTEGRATORS = {"semi_implicit_euler": 0, "euler": 0, "rk4": 1}
+
+
 class Component(C.Structure):
     _fields_ = [("type", C.c_int32), ("joint", C.c_int32), ("min_velocity", C.c_double), ("max_velocity", C.c_double),
                 ("parameters", C.c_double * 3)]
@@ -91,6 +100,8 @@ SYMBOLS = {
     "rdyn_joint_inertia": (_I, [_VP, _BP, _VP]),
     "rdyn_forward_dynamics_workspace_bytes": (C.c_size_t, [_VP, C.c_int64]),
     "rdyn_forward_dynamics": (_I, [_VP, _BP, _VP, _VP, _VP, C.c_int64, _VP, C.c_size_t]),
+    "rdyn_rollout_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(RolloutDesc), C.c_int64, C.c_int64]),
+    "rdyn_rollout": (_I, [_VP, _BP, C.POINTER(RolloutDesc), C.c_int64, _VP, C.c_size_t]),
     "rdyn_joint_torque_derivatives": (_I, [_VP, _BP, _VP, _VP, _VP]),
     "rdyn_local_ik": (_I, [_VP, _BP, _VP, _DP, C.c_double, _I, _VP, _VP, _VP]),
     "rdyn_local_ik_damped": (_I, [_VP, _BP, _VP, _DP, C.c_double, C.c_double, _I, _VP, _VP, _VP]),

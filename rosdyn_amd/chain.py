@@ -373,6 +373,55 @@ class Chain(object):
                                           workspace.numel() if workspace is not None else 0))
         return DDq, status
 
+    def rollout(self, q0, Dq0, tau, dt, integrator="rk4", n_steps=None, layout="sample", trajectory_every=0, out=None, chunk_samples=0,
+                workspace=None):
+        """Rollout (include/rdyn.h: rdyn_rollout; no reference counterpart): n_steps integrator steps of size dt of the forward dynamics
+        from (q0, Dq0), the torques held over each step.  integrator: "rk4" or "semi_implicit_euler" ("euler").
+        tau: (T, N, n) for layout="sample", (T, n, N) for "element" -- n_steps defaults to T and may be smaller; or (N, n) / (n, N) with an
+        explicit n_steps: the same torques at every step.
+        Returns (q_end, Dq_end, status), and with trajectory_every = k >= 1 also (q_traj, Dq_traj): n_steps // k records, record r = the
+        state after step (r + 1) k, shaped (records,) + q0.shape.  status (N,) int32: 1, or -1 from the step on at which the inertia
+        matrix was not positive definite (NaN state from then on).  out: None or (q_end, Dq_end) tensors; they may be q0 and Dq0."""
+        torch = _torch()
+        b, N, lay = self._batch(layout, q0, Dq0)
+        if integrator not in _lib.INTEGRATORS:
+            raise ValueError("unknown integrator %r" % (integrator,))
+        if tau.dtype != torch.float64 or not tau.is_cuda or not tau.is_contiguous() or tau.device != q0.device:
+            raise ValueError("inputs must be contiguous float64 CUDA tensors")
+        if tau.dim() == 3 and tuple(tau.shape[1:]) == tuple(q0.shape):
+            stride = q0.numel()
+            if n_steps is None:
+                n_steps = tau.shape[0]
+            elif n_steps > tau.shape[0]:
+                raise ValueError("Input data dimensions mismatch")
+        elif tau.dim() == 2 and tuple(tau.shape) == tuple(q0.shape) and n_steps is not None:
+            stride = 0
+        else:
+            raise ValueError("Input data dimensions mismatch")
+        n = self.getActiveJointsNumber()
+        q_end, dq_end = out if out is not None else (None, None)
+        q_end, dq_end = self._out(q0, N, lay, (n,), q_end), self._out(q0, N, lay, (n,), dq_end)
+        status = torch.empty((N,), dtype=torch.int32, device=q0.device)
+        d = _lib.RolloutDesc()
+        d.n_steps, d.integrator, d.dt = int(n_steps), _lib.INTEGRATORS[integrator], float(dt)
+        d.tau, d.tau_step_stride = tau.data_ptr(), stride
+        d.q_end, d.dq_end, d.status = q_end.data_ptr(), dq_end.data_ptr(), status.data_ptr()
+        q_traj = dq_traj = None
+        if trajectory_every:
+            records = max(int(n_steps), 0) // int(trajectory_every) if trajectory_every > 0 else 0
+            q_traj = torch.empty((records,) + tuple(q0.shape), dtype=torch.float64, device=q0.device)
+            dq_traj = torch.empty_like(q_traj)
+            d.q_traj, d.dq_traj = q_traj.data_ptr(), dq_traj.data_ptr()
+            d.traj_step_stride, d.traj_every = q0.numel(), int(trajectory_every)
+        nbytes = lib().rdyn_rollout_workspace_bytes(self._h, C.byref(d), N, chunk_samples)
+        if workspace is None and nbytes > 0:
+            workspace = torch.empty((nbytes,), dtype=torch.uint8, device=q0.device)
+        check(lib().rdyn_rollout(self._h, C.byref(b), C.byref(d), chunk_samples, workspace.data_ptr() if workspace is not None else None,
+                                 workspace.numel() if workspace is not None else 0))
+        if trajectory_every:
+            return q_end, dq_end, status, q_traj, dq_traj
+        return q_end, dq_end, status
+
     def getJointTorqueDerivatives(self, q, Dq, DDq, layout="sample", want=("dq", "dv"), out=None):
         """Derivatives of getJointTorque (include/rdyn.h: rdyn_joint_torque_derivatives; no reference counterpart).  want: any non-empty
         selection of "dq" (d tau / d q), "dv" (d tau / d Dq) and "M" (d tau / d DDq = getJointInertia); returns the tensors in the order of

@@ -550,6 +550,55 @@ static int64_t fwd_dyn_chunk(const rdyn_chain* c, int64_t chunk_samples)
   return chunk_samples > 0 ? chunk_samples : (fit > 16384 ? fit : 16384);
 }
 
+// one pass of the chunked route over n_samples samples: per chunk the image [M | h] (k_long_inertia, the wrench recursion), then k_fwd_solve
+static int fwd_dyn_chunks(const rdyn_chain* c, const double* q, const double* dq, const double* tau, double* ddq, int32_t* status,
+                          int64_t n_samples, int64_t in_ss, int64_t in_sj, int64_t chunk, double* image, hipStream_t stream)
+{
+  const int n = c->n_active();
+  RdynLongLocalArgs ia;
+  memset(&ia, 0, sizeof ia);
+  int st = device_const_long(c, &ia.chain_long);
+  if (st != RDYN_OK) return st;
+  RdynKinExtArgs ha;
+  memset(&ha, 0, sizeof ha);
+  ha.chain_long = ia.chain_long;
+  for (int64_t s0 = 0; s0 < n_samples; s0 += chunk)
+  {
+    const int64_t cnt = (n_samples - s0 < chunk) ? n_samples - s0 : chunk;
+    ia.q = q + s0 * in_ss;
+    ia.n_samples = cnt;
+    ia.in_ss = in_ss;
+    ia.in_sj = in_sj;
+    ia.n_active = n;
+    ia.M = image;
+    ia.m_ss = 1;
+    ia.m_se = cnt;
+    RDYN_HIP_TRY(rdyn_launch_long_local(RDYN_MODE_INERTIA, c->n_joints(), ia, stream));
+    ha.q = ia.q;
+    ha.dq = dq + s0 * in_ss;
+    ha.n_samples = cnt;
+    ha.in_ss = in_ss;
+    ha.in_sj = in_sj;
+    ha.tau = image + (int64_t)n * n * cnt;
+    ha.tau_ss = 1;
+    ha.tau_sj = cnt;
+    RDYN_HIP_TRY(rdyn_launch_long_ext(c->n_joints(), ha, stream));
+    RdynFwdSolveArgs sa;
+    memset(&sa, 0, sizeof sa);
+    sa.image = image;
+    sa.ld = cnt;
+    sa.n = n;
+    sa.tau = tau + s0 * in_ss;
+    sa.ddq = ddq + s0 * in_ss;
+    sa.status = status ? status + s0 : nullptr;
+    sa.n_samples = cnt;
+    sa.in_ss = in_ss;
+    sa.in_sj = in_sj;
+    RDYN_HIP_TRY(rdyn_launch_forward_solve(sa, stream));
+  }
+  return RDYN_OK;
+}
+
 size_t rdyn_forward_dynamics_workspace_bytes(const rdyn_chain* c, int64_t chunk_samples)
 {
   if (!c || c->n_active() < 1 || chunk_samples < 0 || !fwd_dyn_by_chunks(c)) return 0;
@@ -605,49 +654,174 @@ int rdyn_forward_dynamics(const rdyn_chain* c, const rdyn_batch* b, const double
     RDYN_HIP_TRY(rdyn_launch_forward_dynamics(sw->n_joints(), a, stream));
     return RDYN_OK;
   }
-  const int64_t chunk = fwd_dyn_chunk(c, chunk_samples);
-  double* const image = (double*)workspace;
-  RdynLongLocalArgs ia;
-  memset(&ia, 0, sizeof ia);
-  st = device_const_long(c, &ia.chain_long);
+  return fwd_dyn_chunks(c, b->q, b->dq, tau, ddq, status, b->n_samples, in_ss, in_sj, fwd_dyn_chunk(c, chunk_samples), (double*)workspace, stream);
+}
+
+// ---- rollouts: T integrator steps of the forward dynamics (rdyn_rollout.hip) ------------------------------------
+// Chains the unrolled kernels sweep: one launch for the whole horizon.  More input joints: per stage the chunked forward dynamics above,
+// then k_rollout_stage; behind the forward-dynamics images the workspace holds, each n N doubles in the batch's layout, q | dq | ddq and for
+// RK4 sq | sv | aq | av, then two int32 per sample (the pass's status, the running minimum).
+static size_t rollout_state_arrays(int integrator) { return integrator == RDYN_INTEGRATOR_RK4 ? 7 : 3; }
+static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+size_t rdyn_rollout_workspace_bytes(const rdyn_chain* c, const rdyn_rollout_desc* d, int64_t n_samples, int64_t chunk_samples)
+{
+  if (!c || !d || c->n_active() < 1 || n_samples < 0 || chunk_samples < 0 || !fwd_dyn_by_chunks(c)) return 0;
+  const size_t arr = align256((size_t)n_samples * (size_t)c->n_active() * sizeof(double));
+  return rdyn_forward_dynamics_workspace_bytes(c, chunk_samples) + rollout_state_arrays(d->integrator) * arr +
+         2 * align256((size_t)n_samples * sizeof(int32_t));
+}
+
+int rdyn_rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_desc* d, int64_t chunk_samples, void* workspace,
+                 size_t workspace_bytes)
+{
+  int st = check_batch(c, b, true, false, "rdyn_rollout", LONG_KERNELS);
   if (st != RDYN_OK) return st;
-  RdynKinExtArgs ha;
-  memset(&ha, 0, sizeof ha);
-  ha.chain_long = ia.chain_long;
-  for (int64_t s0 = 0; s0 < b->n_samples; s0 += chunk)
+  if (!d)
   {
-    const int64_t cnt = (b->n_samples - s0 < chunk) ? b->n_samples - s0 : chunk;
-    ia.q = b->q + s0 * in_ss;
-    ia.n_samples = cnt;
-    ia.in_ss = in_ss;
-    ia.in_sj = in_sj;
-    ia.n_active = n;
-    ia.M = image;
-    ia.m_ss = 1;
-    ia.m_se = cnt;
-    RDYN_HIP_TRY(rdyn_launch_long_local(RDYN_MODE_INERTIA, c->n_joints(), ia, stream));
-    ha.q = ia.q;
-    ha.dq = b->dq + s0 * in_ss;
-    ha.n_samples = cnt;
-    ha.in_ss = in_ss;
-    ha.in_sj = in_sj;
-    ha.tau = image + (int64_t)n * n * cnt;
-    ha.tau_ss = 1;
-    ha.tau_sj = cnt;
-    RDYN_HIP_TRY(rdyn_launch_long_ext(c->n_joints(), ha, stream));
-    RdynFwdSolveArgs sa;
-    memset(&sa, 0, sizeof sa);
-    sa.image = image;
-    sa.ld = cnt;
-    sa.n = n;
-    sa.tau = tau + s0 * in_ss;
-    sa.ddq = ddq + s0 * in_ss;
-    sa.status = status ? status + s0 : nullptr;
-    sa.n_samples = cnt;
-    sa.in_ss = in_ss;
-    sa.in_sj = in_sj;
-    RDYN_HIP_TRY(rdyn_launch_forward_solve(sa, stream));
+    rdyn_set_error("rdyn_rollout: null descriptor");
+    return RDYN_ERR_INVALID_ARGUMENT;
   }
+  const int n = c->n_active();
+  const int64_t N = b->n_samples;
+  if (d->n_steps < 0 || !std::isfinite(d->dt) || d->dt == 0.0 ||
+      (d->integrator != RDYN_INTEGRATOR_SEMI_IMPLICIT_EULER && d->integrator != RDYN_INTEGRATOR_RK4))
+  {
+    rdyn_set_error("rdyn_rollout: negative n_steps, a step size that is zero or not finite, or an unknown integrator");
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  if (d->n_steps > 0 && !d->tau)
+  {
+    rdyn_set_error("rdyn_rollout: null torque pointer");
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  const bool traj = d->q_traj || d->dq_traj;
+  if (N > 0 && !d->q_end && !d->dq_end && !traj)
+  {
+    rdyn_set_error("rdyn_rollout: every output is null");
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  if (traj && (d->traj_every < 1 || d->traj_step_stride < (int64_t)n * N))
+  {
+    rdyn_set_error("rdyn_rollout: a trajectory needs traj_every >= 1 and traj_step_stride >= n * n_samples");
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  if (chunk_samples < 0)
+  {
+    rdyn_set_error("rdyn_rollout: negative chunk_samples");
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  const size_t need = rdyn_rollout_workspace_bytes(c, d, N, chunk_samples);
+  if (N > 0 && need > 0 && (!workspace || workspace_bytes < need))
+  {
+    rdyn_set_error("rdyn_rollout: workspace too small (%zu < %zu bytes)", workspace ? workspace_bytes : (size_t)0, need);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  if (N == 0 || n < 1) return RDYN_OK;
+  DeviceGuard g;
+  st = g.enter(b->device);
+  if (st != RDYN_OK) return st;
+  hipStream_t stream = (hipStream_t)b->stream;
+  int64_t in_ss, in_sj;
+  rec_strides(b, n, &in_ss, &in_sj);
+  const int every = traj ? d->traj_every : 0;
+  if (!fwd_dyn_by_chunks(c))
+  {
+    const rdyn_chain* const sw = c->long_chain() ? c->reduced.get() : c;
+    RdynRolloutArgs a;
+    memset(&a, 0, sizeof a);
+    st = device_const(sw, &a.chain);
+    if (st != RDYN_OK) return st;
+    a.q = b->q;
+    a.dq = b->dq;
+    a.tau = d->tau;
+    a.tau_step = d->tau_step_stride;
+    a.q_end = d->q_end;
+    a.dq_end = d->dq_end;
+    a.q_traj = d->q_traj;
+    a.dq_traj = d->dq_traj;
+    a.traj_step = d->traj_step_stride;
+    a.status = d->status;
+    a.n_samples = N;
+    a.in_ss = in_ss;
+    a.in_sj = in_sj;
+    a.dt = d->dt;
+    a.n_steps = d->n_steps;
+    a.traj_every = every;
+    a.integrator = d->integrator;
+    a.n_active = n;
+    if (b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && !probe_env("RDYN_NO_RECORD_STAGING"))
+    {
+      // whole lines: every record of the kind starts on a line (the trajectory's step stride keeps the alignment of its first record)
+      if ((d->q_end || d->dq_end) && lines_aligned(d->q_end, d->dq_end)) a.staged |= 1;
+      if (traj && lines_aligned(d->q_traj, d->dq_traj) && (d->traj_step_stride * (int64_t)sizeof(double)) % 128 == 0) a.staged |= 2;
+    }
+    RDYN_HIP_TRY(rdyn_launch_rollout(sw->n_joints(), a, stream));
+    return RDYN_OK;
+  }
+  const int64_t chunk = fwd_dyn_chunk(c, chunk_samples);
+  const int64_t count = (int64_t)n * N;
+  const size_t arr = align256((size_t)count * sizeof(double));
+  char* p = (char*)workspace + rdyn_forward_dynamics_workspace_bytes(c, chunk_samples);
+  double* ws[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (size_t i = 0; i < rollout_state_arrays(d->integrator); ++i, p += arr) ws[i] = (double*)p;
+  int32_t* const st_stage = (int32_t*)p;
+  int32_t* const st_run = (int32_t*)(p + align256((size_t)N * sizeof(int32_t)));
+  double *const q = ws[0], *const dq = ws[1], *const ddq = ws[2], *const sq = ws[3], *const sv = ws[4];
+  RdynRolloutCopyArgs ca;
+  memset(&ca, 0, sizeof ca);
+  ca.q_src = b->q;
+  ca.dq_src = b->dq;
+  ca.q_dst = q;
+  ca.dq_dst = dq;
+  ca.st_dst = st_run;
+  ca.count = count;
+  ca.n_samples = N;
+  RDYN_HIP_TRY(rdyn_launch_rollout_copy(ca, stream));
+  RdynRolloutStageArgs sa;
+  memset(&sa, 0, sizeof sa);
+  sa.q = q;
+  sa.dq = dq;
+  sa.sq = sq;
+  sa.sv = sv;
+  sa.aq = ws[5];
+  sa.av = ws[6];
+  sa.ddq = ddq;
+  sa.st_stage = st_stage;
+  sa.st_run = st_run;
+  sa.count = count;
+  sa.n_samples = N;
+  sa.n = n;
+  sa.element_major = b->layout == RDYN_LAYOUT_ELEMENT_MAJOR;
+  sa.integrator = d->integrator;
+  sa.dt = d->dt;
+  const int stages = d->integrator == RDYN_INTEGRATOR_RK4 ? 4 : 1;
+  for (int t = 0; t < d->n_steps; ++t)
+  {
+    const double* const tau_t = d->tau + (int64_t)t * d->tau_step_stride;
+    const bool due = every > 0 && (t + 1) % every == 0;
+    const int64_t rec = due ? ((t + 1) / every - 1) * d->traj_step_stride : 0;
+    for (int stage = 0; stage < stages; ++stage)
+    {
+      st = fwd_dyn_chunks(c, stage ? sq : q, stage ? sv : dq, tau_t, ddq, st_stage, N, in_ss, in_sj, chunk, (double*)workspace, stream);
+      if (st != RDYN_OK) return st;
+      const bool last = stage == stages - 1;
+      sa.stage = stage;
+      sa.q_rec = (last && due && d->q_traj) ? d->q_traj + rec : nullptr;
+      sa.dq_rec = (last && due && d->dq_traj) ? d->dq_traj + rec : nullptr;
+      RDYN_HIP_TRY(rdyn_launch_rollout_stage(sa, stream));
+    }
+  }
+  memset(&ca, 0, sizeof ca);
+  ca.q_src = q;
+  ca.dq_src = dq;
+  ca.q_dst = d->q_end;
+  ca.dq_dst = d->dq_end;
+  ca.st_src = st_run;
+  ca.st_dst = d->status;
+  ca.count = count;
+  ca.n_samples = N;
+  RDYN_HIP_TRY(rdyn_launch_rollout_copy(ca, stream));
   return RDYN_OK;
 }
 

@@ -213,6 +213,49 @@ struct RdynFwdSolveArgs
 };
 hipError_t rdyn_launch_forward_solve(const RdynFwdSolveArgs& a, hipStream_t st);
 
+// rollouts (rdyn_rollout.hip): T integrator steps of the forward dynamics from (q, dq) under the torques tau + t * tau_step (addressed like q)
+struct RdynRolloutArgs
+{
+  const RdynChainConst* chain;
+  const double *q, *dq, *tau;
+  int64_t tau_step;           // doubles between the torques of consecutive steps (0: the same at every step)
+  double *q_end, *dq_end;     // may be null; may alias q / dq
+  double *q_traj, *dq_traj;   // may be null: record k = the state after step (k + 1) traj_every at + k * traj_step
+  int64_t traj_step;
+  int32_t* status;            // may be null: 1, or -1 from the first evaluation on that failed the pivot rule (the state is NaN from that step on)
+  int64_t n_samples, in_ss, in_sj;
+  double dt;
+  int n_steps, traj_every, integrator, n_active;
+  int staged;  // sample-major records through the wave's LDS tile in whole lines (natural strides, line-aligned): bit 0 the end state, bit 1 the trajectory
+};
+hipError_t rdyn_launch_rollout(int n_joints, const RdynRolloutArgs& a, hipStream_t st);
+// ... of a chain with more input joints than the unrolled kernels sweep: the element-wise update after one forward-dynamics pass (stage
+// `stage` of the step; Euler has one).  Every array holds count = n * n_samples doubles in the batch's layout.
+struct RdynRolloutStageArgs
+{
+  double *q, *dq;             // the step's state: advanced at the last stage
+  double *sq, *sv;            // RK4: the state the next stage is evaluated at
+  double *aq, *av;            // RK4: the weighted sums of the slopes
+  const double* ddq;          // what the pass returned
+  const int32_t* st_stage;    // ... and its per-sample status
+  int32_t* st_run;            // running minimum; a sample below 0 gets NaN state at the last stage
+  double *q_rec, *dq_rec;     // last stage, may be null: the trajectory record that is due
+  int64_t count, n_samples;
+  int n, element_major, integrator, stage;
+  double dt;
+};
+hipError_t rdyn_launch_rollout_stage(const RdynRolloutStageArgs& a, hipStream_t st);
+// count doubles q_src -> q_dst, dq_src -> dq_dst (a null destination is skipped); n_samples status words st_src -> st_dst (null source: 1)
+struct RdynRolloutCopyArgs
+{
+  const double *q_src, *dq_src;
+  double *q_dst, *dq_dst;
+  const int32_t* st_src;
+  int32_t* st_dst;
+  int64_t count, n_samples;
+};
+hipError_t rdyn_launch_rollout_copy(const RdynRolloutCopyArgs& a, hipStream_t st);
+
 // derivatives of the joint torque (rdyn_torque_deriv.hip): dtau/dq, dtau/dDq, M = dtau/dDDq; every output n x n per sample, element
 // e = i + n k of sample s at X[s * m_ss + e * m_se]; any output may be null (not all three)
 struct RdynTorqueDerivArgs

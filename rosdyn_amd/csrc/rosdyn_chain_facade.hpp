@@ -819,6 +819,15 @@ public:
   {
     chk(rdyn_forward_dynamics(m_h, &b, tau, ddq, status, chunk_samples, workspace, workspace_bytes));
   }
+  // rollout of a batch (b.q, b.dq = the initial state; every pointer of desc a device pointer in the layout of b.q): rdyn_rollout
+  size_t rolloutWorkspaceBytes(const rdyn_rollout_desc& desc, int64_t n_samples, int64_t chunk_samples = 0) const
+  {
+    return rdyn_rollout_workspace_bytes(m_h, &desc, n_samples, chunk_samples);
+  }
+  void rolloutBatch(const rdyn_batch& b, const rdyn_rollout_desc& desc, int64_t chunk_samples, void* workspace, size_t workspace_bytes) const
+  {
+    chk(rdyn_rollout(m_h, &b, &desc, chunk_samples, workspace, workspace_bytes));
+  }
   // derivatives of the joint torque of a batch (b.q, b.dq, b.ddq; every output n x n per sample, any may be null): rdyn_joint_torque_derivatives
   void getJointTorqueDerivativesBatch(const rdyn_batch& b, double* dtau_dq, double* dtau_dDq, double* M = nullptr) const
   {
