@@ -21,6 +21,9 @@ DT = 1e-3
 # evaluation of the multi-step test: the last column of MULTI_STEP; the wrists of the UR10 models and the last links of mixed_joints are light)
 TAU_SCALE = {"planar_2r": 2.0, "ur10_like": 0.4, "panda_like": 3.0, "mixed_joints": 0.1, "ur10_public_long": 3.0, "rev10": 5.0,
              "rev14": 5.0, "gen20_permuted": 5.0}
+# k_rollout<NJ, .> of the joint counts CHAINS leaves out (one step and the split horizon only: MULTI_STEP has no row for them)
+REV_EXTRA = ["rev1", "rev3", "rev4", "rev5", "rev8", "rev9"]
+TAU_SCALE.update({name: 5.0 for name in REV_EXTRA})
 
 
 def _inputs(name, n, N, T, seed=4100):
@@ -93,7 +96,7 @@ def _lib_fd(torch, chain):
     return fd
 
 
-@pytest.mark.parametrize("name", CHAINS)
+@pytest.mark.parametrize("name", CHAINS + REV_EXTRA)
 @pytest.mark.parametrize("integrator", INTEGRATORS)
 def test_one_step_against_the_library_own_forward_dynamics(name, integrator):
     """Euler: |dq1 - dq0 - dt ddq_lib| <= dt 64 eps cond2(M) max(1, |ddq_lib|) + 4 eps (|dq0| + dt |ddq_lib|) (the solver bound of
@@ -136,8 +139,9 @@ def test_one_step_against_the_library_own_forward_dynamics(name, integrator):
 
 
 # ---- 2. one Euler step against the oracle, residual form
-def _euler_residual_check(torch, chain, ref, name, N, layout, seed):
-    q0, dq0, tau = _inputs(name, ref.n, N, 1, seed=seed)
+def _euler_residual_check(torch, chain, ref, name, N, layout, seed, inputs=None):
+    """inputs: None (this module's inputs for the chain `name`), or (q0, dq0, tau) with tau of shape (1, N, n) and `name` a label"""
+    q0, dq0, tau = inputs if inputs is not None else _inputs(name, ref.n, N, 1, seed=seed)
     q1, dq1, st = _rollout(torch, chain, q0, dq0, tau, DT, "semi_implicit_euler", layout)
     assert (st == 1).all(), np.unique(st)
     ddq = (dq1 - dq0) / DT
@@ -162,7 +166,7 @@ def test_one_euler_step_against_the_oracle_in_residual_form(name, layout):
 
 
 # ---- 3. the horizon can be split anywhere, bitwise
-@pytest.mark.parametrize("name", ["ur10_like", "mixed_joints", "ur10_public_long", "rev10", "rev14", "gen20_permuted"])
+@pytest.mark.parametrize("name", ["ur10_like", "mixed_joints", "ur10_public_long", "rev10", "rev14", "gen20_permuted"] + REV_EXTRA)
 @pytest.mark.parametrize("integrator", INTEGRATORS)
 def test_the_horizon_can_be_split_anywhere_bitwise(name, integrator):
     torch = pytest.importorskip("torch")
