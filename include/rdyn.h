@@ -286,8 +286,9 @@ int rdyn_forward_dynamics(const rdyn_chain* chain, const rdyn_batch* batch, cons
  * status (device int32 per sample, may be NULL): 1 if every evaluation of the sample solved, -1 if one did not by the pivot rule of
  * rdyn_forward_dynamics.  From the failing step on every state of that sample -- the end state and all later trajectory records -- is
  * quiet NaN; the failure is sticky and no sample affects another.
- * Friction and spring components and external wrenches are NOT parameters of this call: they depend on the state, so unlike in
- * rdyn_forward_dynamics a caller cannot fold them into tau across steps (left for a follow-up).  No joint limits, no adaptive steps.
+ * Friction and spring components depend on the state, so unlike in rdyn_forward_dynamics a caller cannot fold them into tau across
+ * steps: rdyn_rollout_components (below, behind the component types) takes them.  External wrenches are NOT parameters of either call
+ * (left for a follow-up).  No joint limits, no adaptive steps.
  * Chains swept in registers (at most RDYN_MAX_SWEPT_JOINTS input joints; longer chains through their rigid-body reduction): ONE kernel
  * launch for the whole horizon, the state in registers between the steps; a step reads n torques per sample and writes only the
  * trajectory record that is due; the workspace query returns 0 and workspace may be NULL.  More input joints (up to RDYN_MAX_JOINTS, any
@@ -424,6 +425,35 @@ int rdyn_components_columns(const rdyn_component* comps, int n_comps);
  * tau_add (optional, layout of batch->q): += component torques.  C or tau_add may be NULL.  At most 30 components. */
 int rdyn_components_regressor(const rdyn_component* comps, int n_comps, int n_active, const rdyn_batch* batch, double* C,
                               const rdyn_regressor_layout* c_layout, double* tau_add);
+
+/* Forward dynamics and rollouts with components: the model rdyn_identification_gram / rdyn_identification_tsqr identify, simulated.
+ * Let tau_c(q, Dq) be the component torque of the list: for active joint j the sum, over the components whose `joint` is j in list
+ * order, of row . parameters -- exactly what rdyn_components_regressor accumulates into a zero-initialised tau_add (the same
+ * saturations, the same min_velocity / max_velocity constants, the same fma order).  Then
+ *     FD_c(q, Dq, tau) = FD(q, Dq, tau - tau_c(q, Dq))
+ * with FD the function of rdyn_forward_dynamics for the chain AS CONFIGURED (input-joint selection and order, locked joints, the
+ * reduced companion of a long chain with at most RDYN_MAX_SWEPT_JOINTS input joints, the chunked route with more).  component.joint
+ * indexes the active joints in INPUT order, whatever order the chain's joints are swept in.
+ *   rdyn_forward_dynamics_components   ddq = FD_c(q, Dq, tau); every other argument, the status, the aliasing rule (ddq may alias tau)
+ *                                      and the workspace are those of rdyn_forward_dynamics.
+ *   rdyn_rollout_components            integrates x' = (Dq, FD_c(q, Dq, tau_t)); tau_c is evaluated at EVERY integrator stage at that
+ *                                      stage's own state: RK4 at (stage state, stage velocity), semi-implicit Euler at (q_t, Dq_t).
+ *                                      Everything else is rdyn_rollout's: the descriptor, status and sticky NaN, aliasing, trajectory
+ *                                      records, the bitwise split of the horizon, independence from the chunk size.
+ * n_comps = 0 is allowed (comps may then be NULL) and IS rdyn_forward_dynamics / rdyn_rollout: the same kernels, the same bits.
+ * n_comps > 0: a NULL list, more than 30 components, an unknown type or a joint outside [0, n_active) are RDYN_ERR_INVALID_ARGUMENT
+ * before any device work, as are all argument errors of the two base calls.  The workspace queries of the base calls answer for these
+ * calls too (no extra workspace).  Chains swept in registers: still ONE launch, the list in the kernel arguments; more input joints: the
+ * solve kernel of the chunked route reads the sample's q and Dq where it reads tau.  No allocation, no synchronisation, capturable into
+ * a graph as the base calls are.
+ * Chatter: the friction "sign" is linear inside +-min_velocity with slope coulomb / min_velocity -- continuous and bounded, but stiff.
+ * When dt * coulomb / (min_velocity * M_jj) is not small, an explicit integrator chatters inside that band; the amplitude stays
+ * bounded by dt * coulomb / M_jj.  There is no implicit integrator. */
+int rdyn_forward_dynamics_components(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_component* comps, int n_comps,
+                                     const double* tau, double* ddq, int32_t* status, int64_t chunk_samples, void* workspace,
+                                     size_t workspace_bytes);
+int rdyn_rollout_components(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_rollout_desc* desc, const rdyn_component* comps,
+                            int n_comps, int64_t chunk_samples, void* workspace, size_t workspace_bytes);
 
 /* ---- mixed-chain batch (BASELINE.json configs[4]: 256 distinct 6-7-DOF chains x 4 096 samples) --------------
  * One launch per group of chains with equal joint count (and output-layout kind) evaluates rdyn_regressor for MANY

@@ -102,6 +102,8 @@ SYMBOLS = {
     "rdyn_forward_dynamics": (_I, [_VP, _BP, _VP, _VP, _VP, C.c_int64, _VP, C.c_size_t]),
     "rdyn_rollout_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(RolloutDesc), C.c_int64, C.c_int64]),
     "rdyn_rollout": (_I, [_VP, _BP, C.POINTER(RolloutDesc), C.c_int64, _VP, C.c_size_t]),
+    "rdyn_forward_dynamics_components": (_I, [_VP, _BP, _VP, _I, _VP, _VP, _VP, C.c_int64, _VP, C.c_size_t]),
+    "rdyn_rollout_components": (_I, [_VP, _BP, C.POINTER(RolloutDesc), _VP, _I, C.c_int64, _VP, C.c_size_t]),
     "rdyn_joint_torque_derivatives": (_I, [_VP, _BP, _VP, _VP, _VP]),
     "rdyn_local_ik": (_I, [_VP, _BP, _VP, _DP, C.c_double, _I, _VP, _VP, _VP]),
     "rdyn_local_ik_damped": (_I, [_VP, _BP, _VP, _DP, C.c_double, C.c_double, _I, _VP, _VP, _VP]),

@@ -356,10 +356,17 @@ class Chain(object):
         check(lib().rdyn_joint_inertia(self._h, C.byref(b), M.data_ptr()))
         return M
 
-    def getJointAcceleration(self, q, Dq, tau, layout="sample", out=None, chunk_samples=0, workspace=None):
+    def _component_list(self, components):
+        """(pointer, count) of a ComponentSet for the calls that take a component list"""
+        assert components.n_active == self.getActiveJointsNumber(), "the ComponentSet was made for another number of active joints"
+        return C.cast(components._arr, C.c_void_p), components.n_comps
+
+    def getJointAcceleration(self, q, Dq, tau, layout="sample", out=None, chunk_samples=0, workspace=None, components=None):
         """Forward dynamics (include/rdyn.h: rdyn_forward_dynamics; no reference counterpart): DDq solves
         getJointInertia(q) DDq = tau - getJointTorqueNonLinearPart(q, Dq) per sample.  Returns (DDq, status): status (N,) int32, 1 solved,
-        -1 the inertia matrix is not positive definite (that sample's DDq is NaN).  out may be tau itself."""
+        -1 the inertia matrix is not positive definite (that sample's DDq is NaN).  out may be tau itself.
+        components: None, or a ComponentSet (friction, springs) whose torque at (q, Dq) is subtracted from tau first
+        (rdyn_forward_dynamics_components)."""
         torch = _torch()
         b, N, lay = self._batch(layout, q, Dq, tau)
         b.ddq = None
@@ -368,20 +375,26 @@ class Chain(object):
         nbytes = lib().rdyn_forward_dynamics_workspace_bytes(self._h, chunk_samples)
         if workspace is None and nbytes > 0:
             workspace = torch.empty((nbytes,), dtype=torch.uint8, device=q.device)
-        check(lib().rdyn_forward_dynamics(self._h, C.byref(b), tau.data_ptr(), DDq.data_ptr(), status.data_ptr(), chunk_samples,
-                                          workspace.data_ptr() if workspace is not None else None,
-                                          workspace.numel() if workspace is not None else 0))
+        ws = (workspace.data_ptr() if workspace is not None else None, workspace.numel() if workspace is not None else 0)
+        if components is None:
+            check(lib().rdyn_forward_dynamics(self._h, C.byref(b), tau.data_ptr(), DDq.data_ptr(), status.data_ptr(), chunk_samples, *ws))
+        else:
+            comps, n_comps = self._component_list(components)
+            check(lib().rdyn_forward_dynamics_components(self._h, C.byref(b), comps, n_comps, tau.data_ptr(), DDq.data_ptr(),
+                                                         status.data_ptr(), chunk_samples, *ws))
         return DDq, status
 
     def rollout(self, q0, Dq0, tau, dt, integrator="rk4", n_steps=None, layout="sample", trajectory_every=0, out=None, chunk_samples=0,
-                workspace=None):
+                workspace=None, components=None):
         """Rollout (include/rdyn.h: rdyn_rollout; no reference counterpart): n_steps integrator steps of size dt of the forward dynamics
         from (q0, Dq0), the torques held over each step.  integrator: "rk4" or "semi_implicit_euler" ("euler").
         tau: (T, N, n) for layout="sample", (T, n, N) for "element" -- n_steps defaults to T and may be smaller; or (N, n) / (n, N) with an
         explicit n_steps: the same torques at every step.
         Returns (q_end, Dq_end, status), and with trajectory_every = k >= 1 also (q_traj, Dq_traj): n_steps // k records, record r = the
         state after step (r + 1) k, shaped (records,) + q0.shape.  status (N,) int32: 1, or -1 from the step on at which the inertia
-        matrix was not positive definite (NaN state from then on).  out: None or (q_end, Dq_end) tensors; they may be q0 and Dq0."""
+        matrix was not positive definite (NaN state from then on).  out: None or (q_end, Dq_end) tensors; they may be q0 and Dq0.
+        components: None, or a ComponentSet (friction, springs) whose torque is subtracted from tau at every integrator stage, at the
+        stage's own state (rdyn_rollout_components)."""
         torch = _torch()
         b, N, lay = self._batch(layout, q0, Dq0)
         if integrator not in _lib.INTEGRATORS:
@@ -416,8 +429,12 @@ class Chain(object):
         nbytes = lib().rdyn_rollout_workspace_bytes(self._h, C.byref(d), N, chunk_samples)
         if workspace is None and nbytes > 0:
             workspace = torch.empty((nbytes,), dtype=torch.uint8, device=q0.device)
-        check(lib().rdyn_rollout(self._h, C.byref(b), C.byref(d), chunk_samples, workspace.data_ptr() if workspace is not None else None,
-                                 workspace.numel() if workspace is not None else 0))
+        ws = (workspace.data_ptr() if workspace is not None else None, workspace.numel() if workspace is not None else 0)
+        if components is None:
+            check(lib().rdyn_rollout(self._h, C.byref(b), C.byref(d), chunk_samples, *ws))
+        else:
+            comps, n_comps = self._component_list(components)
+            check(lib().rdyn_rollout_components(self._h, C.byref(b), C.byref(d), comps, n_comps, chunk_samples, *ws))
         if trajectory_every:
             return q_end, dq_end, status, q_traj, dq_traj
         return q_end, dq_end, status

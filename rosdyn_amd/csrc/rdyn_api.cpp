@@ -551,8 +551,10 @@ static int64_t fwd_dyn_chunk(const rdyn_chain* c, int64_t chunk_samples)
 }
 
 // one pass of the chunked route over n_samples samples: per chunk the image [M | h] (k_long_inertia, the wrench recursion), then k_fwd_solve
+// (comps: null = the plain solve kernel; otherwise its variant, which subtracts tau_c at the sample's (q, dq) from tau)
 static int fwd_dyn_chunks(const rdyn_chain* c, const double* q, const double* dq, const double* tau, double* ddq, int32_t* status,
-                          int64_t n_samples, int64_t in_ss, int64_t in_sj, int64_t chunk, double* image, hipStream_t stream)
+                          int64_t n_samples, int64_t in_ss, int64_t in_sj, int64_t chunk, double* image, hipStream_t stream,
+                          const RdynComponentTable* comps)
 {
   const int n = c->n_active();
   RdynLongLocalArgs ia;
@@ -594,8 +596,37 @@ static int fwd_dyn_chunks(const rdyn_chain* c, const double* q, const double* dq
     sa.n_samples = cnt;
     sa.in_ss = in_ss;
     sa.in_sj = in_sj;
-    RDYN_HIP_TRY(rdyn_launch_forward_solve(sa, stream));
+    if (!comps)
+    {
+      RDYN_HIP_TRY(rdyn_launch_forward_solve(sa, stream));
+      continue;
+    }
+    RdynFwdSolveCompArgs sc;
+    sc.s = sa;
+    sc.q = ia.q;
+    sc.dq = ha.dq;
+    sc.t = *comps;
+    RDYN_HIP_TRY(rdyn_launch_forward_solve_components(sc, stream));
   }
+  return RDYN_OK;
+}
+
+// the component list of rdyn_forward_dynamics_components / rdyn_rollout_components, validated and sanitised (fill_components)
+static int fill_components(const rdyn_component* comps, int n_comps, int n_active, RdynComponentArgs* a);
+static int fill_component_table(const rdyn_component* comps, int n_comps, int n_active, const char* who, RdynComponentTable* t)
+{
+  memset(t, 0, sizeof *t);
+  if (n_comps < 0 || n_comps > RDYN_MAX_COMPONENTS || (n_comps > 0 && !comps))
+  {
+    rdyn_set_error("%s: 0..%d components, a list when there are any", who, RDYN_MAX_COMPONENTS);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  RdynComponentArgs a;
+  memset(&a, 0, sizeof a);
+  const int st = fill_components(comps, n_comps, n_active, &a);
+  if (st != RDYN_OK) return st;
+  t->n_comps = n_comps;
+  for (int i = 0; i < n_comps; ++i) t->comps[i] = a.comps[i];
   return RDYN_OK;
 }
 
@@ -606,27 +637,31 @@ size_t rdyn_forward_dynamics_workspace_bytes(const rdyn_chain* c, int64_t chunk_
   return ((size_t)fwd_dyn_chunk(c, chunk_samples) * (n * n + n) * sizeof(double) + 255) & ~(size_t)255;
 }
 
-int rdyn_forward_dynamics(const rdyn_chain* c, const rdyn_batch* b, const double* tau, double* ddq, int32_t* status, int64_t chunk_samples,
-                          void* workspace, size_t workspace_bytes)
+// who = the entry point (error texts); comps with n_comps = 0 is the plain call: the same kernels
+static int forward_dynamics(const rdyn_chain* c, const rdyn_batch* b, const rdyn_component* comps, int n_comps, const double* tau, double* ddq,
+                            int32_t* status, int64_t chunk_samples, void* workspace, size_t workspace_bytes, const char* who)
 {
-  int st = check_batch(c, b, true, false, "rdyn_forward_dynamics", LONG_KERNELS);
+  int st = check_batch(c, b, true, false, who, LONG_KERNELS);
   if (st != RDYN_OK) return st;
   if (b->n_samples > 0 && (!tau || !ddq))
   {
-    rdyn_set_error("rdyn_forward_dynamics: null torque or acceleration pointer");
+    rdyn_set_error("%s: null torque or acceleration pointer", who);
     return RDYN_ERR_INVALID_ARGUMENT;
   }
   if (chunk_samples < 0)
   {
-    rdyn_set_error("rdyn_forward_dynamics: negative chunk_samples");
+    rdyn_set_error("%s: negative chunk_samples", who);
     return RDYN_ERR_INVALID_ARGUMENT;
   }
   const size_t need = rdyn_forward_dynamics_workspace_bytes(c, chunk_samples);
   if (b->n_samples > 0 && need > 0 && (!workspace || workspace_bytes < need))
   {
-    rdyn_set_error("rdyn_forward_dynamics: workspace too small (%zu < %zu bytes)", workspace ? workspace_bytes : (size_t)0, need);
+    rdyn_set_error("%s: workspace too small (%zu < %zu bytes)", who, workspace ? workspace_bytes : (size_t)0, need);
     return RDYN_ERR_INVALID_ARGUMENT;
   }
+  RdynComponentTable table;
+  st = fill_component_table(comps, n_comps, c->n_active(), who, &table);
+  if (st != RDYN_OK) return st;
   if (b->n_samples == 0 || c->n_active() < 1) return RDYN_OK;
   DeviceGuard g;
   st = g.enter(b->device);
@@ -651,10 +686,31 @@ int rdyn_forward_dynamics(const rdyn_chain* c, const rdyn_batch* b, const double
     a.in_ss = in_ss;
     a.in_sj = in_sj;
     a.staged = (b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(ddq) && !probe_env("RDYN_NO_RECORD_STAGING")) ? n : 0;
-    RDYN_HIP_TRY(rdyn_launch_forward_dynamics(sw->n_joints(), a, stream));
+    if (n_comps == 0)
+    {
+      RDYN_HIP_TRY(rdyn_launch_forward_dynamics(sw->n_joints(), a, stream));
+      return RDYN_OK;
+    }
+    RdynFwdDynCompArgs ac;
+    ac.f = a;
+    ac.t = table;
+    RDYN_HIP_TRY(rdyn_launch_forward_dynamics_components(sw->n_joints(), ac, stream));
     return RDYN_OK;
   }
-  return fwd_dyn_chunks(c, b->q, b->dq, tau, ddq, status, b->n_samples, in_ss, in_sj, fwd_dyn_chunk(c, chunk_samples), (double*)workspace, stream);
+  return fwd_dyn_chunks(c, b->q, b->dq, tau, ddq, status, b->n_samples, in_ss, in_sj, fwd_dyn_chunk(c, chunk_samples), (double*)workspace, stream,
+                        n_comps ? &table : nullptr);
+}
+
+int rdyn_forward_dynamics(const rdyn_chain* c, const rdyn_batch* b, const double* tau, double* ddq, int32_t* status, int64_t chunk_samples,
+                          void* workspace, size_t workspace_bytes)
+{
+  return forward_dynamics(c, b, nullptr, 0, tau, ddq, status, chunk_samples, workspace, workspace_bytes, "rdyn_forward_dynamics");
+}
+
+int rdyn_forward_dynamics_components(const rdyn_chain* c, const rdyn_batch* b, const rdyn_component* comps, int n_comps, const double* tau,
+                                     double* ddq, int32_t* status, int64_t chunk_samples, void* workspace, size_t workspace_bytes)
+{
+  return forward_dynamics(c, b, comps, n_comps, tau, ddq, status, chunk_samples, workspace, workspace_bytes, "rdyn_forward_dynamics_components");
 }
 
 // ---- rollouts: T integrator steps of the forward dynamics (rdyn_rollout.hip) ------------------------------------
@@ -672,14 +728,15 @@ size_t rdyn_rollout_workspace_bytes(const rdyn_chain* c, const rdyn_rollout_desc
          2 * align256((size_t)n_samples * sizeof(int32_t));
 }
 
-int rdyn_rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_desc* d, int64_t chunk_samples, void* workspace,
-                 size_t workspace_bytes)
+// who = the entry point (error texts); comps with n_comps = 0 is the plain call: the same kernels
+static int rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_desc* d, const rdyn_component* comps, int n_comps,
+                   int64_t chunk_samples, void* workspace, size_t workspace_bytes, const char* who)
 {
-  int st = check_batch(c, b, true, false, "rdyn_rollout", LONG_KERNELS);
+  int st = check_batch(c, b, true, false, who, LONG_KERNELS);
   if (st != RDYN_OK) return st;
   if (!d)
   {
-    rdyn_set_error("rdyn_rollout: null descriptor");
+    rdyn_set_error("%s: null descriptor", who);
     return RDYN_ERR_INVALID_ARGUMENT;
   }
   const int n = c->n_active();
@@ -687,36 +744,39 @@ int rdyn_rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_de
   if (d->n_steps < 0 || !std::isfinite(d->dt) || d->dt == 0.0 ||
       (d->integrator != RDYN_INTEGRATOR_SEMI_IMPLICIT_EULER && d->integrator != RDYN_INTEGRATOR_RK4))
   {
-    rdyn_set_error("rdyn_rollout: negative n_steps, a step size that is zero or not finite, or an unknown integrator");
+    rdyn_set_error("%s: negative n_steps, a step size that is zero or not finite, or an unknown integrator", who);
     return RDYN_ERR_INVALID_ARGUMENT;
   }
   if (d->n_steps > 0 && !d->tau)
   {
-    rdyn_set_error("rdyn_rollout: null torque pointer");
+    rdyn_set_error("%s: null torque pointer", who);
     return RDYN_ERR_INVALID_ARGUMENT;
   }
   const bool traj = d->q_traj || d->dq_traj;
   if (N > 0 && !d->q_end && !d->dq_end && !traj)
   {
-    rdyn_set_error("rdyn_rollout: every output is null");
+    rdyn_set_error("%s: every output is null", who);
     return RDYN_ERR_INVALID_ARGUMENT;
   }
   if (traj && (d->traj_every < 1 || d->traj_step_stride < (int64_t)n * N))
   {
-    rdyn_set_error("rdyn_rollout: a trajectory needs traj_every >= 1 and traj_step_stride >= n * n_samples");
+    rdyn_set_error("%s: a trajectory needs traj_every >= 1 and traj_step_stride >= n * n_samples", who);
     return RDYN_ERR_INVALID_ARGUMENT;
   }
   if (chunk_samples < 0)
   {
-    rdyn_set_error("rdyn_rollout: negative chunk_samples");
+    rdyn_set_error("%s: negative chunk_samples", who);
     return RDYN_ERR_INVALID_ARGUMENT;
   }
   const size_t need = rdyn_rollout_workspace_bytes(c, d, N, chunk_samples);
   if (N > 0 && need > 0 && (!workspace || workspace_bytes < need))
   {
-    rdyn_set_error("rdyn_rollout: workspace too small (%zu < %zu bytes)", workspace ? workspace_bytes : (size_t)0, need);
+    rdyn_set_error("%s: workspace too small (%zu < %zu bytes)", who, workspace ? workspace_bytes : (size_t)0, need);
     return RDYN_ERR_INVALID_ARGUMENT;
   }
+  RdynComponentTable table;
+  st = fill_component_table(comps, n_comps, n, who, &table);
+  if (st != RDYN_OK) return st;
   if (N == 0 || n < 1) return RDYN_OK;
   DeviceGuard g;
   st = g.enter(b->device);
@@ -756,7 +816,15 @@ int rdyn_rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_de
       if ((d->q_end || d->dq_end) && lines_aligned(d->q_end, d->dq_end)) a.staged |= 1;
       if (traj && lines_aligned(d->q_traj, d->dq_traj) && (d->traj_step_stride * (int64_t)sizeof(double)) % 128 == 0) a.staged |= 2;
     }
-    RDYN_HIP_TRY(rdyn_launch_rollout(sw->n_joints(), a, stream));
+    if (n_comps == 0)
+    {
+      RDYN_HIP_TRY(rdyn_launch_rollout(sw->n_joints(), a, stream));
+      return RDYN_OK;
+    }
+    RdynRolloutCompArgs ac;
+    ac.r = a;
+    ac.t = table;
+    RDYN_HIP_TRY(rdyn_launch_rollout_components(sw->n_joints(), ac, stream));
     return RDYN_OK;
   }
   const int64_t chunk = fwd_dyn_chunk(c, chunk_samples);
@@ -803,7 +871,8 @@ int rdyn_rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_de
     const int64_t rec = due ? ((t + 1) / every - 1) * d->traj_step_stride : 0;
     for (int stage = 0; stage < stages; ++stage)
     {
-      st = fwd_dyn_chunks(c, stage ? sq : q, stage ? sv : dq, tau_t, ddq, st_stage, N, in_ss, in_sj, chunk, (double*)workspace, stream);
+      st = fwd_dyn_chunks(c, stage ? sq : q, stage ? sv : dq, tau_t, ddq, st_stage, N, in_ss, in_sj, chunk, (double*)workspace, stream,
+                          n_comps ? &table : nullptr);  // components see the stage state
       if (st != RDYN_OK) return st;
       const bool last = stage == stages - 1;
       sa.stage = stage;
@@ -823,6 +892,18 @@ int rdyn_rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_de
   ca.n_samples = N;
   RDYN_HIP_TRY(rdyn_launch_rollout_copy(ca, stream));
   return RDYN_OK;
+}
+
+int rdyn_rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_desc* d, int64_t chunk_samples, void* workspace,
+                 size_t workspace_bytes)
+{
+  return rollout(c, b, d, nullptr, 0, chunk_samples, workspace, workspace_bytes, "rdyn_rollout");
+}
+
+int rdyn_rollout_components(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_desc* d, const rdyn_component* comps, int n_comps,
+                            int64_t chunk_samples, void* workspace, size_t workspace_bytes)
+{
+  return rollout(c, b, d, comps, n_comps, chunk_samples, workspace, workspace_bytes, "rdyn_rollout_components");
 }
 
 // ---- derivatives of the joint torque: dtau/dq, dtau/dDq, M (rdyn_torque_deriv.hip) ------------------------------

@@ -11,6 +11,7 @@
 // behind it.  Pure streaming: 16 B read, n * K * 8 B written per sample.
 #include <hip/hip_runtime.h>
 #include "rdyn_kernels.h"
+#include "rdyn_component_row.h"
 
 namespace
 {
@@ -26,26 +27,8 @@ __global__ __launch_bounds__(256) void k_components(const RdynComponentArgs a)
   for (int i = 0; i < a.n_comps; ++i)
   {
     const RdynComponent& c = a.comps[i];
-    const int cols = (c.type == RDYN_COMP_FRICTION2) ? 3 : 2;
-    double row[3] = {0.0, 0.0, 0.0};
-    if (c.type == RDYN_COMP_SPRING)
-    {
-      row[0] = qp[c.joint * a.in_sj];
-      row[1] = 1.0;
-    }
-    else
-    {
-      const double v = dqp[c.joint * a.in_sj];
-      const double omega = fmin(fmax(v, -c.max_velocity), c.max_velocity);
-      double sg;
-      if (c.type == RDYN_COMP_FRICTION1)
-        sg = fmin(fmax(omega / c.min_velocity, -1.0), 1.0);
-      else
-        sg = (omega == 0.0) ? 0.0 : (omega > c.min_velocity ? 1.0 : (omega < -c.min_velocity ? -1.0 : omega / c.min_velocity));
-      row[0] = sg;
-      row[1] = omega;
-      row[2] = omega * omega * sg;
-    }
+    double row[3];
+    const int cols = component_row(c, c.type == RDYN_COMP_SPRING ? qp[c.joint * a.in_sj] : dqp[c.joint * a.in_sj], row);
     if (cp)
       for (int j = 0; j < a.n_active; ++j)  // dense image: zeros outside the component's own joint row
         for (int k = 0; k < cols; ++k) cp[j * a.c_sr + (int64_t)(k0 + k) * a.c_sc] = (j == c.joint) ? row[k] : 0.0;

@@ -28,60 +28,30 @@
 #include "rdyn_kernels.h"
 #include "rdyn_record_stage.h"
 #include "rdyn_fwd_dyn_body.h"
+#include "rdyn_component_row.h"
+#include <type_traits>
 
 namespace
 {
 template <int NJ>
 __global__ __launch_bounds__(64) void k_fwd_dyn(const RdynFwdDynArgs a)
 {
-  ChainPtr c = as_const(a.chain);
-  const int lane = threadIdx.x;
-  const int64_t s_wave = (int64_t)blockIdx.x * 64;
-  const int64_t s = s_wave + lane;
-  if (s >= a.n_samples) return;
-  const bool stg = a.staged && a.n_samples - s_wave >= 64;  // wave-uniform: a full wave's records leave in whole lines
-  const double* __restrict__ qp = a.q + s * a.in_ss;
-  const double* __restrict__ dqp = a.dq + s * a.in_ss;
-  const double* tp = a.tau + s * a.in_ss;  // (may alias ddq: every entry is read before the first store)
-
-  double rhs[NJ];
-#pragma unroll
-  for (int f = 0; f < NJ; ++f)
-  {
-    const int idx = c->j[f].in_idx;
-    rhs[f] = idx >= 0 ? tp[idx * a.in_sj] : 0.0;
-  }
-
-#define RDYN_FWD_Q(f, idx) qp[idx * a.in_sj]
-#define RDYN_FWD_DQ(f, idx) dqp[idx * a.in_sj]
-#include "rdyn_fwd_dyn_body.inc"
-#undef RDYN_FWD_Q
-#undef RDYN_FWD_DQ
-
-  if (a.status) a.status[s] = ok ? 1 : -1;
-  const double qnan = __builtin_nan("");
-  SmallRecords sm;
-  if (stg)
-  {
-    extern __shared__ __attribute__((aligned(16))) char fwd_stage_lds[];
-    sm.init(fwd_stage_lds, c->n_active, lane);
-  }
-  double* const op = a.ddq + s * a.in_ss;
-#pragma unroll
-  for (int f = 0; f < NJ; ++f)
-  {
-    const int idx = c->j[f].in_idx;
-    if (idx < 0) continue;
-    const double v = ok ? rhs[f] : qnan;
-    if (stg) sm.put(idx, v);
-    else op[idx * a.in_sj] = v;
-  }
-  if (stg) sm.copy_out(a.ddq + s_wave * a.in_ss, lane);
+#define RDYN_FWD_KERNEL_RHS(rhs)
+#include "rdyn_fwd_dyn_kernel.inc"
+#undef RDYN_FWD_KERNEL_RHS
 }
 
+__device__ __forceinline__ const RdynFwdSolveArgs& solve_args(const RdynFwdSolveArgs& a) { return a; }
+__device__ __forceinline__ const RdynFwdSolveArgs& solve_args(const RdynFwdSolveCompArgs& a) { return a.s; }
+
 // element (i, j) of the lane's M at image[(i n + j) ld], h_i at image[(n n + i) ld]; both triangles of M are present, the lower one is used
-__global__ __launch_bounds__(64) void k_fwd_solve(const RdynFwdSolveArgs a)
+// Args = RdynFwdSolveArgs: the torque is tau; RdynFwdSolveCompArgs: tau - tau_c at the sample's (q, dq), which the lane reads the way it
+// reads tau (rdyn_forward_dynamics_components, the stages of rdyn_rollout_components)
+template <class Args>
+__global__ __launch_bounds__(64) void k_fwd_solve(const Args aa)
 {
+  constexpr bool COMPS = std::is_same<Args, RdynFwdSolveCompArgs>::value;
+  const RdynFwdSolveArgs& a = solve_args(aa);
   extern __shared__ __attribute__((aligned(16))) double fwd_lds[];  // [2][n][64]: row j of L | the solution vector
   const int n = a.n;
   const int lane = threadIdx.x;
@@ -99,7 +69,9 @@ __global__ __launch_bounds__(64) void k_fwd_solve(const RdynFwdSolveArgs a)
   for (int i = 0; i < n; ++i)
   {
     trace += G[(int64_t)(i * n + i) * ld];
-    y[i * 64] = tp[i * a.in_sj] - G[(int64_t)(n * n + i) * ld];
+    double t = tp[i * a.in_sj];
+    if constexpr (COMPS) t -= joint_component_torque(aa.t, i, aa.q[sl * a.in_ss + i * a.in_sj], aa.dq[sl * a.in_ss + i * a.in_sj]);
+    y[i * 64] = t - G[(int64_t)(n * n + i) * ld];
   }
   const double floor = RDYN_FWD_PIVOT_FLOOR * trace;
   bool ok = true;
@@ -183,6 +155,15 @@ hipError_t rdyn_launch_forward_solve(const RdynFwdSolveArgs& a, hipStream_t st)
   if (a.n_samples <= 0) return hipSuccess;
   if (a.n < 1 || a.n > RDYN_MAX_JOINTS || a.ld < a.n_samples) return hipErrorInvalidValue;
   const size_t lds = (size_t)2 * a.n * 64 * sizeof(double);  // <= 32 KB
-  hipLaunchKernelGGL(k_fwd_solve, dim3((unsigned)((a.n_samples + 63) / 64)), dim3(64), lds, st, a);
+  hipLaunchKernelGGL(k_fwd_solve<RdynFwdSolveArgs>, dim3((unsigned)((a.n_samples + 63) / 64)), dim3(64), lds, st, a);
+  return hipGetLastError();
+}
+
+hipError_t rdyn_launch_forward_solve_components(const RdynFwdSolveCompArgs& a, hipStream_t st)
+{
+  if (a.s.n_samples <= 0) return hipSuccess;
+  if (a.s.n < 1 || a.s.n > RDYN_MAX_JOINTS || a.s.ld < a.s.n_samples || a.t.n_comps < 0 || a.t.n_comps > RDYN_MAX_COMPONENTS) return hipErrorInvalidValue;
+  const size_t lds = (size_t)2 * a.s.n * 64 * sizeof(double);  // <= 32 KB
+  hipLaunchKernelGGL(k_fwd_solve<RdynFwdSolveCompArgs>, dim3((unsigned)((a.s.n_samples + 63) / 64)), dim3(64), lds, st, a);
   return hipGetLastError();
 }

@@ -519,6 +519,34 @@ struct RdynComponentArgs
 };
 hipError_t rdyn_launch_components(const RdynComponentArgs& a, hipStream_t st);
 
+// forward dynamics and rollouts with components (rdyn_fwd_dyn_comp.hip, rdyn_rollout_comp.hip, k_fwd_solve's variant in rdyn_fwd_dyn.hip):
+// the evaluation's torque is tau - tau_c(q, dq), tau_c what k_components adds to a zero-initialised tau; the table travels in the
+// kernel arguments behind the arguments of the plain kernel (constants already sanitised by the API, comps[i].joint an input index)
+struct RdynComponentTable
+{
+  int n_comps;
+  RdynComponent comps[RDYN_MAX_COMPONENTS];
+};
+struct RdynFwdDynCompArgs
+{
+  RdynFwdDynArgs f;
+  RdynComponentTable t;
+};
+hipError_t rdyn_launch_forward_dynamics_components(int n_joints, const RdynFwdDynCompArgs& a, hipStream_t st);
+struct RdynFwdSolveCompArgs
+{
+  RdynFwdSolveArgs s;
+  const double *q, *dq;  // the chunk's first sample, addressed like tau
+  RdynComponentTable t;
+};
+hipError_t rdyn_launch_forward_solve_components(const RdynFwdSolveCompArgs& a, hipStream_t st);
+struct RdynRolloutCompArgs
+{
+  RdynRolloutArgs r;
+  RdynComponentTable t;
+};
+hipError_t rdyn_launch_rollout_components(int n_joints, const RdynRolloutCompArgs& a, hipStream_t st);
+
 // pieces of rdyn_identification_tsqr for the multi-device form (rdyn_api.cpp): widths of the swept / the chain's factor, the factor of
 // the swept chain alone, the expansion (+ accumulation) of a swept factor
 int rdyn_internal_tsqr_widths(const rdyn_chain* c, const rdyn_component* comps, int n_comps, int* n1s, int* n1, int* expands);

@@ -593,6 +593,19 @@ public:
   // positive definite (a fixed joint among the input joints, links without <inertial> at the end of the chain).
   VectorXd getJointAcceleration(const VectorXd& q, const VectorXd& Dq, const VectorXd& tau)
   {
+    return jointAcceleration(q, Dq, tau, nullptr);
+  }
+  // ... with friction and spring components (include/rdyn.h: rdyn_forward_dynamics_components): their torque at (q, Dq) is subtracted
+  // from tau first
+  VectorXd getJointAcceleration(const VectorXd& q, const VectorXd& Dq, const VectorXd& tau, const std::vector<rdyn_component>& comps)
+  {
+    return jointAcceleration(q, Dq, tau, &comps);
+  }
+
+private:
+  // comps == nullptr: rdyn_forward_dynamics, as before the components were added; otherwise rdyn_forward_dynamics_components
+  VectorXd jointAcceleration(const VectorXd& q, const VectorXd& Dq, const VectorXd& tau, const std::vector<rdyn_component>* comps)
+  {
     const size_t n = m_active_joints_number;
     stage(&q, &Dq, &tau);  // tau rides in the DDq slot of the staging buffer
     // device record after the inputs: DDq (n) | status (int32 in one double) | the one-sample chunk image of the chunked route
@@ -601,7 +614,9 @@ public:
     int32_t* const flag = reinterpret_cast<int32_t*>(out(n));
     const double* const d_tau = m_b.ddq;
     m_b.ddq = nullptr;
-    chk(rdyn_forward_dynamics(m_h, &m_b, d_tau, out(0), flag, 1, ws_bytes ? out(n + 1) : nullptr, ws_bytes));
+    void* const ws = ws_bytes ? out(n + 1) : nullptr;
+    if (!comps) chk(rdyn_forward_dynamics(m_h, &m_b, d_tau, out(0), flag, 1, ws, ws_bytes));
+    else chk(rdyn_forward_dynamics_components(m_h, &m_b, comps->data(), (int)comps->size(), d_tau, out(0), flag, 1, ws, ws_bytes));
     wait_done();
     int32_t st;
     std::memcpy(&st, hout(n), sizeof st);
@@ -611,6 +626,7 @@ public:
     return ddq;
   }
 
+public:
   // Derivatives of getJointTorque (no reference counterpart; include/rdyn.h: rdyn_joint_torque_derivatives):
   // dtau_dq(i, k) = d tau_i / d q_k, dtau_dDq(i, k) = d tau_i / d Dq_k for the chain as configured; d tau / d DDq is getJointInertia(q).
   void getJointTorqueDerivatives(const VectorXd& q, const VectorXd& Dq, const VectorXd& DDq, MatrixXd& dtau_dq, MatrixXd& dtau_dDq)
@@ -819,6 +835,12 @@ public:
   {
     chk(rdyn_forward_dynamics(m_h, &b, tau, ddq, status, chunk_samples, workspace, workspace_bytes));
   }
+  // ... with friction and spring components (rdyn_forward_dynamics_components; the same workspace query)
+  void getJointAccelerationBatch(const std::vector<rdyn_component>& comps, const rdyn_batch& b, const double* tau, double* ddq, int32_t* status,
+                                 int64_t chunk_samples, void* workspace, size_t workspace_bytes) const
+  {
+    chk(rdyn_forward_dynamics_components(m_h, &b, comps.data(), (int)comps.size(), tau, ddq, status, chunk_samples, workspace, workspace_bytes));
+  }
   // rollout of a batch (b.q, b.dq = the initial state; every pointer of desc a device pointer in the layout of b.q): rdyn_rollout
   size_t rolloutWorkspaceBytes(const rdyn_rollout_desc& desc, int64_t n_samples, int64_t chunk_samples = 0) const
   {
@@ -827,6 +849,12 @@ public:
   void rolloutBatch(const rdyn_batch& b, const rdyn_rollout_desc& desc, int64_t chunk_samples, void* workspace, size_t workspace_bytes) const
   {
     chk(rdyn_rollout(m_h, &b, &desc, chunk_samples, workspace, workspace_bytes));
+  }
+  // ... with friction and spring components, evaluated at every integrator stage (rdyn_rollout_components; the same workspace query)
+  void rolloutBatch(const std::vector<rdyn_component>& comps, const rdyn_batch& b, const rdyn_rollout_desc& desc, int64_t chunk_samples,
+                    void* workspace, size_t workspace_bytes) const
+  {
+    chk(rdyn_rollout_components(m_h, &b, &desc, comps.data(), (int)comps.size(), chunk_samples, workspace, workspace_bytes));
   }
   // derivatives of the joint torque of a batch (b.q, b.dq, b.ddq; every output n x n per sample, any may be null): rdyn_joint_torque_derivatives
   void getJointTorqueDerivativesBatch(const rdyn_batch& b, double* dtau_dq, double* dtau_dDq, double* M = nullptr) const
