@@ -29,7 +29,6 @@
 // its rounding is what gamma measures.  tools/cholqr_emulate.py replays the dense steps in numpy.
 // k_cholqr_expand: factor of the reduced chain -> factor of a chain with fixed joints; k_cholqr_fold: the accumulate step.
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <cstdint>
 #include <type_traits>
 #include "rdyn_device.h"
@@ -37,6 +36,7 @@
 #include "rdyn_kernels.h"
 #include "rdyn_gram_common.h"
 #include "rdyn_duo_common.h"
+#include "rdyn_launch_util.h"
 
 #ifndef RDYN_CHOLQR_AHEAD
 #define RDYN_CHOLQR_AHEAD 2  // rows of W operands requested ahead of their MFMAs when W is read from global memory (1 / 2 / 3: 6.47 / 6.33 / 6.36 ms at config 3)
@@ -1409,27 +1409,10 @@ __global__ __launch_bounds__(NTD) void k_cholqr_fold(const double* __restrict__ 
       if (e % n1 > e / n1) R[e] = 0.0;
 }
 
-template <class K>
-hipError_t opt_in_lds_once(K kernel, std::atomic<uint64_t>& done, int max_bytes = 160 * 1024)
-{
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(done.load(std::memory_order_acquire) & bit))
-  {
-    e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, max_bytes);
-    if (e != hipSuccess) return e;
-    done.fetch_or(bit, std::memory_order_release);
-  }
-  return hipSuccess;
-}
-
 template <int NJ, bool ALLREV, int NPAIR, bool WGLOBAL, int XB = 0, int KIN = 0>
 hipError_t launch_pgram3(const RdynLdsGramArgs& a, const double* W, const int* run_flag, int blocks, hipStream_t st)
 {
-  static std::atomic<uint64_t> attr{0};
-  hipError_t e = opt_in_lds_once(k_regressor_pgram<NJ, ALLREV, NPAIR, WGLOBAL, XB, KIN>, attr);
+  hipError_t e = opt_in_lds_once<k_regressor_pgram<NJ, ALLREV, NPAIR, WGLOBAL, XB, KIN>>();
   if (e != hipSuccess) return e;
   constexpr int NB = (10 * NJ + 1 + 15) / 16 + XB, NT = NB * (NB + 1) / 2;
   size_t lds = (WGLOBAL ? 0 : (size_t)NT * 2048) + (size_t)NPAIR * a.tile_bytes + (KIN ? RDYN_KIN_XCH_BYTES_XV(NJ <= 6 ? 21 : 12) : 0);
@@ -1488,8 +1471,7 @@ template <int NB>
 hipError_t launch_pgram_rows(const double* A, const double* b, int64_t rows, int64_t lda, int n_cols, const double* W, double* slabs, const int* run_flag,
                              int blocks, hipStream_t st)
 {
-  static std::atomic<uint64_t> attr{0};
-  hipError_t e = opt_in_lds_once(k_pgram_rows<NB>, attr);
+  hipError_t e = opt_in_lds_once<k_pgram_rows<NB>>();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL((k_pgram_rows<NB>), dim3(blocks), dim3(256), (size_t)(NB * (NB + 1) / 2) * 2048, st, A, b, rows, lda, n_cols, W, slabs, run_flag);
   return hipGetLastError();
@@ -1554,16 +1536,9 @@ hipError_t rdyn_launch_pgram_rows(const double* A, const double* b, int64_t rows
 
 hipError_t rdyn_launch_regressor_pgram(int n_joints, const RdynLdsGramArgs& a, const double* W, const int* run_flag, int blocks, int pairs, hipStream_t st)
 {
-  switch (n_joints)
-  {
-  case 2: return launch_pgram<2>(a, W, run_flag, blocks, pairs, st);
-  case 3: return launch_pgram<3>(a, W, run_flag, blocks, pairs, st);
-  case 4: return launch_pgram<4>(a, W, run_flag, blocks, pairs, st);
-  case 5: return launch_pgram<5>(a, W, run_flag, blocks, pairs, st);
-  case 6: return launch_pgram<6>(a, W, run_flag, blocks, pairs, st);
-  case 7: return launch_pgram<7>(a, W, run_flag, blocks, pairs, st);
-  default: return hipErrorInvalidValue;
-  }
+#define CALL(N) launch_pgram<N>(a, W, run_flag, blocks, pairs, st)
+  RDYN_DISPATCH_JOINTS_2_7(n_joints, CALL)
+#undef CALL
 }
 
 int rdyn_cholqr_max_cols() { return kMaxN1; }          // rdyn_tsqr on a materialised matrix (the squares of the dense steps in the workspace beyond 96)
@@ -1580,8 +1555,7 @@ hipError_t rdyn_launch_cholqr_precond(const double* R1, const double* Gs, const 
     hipLaunchKernelGGL(k_cholqr_precond<true>, dim3(1), dim3(NTD), 0, st, R1, Gs, cs, bbs, n1, col_shift, nb_w, row_scale, T, W, V, zmask, flags, round, run_flag, gamma_out, wide_sq);
     return hipGetLastError();
   }
-  static std::atomic<uint64_t> attr{0};
-  hipError_t e = opt_in_lds_once(k_cholqr_precond<false>, attr, 146 * 1024);
+  hipError_t e = opt_in_lds_once<k_cholqr_precond<false>>(146 * 1024);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_cholqr_precond<false>, dim3(1), dim3(NTD), ((size_t)2 * n1 * n1 + n1) * sizeof(double), st, R1, Gs, cs, bbs, n1, col_shift, nb_w, row_scale, T, W, V, zmask, flags, round, run_flag,
                      gamma_out, nullptr);
@@ -1598,8 +1572,7 @@ hipError_t rdyn_launch_cholqr_factor(const double* G, const double* c, const dou
     hipLaunchKernelGGL(k_cholqr_factor<true>, dim3(1), dim3(NTD), 0, st, G, c, bb, n1, has_b, T, V, zmask, R, flags, round, run_flag, rho_out, wide_sq);
     return hipGetLastError();
   }
-  static std::atomic<uint64_t> attr{0};
-  hipError_t e = opt_in_lds_once(k_cholqr_factor<false>, attr, 146 * 1024);
+  hipError_t e = opt_in_lds_once<k_cholqr_factor<false>>(146 * 1024);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_cholqr_factor<false>, dim3(1), dim3(NTD), (size_t)2 * n1 * n1 * sizeof(double), st, G, c, bb, n1, has_b, T, V, zmask, R, flags, round, run_flag, rho_out, nullptr);
   return hipGetLastError();
@@ -1611,8 +1584,7 @@ hipError_t rdyn_launch_cholqr_expand(const RdynGramExpandArgs& a, const double* 
   const int n1 = 10 * a.n_joints + a.n_comp_cols + 1, nr = 10 * a.n_red + a.n_comp_cols + 1;
   const size_t lds = ((size_t)n1 * nr + nr) * sizeof(double);
   if (lds > 156 * 1024) return hipErrorInvalidValue;
-  static std::atomic<uint64_t> attr{0};
-  hipError_t e = opt_in_lds_once(k_cholqr_expand<false>, attr, 156 * 1024);
+  hipError_t e = opt_in_lds_once<k_cholqr_expand<false>>(156 * 1024);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_cholqr_expand<false>, dim3(1), dim3(NTD), lds, st, a, R_red, R, nullptr);
   return hipGetLastError();
@@ -1631,15 +1603,13 @@ hipError_t rdyn_launch_cholqr_fold(const double* R_new, double* R, int n1, hipSt
   const size_t both = ((size_t)n1 * (n1 + 1) / 2 + b_doubles) * sizeof(double);
   if (n1 <= kMaxFoldN1 && both <= 156 * 1024)
   {
-    static std::atomic<uint64_t> attr{0};
-    hipError_t e = opt_in_lds_once(k_cholqr_fold<false>, attr, 156 * 1024);
+    hipError_t e = opt_in_lds_once<k_cholqr_fold<false>>(156 * 1024);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_cholqr_fold<false>, dim3(1), dim3(NTD), both, st, R_new, R, n1, rn, nullptr);
     return hipGetLastError();
   }
   if (b_doubles * sizeof(double) > 156 * 1024) return hipErrorInvalidValue;
-  static std::atomic<uint64_t> attr_g{0};
-  hipError_t e = opt_in_lds_once(k_cholqr_fold<true>, attr_g, 156 * 1024);
+  hipError_t e = opt_in_lds_once<k_cholqr_fold<true>>(156 * 1024);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_cholqr_fold<true>, dim3(1), dim3(NTD), b_doubles * sizeof(double), st, R_new, R, n1, rn, nullptr);
   return hipGetLastError();

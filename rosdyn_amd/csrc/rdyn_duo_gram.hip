@@ -19,13 +19,13 @@
 // Requirements (else rdyn_regressor_gram uses the single-wave kernels): 2 <= chain joints <= 7, input joints in chain order,
 // four tiles inside 160 KB of LDS.
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <cstdint>
 #include "rdyn_device.h"
 #include "rdyn_devmath.h"
 #include "rdyn_kernels.h"
 #include "rdyn_gram_common.h"
 #include "rdyn_duo_common.h"
+#include "rdyn_launch_util.h"
 
 #ifndef RDYN_DUO_SWEEP_UNROLL
 #define RDYN_DUO_SWEEP_UNROLL 1  // link loop of the sweeper: 1 = rolled (unrolled measured no better: more moves and SGPR spills)
@@ -351,17 +351,8 @@ __global__ __launch_bounds__(KIN ? 768 : 512) void k_regressor_gram_duo(const Rd
 template <int NJ, bool DIRECT, int XB, bool ALLREV = false, int KIN = 0>
 hipError_t launch_duo_nj2(const RdynLdsGramArgs& a, int blocks, size_t lds_bytes, hipStream_t st)
 {
-  static std::atomic<uint64_t> attr_set{0};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  hipError_t e = opt_in_lds_once<k_regressor_gram_duo<NJ, DIRECT, XB, ALLREV, KIN>>();
   if (e != hipSuccess) return e;
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(attr_set.load(std::memory_order_acquire) & bit))
-  {
-    e = hipFuncSetAttribute((const void*)k_regressor_gram_duo<NJ, DIRECT, XB, ALLREV, KIN>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set.fetch_or(bit, std::memory_order_release);
-  }
   hipLaunchKernelGGL((k_regressor_gram_duo<NJ, DIRECT, XB, ALLREV, KIN>), dim3(blocks), dim3(KIN ? 768 : 512), lds_bytes, st, a);
   return hipGetLastError();
 }
@@ -416,14 +407,7 @@ bool rdyn_regressor_gram_duo_supports_components(int n_cols, int n_comp_cols)
 
 hipError_t rdyn_launch_regressor_gram_duo(int n_cols, const RdynLdsGramArgs& a, int blocks, size_t lds_bytes, hipStream_t st)
 {
-  switch (n_cols / 10)  // chain joints
-  {
-  case 2: return launch_duo_nj<2>(a, blocks, lds_bytes, st);
-  case 3: return launch_duo_nj<3>(a, blocks, lds_bytes, st);
-  case 4: return launch_duo_nj<4>(a, blocks, lds_bytes, st);
-  case 5: return launch_duo_nj<5>(a, blocks, lds_bytes, st);
-  case 6: return launch_duo_nj<6>(a, blocks, lds_bytes, st);
-  case 7: return launch_duo_nj<7>(a, blocks, lds_bytes, st);
-  default: return hipErrorInvalidValue;
-  }
+#define CALL(N) launch_duo_nj<N>(a, blocks, lds_bytes, st)
+  RDYN_DISPATCH_JOINTS_2_7(n_cols / 10, CALL)  // chain joints
+#undef CALL
 }

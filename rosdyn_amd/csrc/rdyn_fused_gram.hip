@@ -26,6 +26,7 @@
 #include "rdyn_kernels.h"
 #include "rdyn_record_stage.h"
 #include "rdyn_gram_common.h"
+#include "rdyn_launch_util.h"
 
 namespace
 {
@@ -183,18 +184,7 @@ hipError_t launch_fused_nj(const RdynFusedGramArgs& a, int blocks, hipStream_t s
 
 hipError_t rdyn_launch_regressor_gram_fused(int n_joints, const RdynFusedGramArgs& a, int blocks, hipStream_t st)
 {
-  switch (n_joints)
-  {
-  case 1: return launch_fused_nj<1>(a, blocks, st);
-  case 2: return launch_fused_nj<2>(a, blocks, st);
-  case 3: return launch_fused_nj<3>(a, blocks, st);
-  case 4: return launch_fused_nj<4>(a, blocks, st);
-  case 5: return launch_fused_nj<5>(a, blocks, st);
-  case 6: return launch_fused_nj<6>(a, blocks, st);
-  case 7: return launch_fused_nj<7>(a, blocks, st);
-  case 8: return launch_fused_nj<8>(a, blocks, st);
-  case 9: return launch_fused_nj<9>(a, blocks, st);
-  case 10: return launch_fused_nj<10>(a, blocks, st);
-  default: return hipErrorInvalidValue;
-  }
+#define CALL(N) launch_fused_nj<N>(a, blocks, st)
+  RDYN_DISPATCH_NJ(n_joints, CALL)
+#undef CALL
 }

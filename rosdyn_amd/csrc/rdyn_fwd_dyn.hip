@@ -29,6 +29,7 @@
 #include "rdyn_record_stage.h"
 #include "rdyn_fwd_dyn_body.h"
 #include "rdyn_component_row.h"
+#include "rdyn_launch_util.h"
 #include <type_traits>
 
 namespace
@@ -134,20 +135,9 @@ hipError_t launch_fwd_nj(const RdynFwdDynArgs& a, hipStream_t st)
 hipError_t rdyn_launch_forward_dynamics(int n_joints, const RdynFwdDynArgs& a, hipStream_t st)
 {
   if (a.n_samples <= 0) return hipSuccess;
-  switch (n_joints)
-  {
-  case 1: return launch_fwd_nj<1>(a, st);
-  case 2: return launch_fwd_nj<2>(a, st);
-  case 3: return launch_fwd_nj<3>(a, st);
-  case 4: return launch_fwd_nj<4>(a, st);
-  case 5: return launch_fwd_nj<5>(a, st);
-  case 6: return launch_fwd_nj<6>(a, st);
-  case 7: return launch_fwd_nj<7>(a, st);
-  case 8: return launch_fwd_nj<8>(a, st);
-  case 9: return launch_fwd_nj<9>(a, st);
-  case 10: return launch_fwd_nj<10>(a, st);
-  default: return hipErrorInvalidValue;
-  }
+#define CALL(N) launch_fwd_nj<N>(a, st)
+  RDYN_DISPATCH_NJ(n_joints, CALL)
+#undef CALL
 }
 
 hipError_t rdyn_launch_forward_solve(const RdynFwdSolveArgs& a, hipStream_t st)

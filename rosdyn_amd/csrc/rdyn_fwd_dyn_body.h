@@ -4,34 +4,22 @@
 // described at the head of rdyn_fwd_dyn.hip and written once, in rdyn_fwd_dyn_body.inc.  k_fwd_dyn includes that text in place with q and
 // dq loaded where they are used: called through the function below (any way of handing it the loads: a functor, a flag) its register
 // figures moved (k_fwd_dyn<3> 166 -> 167 VGPRs, <9> and <10> 104 -> 98 and 146 -> 138 AGPRs), and the refactoring was not to change it.
-// k_rollout calls the function, q and dq in registers.
+// k_rollout calls the function, q and dq in registers.  The same holds for the steps of rdyn_joint_step.h: joint_transform and
+// composite_to_parent are called (every kernel's registers, scratch and instruction count as before); joint_sincos_state moved the
+// registers of k_fwd_dyn<8..10> (320 -> 318, 360 -> 358, 402 -> 406 VGPRs), link_wrench those of k_rollout<5..6, .> and the scratch of
+// k_rollout<10, .> (0 -> 20 B with Euler), and the forward step with DDq = 0 is not primal_step (one more fma per axis): these three stay
+// written out in the .inc.
 #ifndef RDYN_FWD_DYN_BODY_H
 #define RDYN_FWD_DYN_BODY_H
 #include <hip/hip_runtime.h>
 #include "rdyn_device.h"
 #include "rdyn_devmath.h"
+#include "rdyn_joint_step.h"
 
 namespace
 {
 #define RDYN_FWD_PIVOT_FLOOR 1e-10  // rdyn_ik.hip's RDYN_IK_PIVOT_FLOOR
 #define TRI(i, j) ((i) * ((i) + 1) / 2 + (j))  // lower triangle, i >= j
-
-// parent -> child transform of a joint from its saved sin q / 1 - cos q (revolute) or q (prismatic)
-__device__ __forceinline__ void joint_transform(JointRef J, double s0, double s1, double (&R)[9], V3& t)
-{
-  t = ld3(J.t);
-  if (J.type == RDYN_REVOLUTE)
-  {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = fma(s0, J.B[i], fma(s1, J.C[i], J.A[i]));
-  }
-  else
-  {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = J.A[i];
-    if (J.type == RDYN_PRISMATIC) t = axpy(t, ld3(J.up), s0);
-  }
-}
 
 // the evaluation at a state held in registers (by chain joint): returns ok
 template <int NJ>

@@ -128,20 +128,7 @@
       cN[f] = rot(R, cN[f]) + cross(t, Fp);
       cF[f] = Fp;
     }
-    {
-      // m, h = m c, I about the origin: h' = R h + m t, I' = R I R' + (m |t|^2 + 2 t.hb) 1 - (m t t' + t hb' + hb t'), hb = R h
-      const V3 hb = rot(R, ch);
-      const V3 r0 = mk(R[0], R[1], R[2]), r1 = mk(R[3], R[4], R[5]), r2 = mk(R[6], R[7], R[8]);
-      const V3 c0 = symv(cI, r0), c1 = symv(cI, r1), c2 = symv(cI, r2);
-      const double tr = cm * dot(t, t) + 2.0 * dot(t, hb);
-      cI[0] = dot(r0, c0) + tr - (cm * t.x * t.x + 2.0 * t.x * hb.x);
-      cI[1] = dot(r0, c1) - (cm * t.x * t.y + t.x * hb.y + hb.x * t.y);
-      cI[2] = dot(r0, c2) - (cm * t.x * t.z + t.x * hb.z + hb.x * t.z);
-      cI[3] = dot(r1, c1) + tr - (cm * t.y * t.y + 2.0 * t.y * hb.y);
-      cI[4] = dot(r1, c2) - (cm * t.y * t.z + t.y * hb.z + hb.y * t.z);
-      cI[5] = dot(r2, c2) + tr - (cm * t.z * t.z + 2.0 * t.z * hb.z);
-      ch = axpy(hb, t, cm);
-    }
+    ch = composite_to_parent(R, t, cm, ch, cI);
   }
 
   // ---- M = L L' in place (the diagonal holds 1 / L_jj), L y = rhs, L' x = y

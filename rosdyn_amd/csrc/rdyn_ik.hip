@@ -27,6 +27,7 @@
 #include "rdyn_devmath.h"
 #include "rdyn_kernels.h"
 #include "rdyn_rotvec.h"
+#include "rdyn_launch_util.h"
 
 namespace
 {
@@ -492,18 +493,7 @@ hipError_t rdyn_launch_frame_distance(const RdynFrameDistanceArgs& a, hipStream_
 
 hipError_t rdyn_launch_local_ik(int n_joints, const RdynIkArgs& a, hipStream_t st)
 {
-  switch (n_joints)
-  {
-  case 1: return launch_ik_nj<1>(a, st);
-  case 2: return launch_ik_nj<2>(a, st);
-  case 3: return launch_ik_nj<3>(a, st);
-  case 4: return launch_ik_nj<4>(a, st);
-  case 5: return launch_ik_nj<5>(a, st);
-  case 6: return launch_ik_nj<6>(a, st);
-  case 7: return launch_ik_nj<7>(a, st);
-  case 8: return launch_ik_nj<8>(a, st);
-  case 9: return launch_ik_nj<9>(a, st);
-  case 10: return launch_ik_nj<10>(a, st);
-  default: return hipErrorInvalidValue;
-  }
+#define CALL(N) launch_ik_nj<N>(a, st)
+  RDYN_DISPATCH_NJ(n_joints, CALL)
+#undef CALL
 }

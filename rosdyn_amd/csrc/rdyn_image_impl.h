@@ -28,11 +28,11 @@
 #ifndef RDYN_IMAGE_IMPL_H
 #define RDYN_IMAGE_IMPL_H
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include "rdyn_device.h"
 #include "rdyn_devmath.h"
 #include "rdyn_kernels.h"
 #include "rdyn_image_patterns.h"
+#include "rdyn_launch_util.h"
 
 namespace
 {
@@ -132,16 +132,8 @@ hipError_t launch_image(const RdynSweepArgs& a, hipStream_t st)
 #endif
   if constexpr (WV > 1)
   {
-    static std::atomic<uint64_t> attr{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    hipError_t e = opt_in_lds_once<k_image_sweep<NJ, FIX, kNT, STACKED, MAP, EXPAND>>();
     if (e != hipSuccess) return e;
-    if (!(attr.load() & (1ull << (dev & 63))))
-    {
-      e = hipFuncSetAttribute((const void*)k_image_sweep<NJ, FIX, kNT, STACKED, MAP, EXPAND>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-      attr.fetch_or(1ull << (dev & 63));
-    }
   }
   hipLaunchKernelGGL((k_image_sweep<NJ, FIX, kNT, STACKED, MAP, EXPAND>), grid, dim3(64 * WV), lds, st, a);
   return hipGetLastError();

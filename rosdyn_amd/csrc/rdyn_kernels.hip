@@ -36,6 +36,7 @@
 #include "rdyn_devmath.h"
 #include "rdyn_kernels.h"
 #include "rdyn_record_stage.h"
+#include "rdyn_launch_util.h"
 
 namespace
 {
@@ -557,22 +558,6 @@ hipError_t launch_base_nj(const RdynKinArgs& a, hipStream_t st)
 }
 
 }  // namespace
-
-#define RDYN_DISPATCH_NJ(nj, CALL)                 \
-  switch (nj)                                      \
-  {                                                \
-  case 1: return CALL(1);                          \
-  case 2: return CALL(2);                          \
-  case 3: return CALL(3);                          \
-  case 4: return CALL(4);                          \
-  case 5: return CALL(5);                          \
-  case 6: return CALL(6);                          \
-  case 7: return CALL(7);                          \
-  case 8: return CALL(8);                          \
-  case 9: return CALL(9);                          \
-  case 10: return CALL(10);                        \
-  default: return hipErrorInvalidValue;            \
-  }
 
 // The file is compiled in slices (Makefile: -DRDYN_KERNELS_PART=0..3, like rdyn_image_part.hip) so that the instantiations build in
 // parallel: 0 the single-chain sweeps, 1 every getter of a sample in one launch, 2 the base sweeps, 3 the mixed-chain plans.

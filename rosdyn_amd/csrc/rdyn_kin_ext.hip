@@ -15,6 +15,7 @@
 #include "rdyn_devmath.h"
 #include "rdyn_kernels.h"
 #include "rdyn_record_stage.h"
+#include "rdyn_launch_util.h"
 
 namespace
 {
@@ -367,18 +368,7 @@ hipError_t launch_ext_nj(const RdynKinExtArgs& a, hipStream_t st)
 hipError_t rdyn_launch_base_ext(int n_joints, const RdynKinExtArgs& a, hipStream_t st)
 {
   if (a.n_samples <= 0) return hipSuccess;
-  switch (n_joints)
-  {
-  case 1: return launch_ext_nj<1>(a, st);
-  case 2: return launch_ext_nj<2>(a, st);
-  case 3: return launch_ext_nj<3>(a, st);
-  case 4: return launch_ext_nj<4>(a, st);
-  case 5: return launch_ext_nj<5>(a, st);
-  case 6: return launch_ext_nj<6>(a, st);
-  case 7: return launch_ext_nj<7>(a, st);
-  case 8: return launch_ext_nj<8>(a, st);
-  case 9: return launch_ext_nj<9>(a, st);
-  case 10: return launch_ext_nj<10>(a, st);
-  default: return hipErrorInvalidValue;
-  }
+#define CALL(N) launch_ext_nj<N>(a, st)
+  RDYN_DISPATCH_NJ(n_joints, CALL)
+#undef CALL
 }

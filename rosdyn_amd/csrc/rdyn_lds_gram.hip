@@ -18,13 +18,13 @@
 // Requirements (else rdyn_regressor_gram falls back to rdyn_fused_gram.hip): 2 <= n_active <= 7, input joints in
 // chain order (row prefix property), LDS tile x 4 waves <= 160 KB.
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <cstdint>
 #include "rdyn_device.h"
 #include "rdyn_devmath.h"
 #include "rdyn_kernels.h"
 #include "rdyn_gram_common.h"
 #include "rdyn_duo_common.h"
+#include "rdyn_launch_util.h"
 
 namespace
 {
@@ -325,18 +325,8 @@ __global__ __launch_bounds__(256) void k_regressor_gram_lds(const RdynLdsGramArg
 template <int NJ>
 hipError_t launch_lds_nj(const RdynLdsGramArgs& a, int blocks, size_t lds_bytes, hipStream_t st)
 {
-  // > 64 KB of dynamic LDS needs the opt-in attribute, once per instantiation AND device (one bit per device ordinal)
-  static std::atomic<uint64_t> attr_set{0};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  hipError_t e = opt_in_lds_once<k_regressor_gram_lds<NJ>>();
   if (e != hipSuccess) return e;
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(attr_set.load(std::memory_order_acquire) & bit))
-  {
-    e = hipFuncSetAttribute((const void*)k_regressor_gram_lds<NJ>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set.fetch_or(bit, std::memory_order_release);
-  }
   hipLaunchKernelGGL((k_regressor_gram_lds<NJ>), dim3(blocks), dim3(256), lds_bytes, st, a);
   return hipGetLastError();
 }
@@ -344,17 +334,7 @@ hipError_t launch_lds_nj(const RdynLdsGramArgs& a, int blocks, size_t lds_bytes,
 
 hipError_t rdyn_launch_regressor_gram_lds(int n_cols, const RdynLdsGramArgs& a, int blocks, size_t lds_bytes, hipStream_t st)
 {
-  switch (n_cols / 10)  // chain joints
-  {
-  case 2: return launch_lds_nj<2>(a, blocks, lds_bytes, st);
-  case 3: return launch_lds_nj<3>(a, blocks, lds_bytes, st);
-  case 4: return launch_lds_nj<4>(a, blocks, lds_bytes, st);
-  case 5: return launch_lds_nj<5>(a, blocks, lds_bytes, st);
-  case 6: return launch_lds_nj<6>(a, blocks, lds_bytes, st);
-  case 7: return launch_lds_nj<7>(a, blocks, lds_bytes, st);
-  case 8: return launch_lds_nj<8>(a, blocks, lds_bytes, st);
-  case 9: return launch_lds_nj<9>(a, blocks, lds_bytes, st);
-  case 10: return launch_lds_nj<10>(a, blocks, lds_bytes, st);
-  default: return hipErrorInvalidValue;
-  }
+#define CALL(N) launch_lds_nj<N>(a, blocks, lds_bytes, st)
+  RDYN_DISPATCH_JOINTS_2_10(n_cols / 10, CALL)  // chain joints
+#undef CALL
 }

@@ -26,12 +26,13 @@
 // n (the moving ones) may be 6 or fewer here; the same floor then applies to S_F (a pivot at most 1e-10 trace(S_F) -> -1), which
 // with lambda^2 below it is singular as soon as fewer than six variables are free.  k_local_ik solves such an undamped H_FF.
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <cfloat>
 #include "rdyn_device.h"
 #include "rdyn_devmath.h"
 #include "rdyn_kernels.h"
 #include "rdyn_rotvec.h"
+#include "rdyn_launch_util.h"
+#include "rdyn_long_common.h"
 
 namespace
 {
@@ -39,47 +40,6 @@ namespace
 #define RDYN_LONG_IK_PIVOT_FLOOR 1e-10  // k_local_ik's RDYN_IK_PIVOT_FLOOR
 #define TRI6(i, j) ((i) * ((i) + 1) / 2 + (j))  // lower triangle of a 6 x 6, i >= j
 constexpr int kLongIkSlots = 7;                 // LDS doubles per variable and lane
-
-typedef const RDYN_CONST_AS RdynLongChainConst* LongChainPtr;
-__device__ __forceinline__ LongChainPtr as_const_long(const RdynLongChainConst* p)
-{
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-  return (LongChainPtr)p;
-#pragma clang diagnostic pop
-}
-
-// one step of computeFrames (primitives_impl.h:863-882): on entry R, p = frame of the parent link, on exit of the child;
-// z = the joint axis in the base frame
-__device__ __forceinline__ void ik_frame_step(JointRef J, double qf, double (&R)[9], V3& p, V3& z)
-{
-  const int type = J.type;
-  double Rpc[9];
-  V3 t = ld3(J.t);
-  if (type == RDYN_REVOLUTE)
-  {
-    double sn, cs;
-    rdyn_sincos(qf, &sn, &cs);
-    const double oc = 1.0 - cs;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) Rpc[i] = fma(sn, J.B[i], fma(oc, J.C[i], J.A[i]));
-  }
-  else
-  {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) Rpc[i] = J.A[i];
-    if (type == RDYN_PRISMATIC) t = axpy(t, ld3(J.up), qf);
-  }
-  z = rot(R, ld3(J.up));
-  p = p + rot(R, t);
-  double Rn[9];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int cc = 0; cc < 3; ++cc) Rn[r * 3 + cc] = fma(R[r * 3 + 0], Rpc[cc], fma(R[r * 3 + 1], Rpc[3 + cc], R[r * 3 + 2] * Rpc[6 + cc]));
-#pragma unroll
-  for (int i = 0; i < 9; ++i) R[i] = Rn[i];
-}
 
 __device__ __forceinline__ double dot6(const double (&x)[6], const double (&y)[6])
 {
@@ -94,11 +54,10 @@ __global__ __launch_bounds__(64) void k_long_ik(const RdynLongIkArgs a)
   const int nj = c->n_joints, n = a.n_var;
   const int64_t s = (int64_t)blockIdx.x * 64 + threadIdx.x;
   if (s >= a.n_samples) return;
-  double* const mine = ik_lds + threadIdx.x;
-  auto at = [&](int slot, int k) -> double& { return mine[(slot * n + k) * 64]; };
+  const JointState js = {ik_lds + threadIdx.x, n, 64};  // slots 0..5: a variable's column, 6: its step
   auto ld_col = [&](int k, double (&ak)[6]) {
 #pragma unroll
-    for (int i = 0; i < 6; ++i) ak[i] = at(i, k);
+    for (int i = 0; i < 6; ++i) ak[i] = js.at(i, k);
   };
 
   // target frame, column-major 3x4 [R | p]
@@ -135,12 +94,12 @@ __global__ __launch_bounds__(64) void k_long_ik(const RdynLongIkArgs a)
     {
       JointRef J = c->j[f];
       const int idx = J.in_idx;
-      V3 z;
-      ik_frame_step(J, idx >= 0 ? sol[idx * a.in_sj] : 0.0, R, p, z);
+      V3 z, d;
+      frame_step(J, idx >= 0 ? sol[idx * a.in_sj] : 0.0, R, p, z, d);
       if (idx >= 0 && J.type != RDYN_FIXED)
       {
-        at(0, k) = p.x; at(1, k) = p.y; at(2, k) = p.z;
-        at(3, k) = z.x; at(4, k) = z.y; at(5, k) = z.z;
+        js.put3(0, k, p);
+        js.put3(3, k, z);
         ++k;
       }
     }
@@ -174,7 +133,7 @@ __global__ __launch_bounds__(64) void k_long_ik(const RdynLongIkArgs a)
     {
       JointRef J = c->j[f];
       if (J.in_idx < 0 || J.type == RDYN_FIXED) continue;
-      const V3 po = mk(at(0, k), at(1, k), at(2, k)), z = mk(at(3, k), at(4, k), at(5, k));
+      const V3 po = js.get3(0, k), z = js.get3(3, k);
       V3 jl = z, ja = mk(0, 0, 0);
       if (J.type == RDYN_REVOLUTE)
       {
@@ -183,7 +142,7 @@ __global__ __launch_bounds__(64) void k_long_ik(const RdynLongIkArgs a)
       }
       const double ak[6] = {sw[0] * jl.x, sw[1] * jl.y, sw[2] * jl.z, sw[3] * ja.x, sw[4] * ja.y, sw[5] * ja.z};
 #pragma unroll
-      for (int i = 0; i < 6; ++i) at(i, k) = ak[i];
+      for (int i = 0; i < 6; ++i) js.at(i, k) = ak[i];
       const double a2 = dot6(ak, ak);
       tr += a2 + lam2;
       amax2 = fmax(amax2, a2);
@@ -204,7 +163,7 @@ __global__ __launch_bounds__(64) void k_long_ik(const RdynLongIkArgs a)
     {
       const double q = sol_of(k), lo = a.q_min[k] - q, hi = a.q_max[k] - q;
       crossed = crossed || lo > hi;
-      at(6, k) = fmin(fmax(0.0, lo), hi);
+      js.at(6, k) = fmin(fmax(0.0, lo), hi);
       if (lo > 0.0) actL |= 1u << k;
       else if (hi < 0.0) actU |= 1u << k;
     }
@@ -243,7 +202,7 @@ __global__ __launch_bounds__(64) void k_long_ik(const RdynLongIkArgs a)
         ld_col(k, ak);
         if ((act >> k) & 1u)
         {
-          const double d = at(6, k);
+          const double d = js.at(6, k);
 #pragma unroll
           for (int i = 0; i < 6; ++i) r[i] = fma(-ak[i], d, r[i]);
         }
@@ -310,7 +269,7 @@ __global__ __launch_bounds__(64) void k_long_ik(const RdynLongIkArgs a)
         if ((act >> k) & 1u) continue;
         double ak[6];
         ld_col(k, ak);
-        const double t = dot6(ak, y), d = at(6, k), q = sol_of(k);
+        const double t = dot6(ak, y), d = js.at(6, k), q = sol_of(k);
         const double lo = a.q_min[k] - q, hi = a.q_max[k] - q;
         if (t < lo || t > hi)
         {
@@ -332,11 +291,11 @@ __global__ __launch_bounds__(64) void k_long_ik(const RdynLongIkArgs a)
           if ((act >> k) & 1u) continue;
           double ak[6];
           ld_col(k, ak);
-          const double d = at(6, k);
-          at(6, k) = fma(alpha, dot6(ak, y) - d, d);
+          const double d = js.at(6, k);
+          js.at(6, k) = fma(alpha, dot6(ak, y) - d, d);
         }
         const double q = sol_of(blk);
-        at(6, blk) = blk_up ? a.q_max[blk] - q : a.q_min[blk] - q;
+        js.at(6, blk) = blk_up ? a.q_max[blk] - q : a.q_min[blk] - q;
         if (blk_up) actU |= 1u << blk;
         else actL |= 1u << blk;
         // the variable just released runs straight back into the bound it left (alpha = 0): its multiplier was rounding -- the
@@ -351,7 +310,7 @@ __global__ __launch_bounds__(64) void k_long_ik(const RdynLongIkArgs a)
         if ((act >> k) & 1u) continue;
         double ak[6];
         ld_col(k, ak);
-        at(6, k) = dot6(ak, y);
+        js.at(6, k) = dot6(ak, y);
       }
       if (act == 0u) break;
       // multipliers of the bound variables: g_B = A_B'(A dq - b) + lambda^2 dq_B, >= 0 at a lower bound, <= 0 at an upper one
@@ -362,7 +321,7 @@ __global__ __launch_bounds__(64) void k_long_ik(const RdynLongIkArgs a)
       {
         double ak[6];
         ld_col(k, ak);
-        const double d = at(6, k);
+        const double d = js.at(6, k);
 #pragma unroll
         for (int i = 0; i < 6; ++i) res[i] = fma(ak[i], d, res[i]);
         sum_ad = fma(sqrt(dot6(ak, ak)), fabs(d), sum_ad);
@@ -377,7 +336,7 @@ __global__ __launch_bounds__(64) void k_long_ik(const RdynLongIkArgs a)
         if (!((act >> k) & 1u)) continue;
         double ak[6];
         ld_col(k, ak);
-        const double g = fma(lam2, at(6, k), dot6(ak, res));
+        const double g = fma(lam2, js.at(6, k), dot6(ak, res));
         const double viol = ((actL >> k) & 1u) ? -g : g;
         if (viol > worst)
         {
@@ -397,7 +356,7 @@ __global__ __launch_bounds__(64) void k_long_ik(const RdynLongIkArgs a)
       break;
     }
 #pragma unroll 1
-    for (k = 0; k < n; ++k) sol_of(k) += at(6, k);  // :1428
+    for (k = 0; k < n; ++k) sol_of(k) += js.at(6, k);  // :1428
   }
   if (a.status) a.status[s] = status;
   if (a.iterations) a.iterations[s] = it;
@@ -414,18 +373,8 @@ hipError_t rdyn_launch_long_ik(const RdynLongIkArgs& a, hipStream_t st)
   const size_t lds = rdyn_long_ik_lds_bytes(a.n_var);
   if (lds > 64 * 1024)
   {
-    // more than 64 KB of dynamic LDS needs the attribute, once per device
-    static std::atomic<uint64_t> done{0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    hipError_t e = opt_in_lds_once<k_long_ik>();
     if (e != hipSuccess) return e;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(done.load(std::memory_order_acquire) & bit))
-    {
-      e = hipFuncSetAttribute((const void*)k_long_ik, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-      done.fetch_or(bit, std::memory_order_release);
-    }
   }
   hipLaunchKernelGGL(k_long_ik, dim3((unsigned)((a.n_samples + 63) / 64)), dim3(64), lds, st, a);
   return hipGetLastError();

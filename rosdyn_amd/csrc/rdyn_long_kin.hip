@@ -19,18 +19,10 @@
 #include "rdyn_devmath.h"
 #include "rdyn_kernels.h"
 #include "rdyn_record_stage.h"
+#include "rdyn_long_common.h"
 
 namespace
 {
-typedef const RDYN_CONST_AS RdynLongChainConst* LongChainPtr;
-__device__ __forceinline__ LongChainPtr as_const_long(const RdynLongChainConst* p)
-{
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-  return (LongChainPtr)p;
-#pragma clang diagnostic pop
-}
-
 struct S6
 {
   V3 l, a;
@@ -55,39 +47,6 @@ __device__ __forceinline__ S6 axpy6(S6 a, S6 b, double s)
   r.l = axpy(a.l, b.l, s);
   r.a = axpy(a.a, b.a, s);
   return r;
-}
-
-// One step of computeFrames / computeScrews (primitives_impl.h:863-882): on entry R, p = frame of the parent link; on exit of the
-// child.  zl = the joint axis in the base frame (rotated by the PARENT frame, :879), d = p_child - p_parent.
-__device__ __forceinline__ void frame_step(JointRef J, double qf, double (&R)[9], V3& p, V3& zl, V3& d)
-{
-  const int type = J.type;
-  double Rpc[9];
-  V3 t = ld3(J.t);
-  if (type == RDYN_REVOLUTE)
-  {
-    double sn, cs;
-    rdyn_sincos(qf, &sn, &cs);
-    const double oc = 1.0 - cs;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) Rpc[i] = fma(sn, J.B[i], fma(oc, J.C[i], J.A[i]));
-  }
-  else
-  {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) Rpc[i] = J.A[i];
-    if (type == RDYN_PRISMATIC) t = axpy(t, ld3(J.up), qf);
-  }
-  zl = rot(R, ld3(J.up));
-  d = rot(R, t);
-  double Rn[9];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int cc = 0; cc < 3; ++cc) Rn[r * 3 + cc] = fma(R[r * 3 + 0], Rpc[cc], fma(R[r * 3 + 1], Rpc[3 + cc], R[r * 3 + 2] * Rpc[6 + cc]));
-#pragma unroll
-  for (int i = 0; i < 9; ++i) R[i] = Rn[i];
-  p = p + d;
 }
 
 // LEVEL as in k_base_sweep: 0 frames only, 1 + the Jacobian, 2 + twists, 3 + spatial accelerations

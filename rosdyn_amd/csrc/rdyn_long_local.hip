@@ -23,71 +23,15 @@
 //     inertia, far inside the parity tolerance.  O(n^2) instead of the reference's O(n^3).
 // Joint torques of such chains: the wrench recursion of rdyn_long_kin.hip (k_long_ext).
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <type_traits>
 #include "rdyn_device.h"
 #include "rdyn_devmath.h"
 #include "rdyn_kernels.h"
+#include "rdyn_launch_util.h"
+#include "rdyn_long_common.h"
 
 namespace
 {
-typedef const RDYN_CONST_AS RdynLongChainConst* LongChainPtr;
-__device__ __forceinline__ LongChainPtr as_const_long(const RdynLongChainConst* p)
-{
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-  return (LongChainPtr)p;
-#pragma clang diagnostic pop
-}
-
-// One step of computeFrames / computeScrews (primitives_impl.h:863-882): on entry R, p = frame of the parent link; on exit of the
-// child.  zl = the joint axis in the base frame (rotated by the PARENT frame, :879), d = p_child - p_parent.
-__device__ __forceinline__ void frame_step(JointRef J, double qf, double (&R)[9], V3& p, V3& zl, V3& d)
-{
-  const int type = J.type;
-  double Rpc[9];
-  V3 t = ld3(J.t);
-  if (type == RDYN_REVOLUTE)
-  {
-    double sn, cs;
-    rdyn_sincos(qf, &sn, &cs);
-    const double oc = 1.0 - cs;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) Rpc[i] = fma(sn, J.B[i], fma(oc, J.C[i], J.A[i]));
-  }
-  else
-  {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) Rpc[i] = J.A[i];
-    if (type == RDYN_PRISMATIC) t = axpy(t, ld3(J.up), qf);
-  }
-  zl = rot(R, ld3(J.up));
-  d = rot(R, t);
-  double Rn[9];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int cc = 0; cc < 3; ++cc) Rn[r * 3 + cc] = fma(R[r * 3 + 0], Rpc[cc], fma(R[r * 3 + 1], Rpc[3 + cc], R[r * 3 + 2] * Rpc[6 + cc]));
-#pragma unroll
-  for (int i = 0; i < 9; ++i) R[i] = Rn[i];
-  p = p + d;
-}
-
-// wave-private per-joint state: value v of joint j of the lane's sample at st[(v * nj + j) * 64 + lane]
-struct JointState
-{
-  double* st;
-  int nj;
-  __device__ __forceinline__ double& at(int v, int j) const { return st[(v * nj + j) * 64]; }
-  __device__ __forceinline__ void put3(int v0, int j, V3 x) const
-  {
-    at(v0, j) = x.x;
-    at(v0 + 1, j) = x.y;
-    at(v0 + 2, j) = x.z;
-  }
-  __device__ __forceinline__ V3 get3(int v0, int j) const { return mk(at(v0, j), at(v0 + 1, j), at(v0 + 2, j)); }
-};
-
 // columns 2 G, 2 G + 1 of one row of a link's block (the closed form above, one column group at a time: the staged kernel forms a link's
 // block in five passes of two columns, see below)
 struct RowCtx
@@ -163,7 +107,7 @@ __global__ __launch_bounds__(64) void k_long_regressor(const RdynLongLocalArgs a
   const bool live = lane < valid;
   if (STAGE == 0 && !live) return;
   const int64_t s = s_wave + (live ? lane : valid - 1);  // (staged: lanes past the batch repeat the last sample and take part in the copy-out)
-  const JointState js = {joint_lds + lane, nj};
+  const JointState js = {joint_lds + lane, nj, 64};
   double* const tile = joint_lds + 7 * nj * 64;
   const double* __restrict__ qp = a.q + s * a.in_ss;
   const double* __restrict__ dqp = a.dq ? a.dq + s * a.in_ss : nullptr;
@@ -417,7 +361,7 @@ __global__ __launch_bounds__(64) void k_long_inertia(const RdynLongLocalArgs a)
   const int lane = threadIdx.x;
   const int64_t s = (int64_t)blockIdx.x * 64 + lane;
   if (s >= a.n_samples) return;
-  const JointState js = {joint_lds + lane, nj};
+  const JointState js = {joint_lds + lane, nj, 64};
   const double* __restrict__ qp = a.q + s * a.in_ss;
   double* __restrict__ mp = a.M + s * a.m_ss;
   Inertia10 total = zero10(), upstream = zero10();
@@ -483,19 +427,18 @@ __global__ __launch_bounds__(64) void k_long_inertia(const RdynLongLocalArgs a)
   }
 }
 
-// more than 64 KB of dynamic LDS needs the attribute, once per kernel and device (slot: 0 inertia, 1..3 the regressor's STAGE 0..2)
-hipError_t allow_big_lds(const void* fn, size_t bytes, int slot)
+// launches Kernel on one wave per 64 samples; more than 64 KB of dynamic LDS needs the attribute first
+template <auto Kernel>
+hipError_t launch_long_local(const RdynLongLocalArgs& a, size_t lds, hipStream_t st)
 {
-  if (bytes <= 64 * 1024) return hipSuccess;
-  static std::atomic<uint64_t> done[4];
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  const uint64_t bit = 1ull << (dev & 63);
-  if (done[slot].load(std::memory_order_acquire) & bit) return hipSuccess;
-  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e == hipSuccess) done[slot].fetch_or(bit, std::memory_order_release);
-  return e;
+  if (lds > 160 * 1024) return hipErrorInvalidValue;
+  if (lds > 64 * 1024)
+  {
+    hipError_t e = opt_in_lds_once<Kernel>();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)((a.n_samples + 63) / 64)), dim3(64), lds, st, a);
+  return hipGetLastError();
 }
 }  // namespace
 
@@ -505,25 +448,12 @@ hipError_t rdyn_launch_long_local(int mode, int n_joints, const RdynLongLocalArg
 {
   if (a.n_samples <= 0) return hipSuccess;
   size_t lds = rdyn_long_local_lds_bytes(mode, n_joints);
-  const dim3 grid((unsigned)((a.n_samples + 63) / 64));
-  if (mode == RDYN_MODE_INERTIA)
-  {
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    hipError_t e = allow_big_lds((const void*)k_long_inertia, lds, 0);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_long_inertia, grid, dim3(64), lds, st, a);
-    return hipGetLastError();
-  }
+  if (mode == RDYN_MODE_INERTIA) return launch_long_local<k_long_inertia>(a, lds, st);
   // a.stage (decided by the host: a row-contiguous layout, 16-byte aligned Y, even strides): the tile behind the joint state
   const size_t tile = a.stage == 1 ? (size_t)64 * (2 * a.n_active + 1) * 8 : (a.stage == 2 ? (size_t)2 * (64 * a.n_active + 2) * 8 : 0);
   const int stage = (a.stage && lds + tile <= 160 * 1024) ? a.stage : 0;
   if (stage) lds += tile;
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  const void* fn = stage == 1 ? (const void*)k_long_regressor<1> : (stage == 2 ? (const void*)k_long_regressor<2> : (const void*)k_long_regressor<0>);
-  hipError_t e = allow_big_lds(fn, lds, 1 + stage);
-  if (e != hipSuccess) return e;
-  if (stage == 1) hipLaunchKernelGGL(k_long_regressor<1>, grid, dim3(64), lds, st, a);
-  else if (stage == 2) hipLaunchKernelGGL(k_long_regressor<2>, grid, dim3(64), lds, st, a);
-  else hipLaunchKernelGGL(k_long_regressor<0>, grid, dim3(64), lds, st, a);
-  return hipGetLastError();
+  if (stage == 1) return launch_long_local<k_long_regressor<1>>(a, lds, st);
+  if (stage == 2) return launch_long_local<k_long_regressor<2>>(a, lds, st);
+  return launch_long_local<k_long_regressor<0>>(a, lds, st);
 }

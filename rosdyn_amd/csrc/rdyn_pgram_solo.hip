@@ -1,7 +1,6 @@
 // rdyn_pgram_solo.hip -- pass B of the preconditioned R factor (rdyn_cholqr.hip) for a 7-joint arm WITH component columns: the
 // kernel whose waves sweep and consume their own tile (its own translation unit: one instantiation per quantised column shift).
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <cstdint>
 #include <type_traits>
 #include "rdyn_device.h"
@@ -9,6 +8,7 @@
 #include "rdyn_kernels.h"
 #include "rdyn_gram_common.h"
 #include "rdyn_duo_common.h"
+#include "rdyn_launch_util.h"
 
 #ifndef RDYN_CHOLQR_AHEAD
 #define RDYN_CHOLQR_AHEAD 2  // rows of W operands requested ahead of their MFMAs (as in rdyn_cholqr.hip)
@@ -274,17 +274,8 @@ __global__ __launch_bounds__(64 * NW) void k_regressor_pgram_solo(const RdynLdsG
 template <int NJ, bool ALLREV, int NW, bool WGLOBAL, int SHC>
 hipError_t launch_pgram_solo(const RdynLdsGramArgs& a, const double* W, const int* run_flag, int blocks, hipStream_t st)
 {
-  static std::atomic<uint64_t> attr{0};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  hipError_t e = opt_in_lds_once<k_regressor_pgram_solo<NJ, ALLREV, NW, WGLOBAL, SHC>>();
   if (e != hipSuccess) return e;
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(attr.load(std::memory_order_acquire) & bit))
-  {
-    e = hipFuncSetAttribute((const void*)k_regressor_pgram_solo<NJ, ALLREV, NW, WGLOBAL, SHC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr.fetch_or(bit, std::memory_order_release);
-  }
   constexpr int NB = (10 * NJ + 1 + 15) / 16 + 1, NT = NB * (NB + 1) / 2;
   size_t lds = (WGLOBAL ? 0 : (size_t)NT * 2048) + NW * (size_t)a.tile_bytes;
   if (lds < (size_t)NT * 2048) lds = (size_t)NT * 2048;

@@ -26,13 +26,13 @@
 // and the body instantiated once per zero band it spills 44 B and wins (4.90 ms).  8+ joints: more spills, no gain
 // (2.97 vs 2.92 ms at 9 joints) -- those chains keep the two-phase kernel.
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <cstdint>
 #include "rdyn_device.h"
 #include "rdyn_devmath.h"
 #include "rdyn_kernels.h"
 #include "rdyn_gram_common.h"
 #include "rdyn_duo_common.h"
+#include "rdyn_launch_util.h"
 
 #ifndef RDYN_PIPE_UNROLL_MAX
 #define RDYN_PIPE_UNROLL_MAX 6  // chains up to this many joints: unrolled link loop; longer: rolled (A/B: tools/probe_pipe.py)
@@ -246,18 +246,8 @@ __global__ __launch_bounds__(256) void k_regressor_gram_pipe(const RdynLdsGramAr
 template <int NJ>
 hipError_t launch_pipe_nj(const RdynLdsGramArgs& a, int blocks, size_t lds_bytes, hipStream_t st)
 {
-  // > 64 KB of dynamic LDS needs the opt-in attribute, once per instantiation AND device (one bit per device ordinal)
-  static std::atomic<uint64_t> attr_set{0};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  hipError_t e = opt_in_lds_once<k_regressor_gram_pipe<NJ, (NJ > RDYN_PIPE_UNROLL_MAX)>>();
   if (e != hipSuccess) return e;
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(attr_set.load(std::memory_order_acquire) & bit))
-  {
-    e = hipFuncSetAttribute((const void*)k_regressor_gram_pipe<NJ, (NJ > RDYN_PIPE_UNROLL_MAX)>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set.fetch_or(bit, std::memory_order_release);
-  }
   hipLaunchKernelGGL((k_regressor_gram_pipe<NJ, (NJ > RDYN_PIPE_UNROLL_MAX)>), dim3(blocks), dim3(256), lds_bytes, st, a);
   return hipGetLastError();
 }
@@ -267,14 +257,7 @@ bool rdyn_regressor_gram_pipe_supported(int n_cols) { return n_cols >= 20 && n_c
 
 hipError_t rdyn_launch_regressor_gram_pipe(int n_cols, const RdynLdsGramArgs& a, int blocks, size_t lds_bytes, hipStream_t st)
 {
-  switch (n_cols / 10)  // chain joints
-  {
-  case 2: return launch_pipe_nj<2>(a, blocks, lds_bytes, st);
-  case 3: return launch_pipe_nj<3>(a, blocks, lds_bytes, st);
-  case 4: return launch_pipe_nj<4>(a, blocks, lds_bytes, st);
-  case 5: return launch_pipe_nj<5>(a, blocks, lds_bytes, st);
-  case 6: return launch_pipe_nj<6>(a, blocks, lds_bytes, st);
-  case 7: return launch_pipe_nj<7>(a, blocks, lds_bytes, st);
-  default: return hipErrorInvalidValue;
-  }
+#define CALL(N) launch_pipe_nj<N>(a, blocks, lds_bytes, st)
+  RDYN_DISPATCH_JOINTS_2_7(n_cols / 10, CALL)  // chain joints
+#undef CALL
 }

@@ -26,6 +26,7 @@
 #include "rdyn_record_stage.h"
 #include "rdyn_fwd_dyn_body.h"
 #include "rdyn_rollout_body.h"
+#include "rdyn_launch_util.h"
 
 namespace
 {
@@ -116,20 +117,9 @@ hipError_t rdyn_launch_rollout(int n_joints, const RdynRolloutArgs& a, hipStream
 {
   if (a.n_samples <= 0) return hipSuccess;
   if (a.integrator != RDYN_INTEGRATOR_SEMI_IMPLICIT_EULER && a.integrator != RDYN_INTEGRATOR_RK4) return hipErrorInvalidValue;
-  switch (n_joints)
-  {
-  case 1: return launch_rollout_nj<1>(a, st);
-  case 2: return launch_rollout_nj<2>(a, st);
-  case 3: return launch_rollout_nj<3>(a, st);
-  case 4: return launch_rollout_nj<4>(a, st);
-  case 5: return launch_rollout_nj<5>(a, st);
-  case 6: return launch_rollout_nj<6>(a, st);
-  case 7: return launch_rollout_nj<7>(a, st);
-  case 8: return launch_rollout_nj<8>(a, st);
-  case 9: return launch_rollout_nj<9>(a, st);
-  case 10: return launch_rollout_nj<10>(a, st);
-  default: return hipErrorInvalidValue;
-  }
+#define CALL(N) launch_rollout_nj<N>(a, st)
+  RDYN_DISPATCH_NJ(n_joints, CALL)
+#undef CALL
 }
 
 hipError_t rdyn_launch_rollout_stage(const RdynRolloutStageArgs& a, hipStream_t st)

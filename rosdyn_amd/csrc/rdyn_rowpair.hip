@@ -3,22 +3,7 @@
 #include "rdyn_device.h"
 #include "rdyn_devmath.h"
 #include "rdyn_kernels.h"
-
-#define RDYN_DISPATCH_NJ(nj, CALL)                 \
-  switch (nj)                                      \
-  {                                                \
-  case 1: return CALL(1);                          \
-  case 2: return CALL(2);                          \
-  case 3: return CALL(3);                          \
-  case 4: return CALL(4);                          \
-  case 5: return CALL(5);                          \
-  case 6: return CALL(6);                          \
-  case 7: return CALL(7);                          \
-  case 8: return CALL(8);                          \
-  case 9: return CALL(9);                          \
-  case 10: return CALL(10);                        \
-  default: return hipErrorInvalidValue;            \
-  }
+#include "rdyn_launch_util.h"
 
 // ---------------------------------------------------------------------------------------------------
 // k_rowpair_sweep<NJ> -- regressor (+ fused torque) for ROW-CONTIGUOUS output layouts (stride_row == 1: the

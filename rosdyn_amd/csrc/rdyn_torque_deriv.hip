@@ -19,7 +19,7 @@
 //             joint gives u x Fc_k in the moment -- the cross product of the joint axis with the PRIMAL wrench through joint k.
 //   Every entry is stored (or dropped into the wave's record tile) the moment it is known: nothing of the n x n outputs stays in
 //   registers.  O(n^2) per sample like the inertia, no division, one sincos per revolute joint.
-//   M         the composite-rigid-body pass of rdyn_fwd_dyn.hip (spatial inertia of everything downstream of joint j carried to the parent
+//   M         the composite-rigid-body pass of rdyn_fwd_dyn_body.inc (spatial inertia of everything downstream of joint j carried to the parent
 //             with the columns already started), entries stored as they appear; skipped when M is null.
 //
 //   k_torque_deriv<NJ>    1 .. RDYN_MAX_SWEPT_JOINTS chain joints, everything unrolled, one lane per sample, ONE launch.  Chain constants
@@ -37,63 +37,16 @@
 #include "rdyn_devmath.h"
 #include "rdyn_kernels.h"
 #include "rdyn_record_stage.h"
+#include "rdyn_launch_util.h"
+#include "rdyn_long_common.h"
+#include "rdyn_joint_step.h"
 
 namespace
 {
-// parent -> child transform of a joint from its saved sin q / 1 - cos q (revolute) or q (prismatic): rdyn_fwd_dyn.hip
-__device__ __forceinline__ void joint_transform(JointRef J, double s0, double s1, double (&R)[9], V3& t)
-{
-  t = ld3(J.t);
-  if (J.type == RDYN_REVOLUTE)
-  {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = fma(s0, J.B[i], fma(s1, J.C[i], J.A[i]));
-  }
-  else
-  {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = J.A[i];
-    if (J.type == RDYN_PRISMATIC) t = axpy(t, ld3(J.up), s0);
-  }
-}
-
 struct Tangent
 {
   V3 w, vl, al, acc;
 };
-
-// the velocity state of a link carried into its child frame and the child joint's own motion added (rdyn_local_sweep_body.inc)
-__device__ __forceinline__ void primal_step(JointRef J, const double (&R)[9], V3 t, double dqf, double ddqf, V3& w, V3& vl, V3& al, V3& acc)
-{
-  const V3 wn = rotT(R, w);
-  const V3 vn = rotT(R, vl + cross(w, t));
-  const V3 aln = rotT(R, al);
-  const V3 an = rotT(R, acc + cross(al, t));
-  w = wn; vl = vn; al = aln; acc = an;
-  const V3 u = ld3(J.u);
-  if (J.type == RDYN_REVOLUTE)
-  {
-    acc = axpy(acc, cross(vl, u), dqf);
-    al = axpy(axpy(al, cross(w, u), dqf), u, ddqf);
-    w = axpy(w, u, dqf);
-  }
-  else if (J.type == RDYN_PRISMATIC)
-  {
-    acc = axpy(axpy(acc, cross(w, u), dqf), u, ddqf);
-    vl = axpy(vl, u, dqf);
-  }
-}
-
-// net wrench of a link about its origin, own frame (getWrench, primitives_impl.h:1240-1250)
-__device__ __forceinline__ void link_wrench(JointRef J, V3 w, V3 vl, V3 al, V3 acc, V3& fo, V3& no)
-{
-  const RDYN_CONST_AS double* pi = J.pi;
-  const double m = pi[0];
-  const V3 h = ld3(pi + 1);
-  const V3 d = acc + cross(w, vl);
-  fo = axpy(cross(al, h) + cross(w, cross(w, h)), d, m);
-  no = symv(pi + 4, al) + cross(w, symv(pi + 4, w)) + cross(h, d);
-}
 
 // the tangent state at link k for a unit change of q_k (KIND 0) or Dq_k (KIND 1)
 __device__ __forceinline__ Tangent tangent_seed(int kind, int type, V3 u, V3 w, V3 vl, V3 al, V3 acc)
@@ -203,18 +156,7 @@ __global__ __launch_bounds__(64) void k_torque_deriv(const RdynTorqueDerivArgs a
         dqf = dqp[o];
         ddqf = ddqp[o];
       }
-      if (J.type == RDYN_REVOLUTE)
-      {
-        double sn, cs;
-        rdyn_sincos(qf, &sn, &cs);
-        sv0[f] = sn;
-        sv1[f] = 1.0 - cs;
-      }
-      else
-      {
-        sv0[f] = qf;
-        sv1[f] = 0.0;
-      }
+      joint_sincos_state(J.type, qf, sv0[f], sv1[f]);
       dqs[f] = dqf;
       double R[9];
       V3 t;
@@ -309,7 +251,7 @@ __global__ __launch_bounds__(64) void k_torque_deriv(const RdynTorqueDerivArgs a
   }
 
   if (!a.M) return;
-  // ---- M by composite rigid bodies (rdyn_fwd_dyn.hip): needs sin q / 1 - cos q only
+  // ---- M by composite rigid bodies (rdyn_fwd_dyn_body.inc): needs sin q / 1 - cos q only
   if (!want_d)
   {
 #pragma unroll
@@ -318,18 +260,7 @@ __global__ __launch_bounds__(64) void k_torque_deriv(const RdynTorqueDerivArgs a
       JointRef J = c->j[f];
       const int idx = J.in_idx;
       const double qf = idx >= 0 ? qp[idx * a.in_sj] : 0.0;
-      if (J.type == RDYN_REVOLUTE)
-      {
-        double sn, cs;
-        rdyn_sincos(qf, &sn, &cs);
-        sv0[f] = sn;
-        sv1[f] = 1.0 - cs;
-      }
-      else
-      {
-        sv0[f] = qf;
-        sv1[f] = 0.0;
-      }
+      joint_sincos_state(J.type, qf, sv0[f], sv1[f]);
     }
   }
   {
@@ -396,49 +327,13 @@ __global__ __launch_bounds__(64) void k_torque_deriv(const RdynTorqueDerivArgs a
         cN[f] = rot(R, cN[f]) + cross(t, Fp);
         cF[f] = Fp;
       }
-      {
-        // m, h = m c, I about the origin: h' = R h + m t, I' = R I R' + (m |t|^2 + 2 t.hb) 1 - (m t t' + t hb' + hb t'), hb = R h
-        const V3 hb = rot(R, ch);
-        const V3 r0 = mk(R[0], R[1], R[2]), r1 = mk(R[3], R[4], R[5]), r2 = mk(R[6], R[7], R[8]);
-        const V3 c0 = symv(cI, r0), c1 = symv(cI, r1), c2 = symv(cI, r2);
-        const double tr = cm * dot(t, t) + 2.0 * dot(t, hb);
-        cI[0] = dot(r0, c0) + tr - (cm * t.x * t.x + 2.0 * t.x * hb.x);
-        cI[1] = dot(r0, c1) - (cm * t.x * t.y + t.x * hb.y + hb.x * t.y);
-        cI[2] = dot(r0, c2) - (cm * t.x * t.z + t.x * hb.z + hb.x * t.z);
-        cI[3] = dot(r1, c1) + tr - (cm * t.y * t.y + 2.0 * t.y * hb.y);
-        cI[4] = dot(r1, c2) - (cm * t.y * t.z + t.y * hb.z + hb.y * t.z);
-        cI[5] = dot(r2, c2) + tr - (cm * t.z * t.z + 2.0 * t.z * hb.z);
-        ch = axpy(hb, t, cm);
-      }
+      ch = composite_to_parent(R, t, cm, ch, cI);
     }
     if (stg) sm.copy_out(a.M + s_wave * a.m_ss, lane);
   }
 }
 
 // ---- more input joints than the unrolled kernel sweeps ---------------------------------------------------------------------------------
-typedef const RDYN_CONST_AS RdynLongChainConst* LongChainPtr;
-__device__ __forceinline__ LongChainPtr as_const_long(const RdynLongChainConst* p)
-{
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-  return (LongChainPtr)p;
-#pragma clang diagnostic pop
-}
-
-// wave-private per-joint state: value v of joint j of the lane's sample at st[(v * nj + j) * lanes + lane]
-struct JointState
-{
-  double* st;
-  int nj, lanes;
-  __device__ __forceinline__ double& at(int v, int j) const { return st[(v * nj + j) * lanes]; }
-  __device__ __forceinline__ void put3(int v0, int j, V3 x) const
-  {
-    at(v0, j) = x.x;
-    at(v0 + 1, j) = x.y;
-    at(v0 + 2, j) = x.z;
-  }
-  __device__ __forceinline__ V3 get3(int v0, int j) const { return mk(at(v0, j), at(v0 + 1, j), at(v0 + 2, j)); }
-};
 enum { TD_W = 0, TD_VL = 3, TD_AL = 6, TD_AC = 9, TD_FC = 12, TD_NC = 15, TD_S0 = 18, TD_S1 = 19, TD_DQ = 20, TD_DF = 21, TD_DN = 24, TD_VALUES = 27 };
 
 __global__ __launch_bounds__(64) void k_long_torque_deriv(const RdynTorqueDerivArgs a)
@@ -470,14 +365,8 @@ __global__ __launch_bounds__(64) void k_long_torque_deriv(const RdynTorqueDerivA
         dqf = dqp[o];
         ddqf = ddqp[o];
       }
-      double s0 = qf, s1 = 0.0;
-      if (J.type == RDYN_REVOLUTE)
-      {
-        double sn, cs;
-        rdyn_sincos(qf, &sn, &cs);
-        s0 = sn;
-        s1 = 1.0 - cs;
-      }
+      double s0, s1;
+      joint_sincos_state(J.type, qf, s0, s1);
       js.at(TD_S0, f) = s0;
       js.at(TD_S1, f) = s1;
       js.at(TD_DQ, f) = dqf;
@@ -598,21 +487,6 @@ size_t device_lds_limit()
   return (size_t)v;
 }
 
-// more than 64 KB of dynamic LDS needs the attribute, once per device
-hipError_t allow_big_lds(const void* fn, size_t bytes, size_t limit)
-{
-  if (bytes <= 64 * 1024) return hipSuccess;
-  static std::atomic<uint64_t> done;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  const uint64_t bit = 1ull << (dev & 63);
-  if (done.load(std::memory_order_acquire) & bit) return hipSuccess;
-  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)limit);
-  if (e == hipSuccess) done.fetch_or(bit, std::memory_order_release);
-  return e;
-}
-
 template <int NJ>
 hipError_t launch_td_nj(const RdynTorqueDerivArgs& a, hipStream_t st)
 {
@@ -625,20 +499,9 @@ hipError_t launch_td_nj(const RdynTorqueDerivArgs& a, hipStream_t st)
 hipError_t rdyn_launch_torque_derivatives(int n_joints, const RdynTorqueDerivArgs& a, hipStream_t st)
 {
   if (a.n_samples <= 0) return hipSuccess;
-  switch (n_joints)
-  {
-  case 1: return launch_td_nj<1>(a, st);
-  case 2: return launch_td_nj<2>(a, st);
-  case 3: return launch_td_nj<3>(a, st);
-  case 4: return launch_td_nj<4>(a, st);
-  case 5: return launch_td_nj<5>(a, st);
-  case 6: return launch_td_nj<6>(a, st);
-  case 7: return launch_td_nj<7>(a, st);
-  case 8: return launch_td_nj<8>(a, st);
-  case 9: return launch_td_nj<9>(a, st);
-  case 10: return launch_td_nj<10>(a, st);
-  default: return hipErrorInvalidValue;
-  }
+#define CALL(N) launch_td_nj<N>(a, st)
+  RDYN_DISPATCH_NJ(n_joints, CALL)
+#undef CALL
 }
 
 size_t rdyn_long_torque_deriv_lds_bytes(int n_joints, int lanes) { return (size_t)TD_VALUES * n_joints * lanes * sizeof(double); }
@@ -670,8 +533,12 @@ hipError_t rdyn_launch_long_torque_derivatives(int n_joints, const RdynTorqueDer
   const int lanes = rdyn_long_torque_deriv_lanes(n_joints);
   if (lanes == 0) return hipErrorInvalidValue;
   const size_t lds = rdyn_long_torque_deriv_lds_bytes(n_joints, lanes);
-  hipError_t e = allow_big_lds((const void*)k_long_torque_deriv, lds, device_lds_limit());
-  if (e != hipSuccess) return e;
+  if (lds > 64 * 1024)
+  {
+    // the device's own limit, not gfx950's 160 KB: the lane count above was chosen for it
+    hipError_t e = opt_in_lds_once<k_long_torque_deriv>((int)device_lds_limit());
+    if (e != hipSuccess) return e;
+  }
   hipLaunchKernelGGL(k_long_torque_deriv, dim3((unsigned)((a.n_samples + lanes - 1) / lanes)), dim3(lanes), lds, st, a);
   return hipGetLastError();
 }

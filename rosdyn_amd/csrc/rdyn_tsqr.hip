@@ -19,13 +19,13 @@
 // Round 2's first version (lane = column, block re-read from LDS twice per step) ran 8.7 ms at the LDS roofline.
 // fp64 VALU + LDS only (Householder updates are rank-1: nothing for the matrix cores at this width).
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <cstdint>
 #include <utility>
 #include "rdyn_device.h"
 #include "rdyn_devmath.h"
 #include "rdyn_kernels.h"
 #include "rdyn_duo_common.h"
+#include "rdyn_launch_util.h"
 
 #define DUO_BARRIER()  // the link body shared with rdyn_duo_gram.hip synchronises with its consumer wave there; not here
 
@@ -490,22 +490,6 @@ __global__ __launch_bounds__(64) void k_tsqr_combine(const double* __restrict__ 
   store_factor2d<NC>(Rr, out + (int64_t)blockIdx.x * (NC * NC), out_ld, out_cols, lane);  // the last level is one wave: offset 0
 }
 
-template <class K>
-hipError_t opt_in_lds(K kernel, std::atomic<uint64_t>& done)
-{
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(done.load(std::memory_order_acquire) & bit))
-  {
-    e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    done.fetch_or(bit, std::memory_order_release);
-  }
-  return hipSuccess;
-}
-
 // folds `count` NC x NC factors at `slab` down to one, written to R (ld_out x n_out, column-major); scratch = second slab region
 template <int NC>
 hipError_t combine_tree(double* slab, int count, double* scratch, double* R, int n_out, const double* extra, hipStream_t st, int fan = 2,
@@ -532,8 +516,7 @@ hipError_t launch_regressor_tsqr(const RdynLdsGramArgs& a, int blocks, size_t ld
                                  hipStream_t st, int fan)
 {
   constexpr int NC = XC == 0 ? 10 * NJ + 1 : 16 * ((10 * NJ + 1 + 15) / 16 + XC);
-  static std::atomic<uint64_t> attr{0};
-  hipError_t e = opt_in_lds(k_regressor_tsqr<NJ, XC>, attr);
+  hipError_t e = opt_in_lds_once<k_regressor_tsqr<NJ, XC>>();
   if (e != hipSuccess) return e;
   const size_t two_factors = 2 * (((size_t)NC * lds_factor_ld(NC) * 8 + 63) / 64 * 64);
   if (lds_bytes < two_factors) lds_bytes = two_factors;  // the block combine parks two factors side by side
@@ -548,8 +531,7 @@ template <int NC>
 hipError_t launch_tsqr_rows(const double* A, const double* b, int64_t rows, int64_t lda, int n_cols, int blocks, double* slab, double* scratch, double* R,
                             const double* extra, hipStream_t st, const int* run_flag, int fan)
 {
-  static std::atomic<uint64_t> attr{0};
-  hipError_t e = opt_in_lds(k_tsqr_rows<NC>, attr);
+  hipError_t e = opt_in_lds_once<k_tsqr_rows<NC>>();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL((k_tsqr_rows<NC>), dim3(blocks), dim3(256), (size_t)4 * NC * ((64 + 2) * 8), st, A, b, rows, lda, n_cols, slab, run_flag);
   e = hipGetLastError();
@@ -589,16 +571,9 @@ hipError_t rdyn_launch_regressor_tsqr(int n_joints, const RdynLdsGramArgs& a, in
     case 6: return launch_regressor_tsqr<6, 1>(a, blocks, lds_bytes, slab, scratch, R, extra, st, tree_fan);
     default: return hipErrorInvalidValue;
     }
-  switch (n_joints)
-  {
-  case 2: return launch_regressor_tsqr<2, 0>(a, blocks, lds_bytes, slab, scratch, R, extra, st, tree_fan);
-  case 3: return launch_regressor_tsqr<3, 0>(a, blocks, lds_bytes, slab, scratch, R, extra, st, tree_fan);
-  case 4: return launch_regressor_tsqr<4, 0>(a, blocks, lds_bytes, slab, scratch, R, extra, st, tree_fan);
-  case 5: return launch_regressor_tsqr<5, 0>(a, blocks, lds_bytes, slab, scratch, R, extra, st, tree_fan);
-  case 6: return launch_regressor_tsqr<6, 0>(a, blocks, lds_bytes, slab, scratch, R, extra, st, tree_fan);
-  case 7: return launch_regressor_tsqr<7, 0>(a, blocks, lds_bytes, slab, scratch, R, extra, st, tree_fan);
-  default: return hipErrorInvalidValue;
-  }
+#define CALL(N) launch_regressor_tsqr<N, 0>(a, blocks, lds_bytes, slab, scratch, R, extra, st, tree_fan)
+  RDYN_DISPATCH_JOINTS_2_7(n_joints, CALL)
+#undef CALL
 }
 
 hipError_t rdyn_launch_tsqr_rows(const double* A, const double* b, int64_t rows, int64_t lda, int n_cols, int blocks, double* workspace, double* R,

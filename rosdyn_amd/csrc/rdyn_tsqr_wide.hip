@@ -20,12 +20,12 @@
 // robust route: small batches, and the STAND-BY of the preconditioned route of rdyn_cholqr.hip for the shapes rdyn_tsqr.hip does not
 // serve (the device starts it only when that route cannot vouch for its result).  fp64 VALU + LDS only.
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <cstdint>
 #include "rdyn_device.h"
 #include "rdyn_devmath.h"
 #include "rdyn_kernels.h"
 #include "rdyn_duo_common.h"
+#include "rdyn_launch_util.h"
 
 #define DUO_BARRIER()  // the link body shared with rdyn_duo_gram.hip synchronises with its consumer wave there; not here
 
@@ -310,21 +310,6 @@ __global__ __launch_bounds__(NTW) void k_tsqr_wide_rows(const double* __restrict
   store_packed_factor(Rp, out + (int64_t)blockIdx.x * ((int64_t)n1 * n1), n1, tid);
 }
 
-hipError_t opt_in(const void* kernel, std::atomic<uint64_t>& done)
-{
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  const uint64_t bit = 1ull << (dev & 63);
-  if (!(done.load(std::memory_order_acquire) & bit))
-  {
-    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    done.fetch_or(bit, std::memory_order_release);
-  }
-  return hipSuccess;
-}
-
 constexpr size_t kWideLdsBudget = 158 * 1024;
 size_t tri_bytes(int n1) { return (((size_t)n1 * (n1 + 1) / 2) * 8 + 255) & ~(size_t)255; }
 constexpr size_t kPubBytes = 2 * PUB * 8;
@@ -341,8 +326,7 @@ hipError_t wide_tree(const double* in, int count, double* scratch, double* R, in
                      int64_t in_stride = 0)
 {
   int64_t stride = in_stride > 0 ? in_stride : (int64_t)n1 * n1;  // doubles between the factors of the first level
-  static std::atomic<uint64_t> attr{0};
-  hipError_t e = opt_in((const void*)k_tsqr_wide_rows, attr);
+  hipError_t e = opt_in_lds_once<k_tsqr_wide_rows>();
   if (e != hipSuccess) return e;
   const size_t lds = tri_bytes(n1) + kPubBytes;
   // a level costs ceil((fan - 1) n1 / 128) folds of n1 dependent steps each (the first factor is taken as it stands): the widest fan
@@ -383,8 +367,7 @@ hipError_t rdyn_launch_regressor_tsqr_wide(int n_joints, const RdynLdsGramArgs& 
   const int n1 = 10 * n_joints + a.n_comp_cols + 1;
   const size_t lds = rdyn_regressor_tsqr_wide_lds_bytes(n1, a.n_active);
   if (lds == 0 || blocks < 1) return hipErrorInvalidValue;
-  static std::atomic<uint64_t> attr{0};
-  hipError_t e = opt_in((const void*)k_regressor_tsqr_wide, attr);
+  hipError_t e = opt_in_lds_once<k_regressor_tsqr_wide>();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_regressor_tsqr_wide, dim3(blocks), dim3(NTW), lds, st, a, n_joints, n1, workspace);
   e = hipGetLastError();
@@ -406,8 +389,7 @@ hipError_t rdyn_launch_tsqr_wide_rows(const double* A, const double* b, int64_t 
   const int n1 = n_cols + (b ? 1 : 0);
   const int rb = kRowsPerBlock;
   if (n1 < 1 || n1 > rdyn_tsqr_wide_max_cols() || blocks < 1) return hipErrorInvalidValue;
-  static std::atomic<uint64_t> attr{0};
-  hipError_t e = opt_in((const void*)k_tsqr_wide_rows, attr);
+  hipError_t e = opt_in_lds_once<k_tsqr_wide_rows>();
   if (e != hipSuccess) return e;
   // whole blocks per workgroup
   const int64_t n_blk = (rows + rb - 1) / rb;
