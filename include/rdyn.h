@@ -328,9 +328,8 @@ int rdyn_rollout(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_ro
  * NULL and is then not computed; all three NULL with n_samples > 0 is RDYN_ERR_INVALID_ARGUMENT.
  * External wrenches and component (friction / spring) torques are NOT parameters: both are additive in tau, so their derivatives are
  * the caller's to add -- in particular the Dq-derivative of a friction component (diagonal) goes on dtau_dv.
- * Derivatives of the forward dynamics DDq = FD(q, Dq, tau) follow without a second entry point: evaluate this call at
- * DDq = FD(q, Dq, tau) (rdyn_forward_dynamics), then
- *     d DDq / d q = -M^-1 dtau_dq,     d DDq / d Dq = -M^-1 dtau_dv,     d DDq / d tau = M^-1.
+ * Derivatives of the forward dynamics DDq = FD(q, Dq, tau), with or without components, are rdyn_forward_dynamics_derivatives (below,
+ * behind the component types): this call's matrices at DDq = FD(q, Dq, tau) with -M^-1 applied, in one launch.
  * Up to RDYN_MAX_SWEPT_JOINTS input joints (longer chains through their rigid-body reduction): one launch, a forward-mode tangent of
  * the recursive Newton-Euler sweep per input joint, O(n^2) per sample.  More input joints (up to RDYN_MAX_JOINTS, any order): one
  * launch with the per-joint state in LDS for the two derivative matrices, plus the launch of the inertia kernel when M is requested (two
@@ -454,6 +453,40 @@ int rdyn_forward_dynamics_components(const rdyn_chain* chain, const rdyn_batch* 
                                      size_t workspace_bytes);
 int rdyn_rollout_components(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_rollout_desc* desc, const rdyn_component* comps,
                             int n_comps, int64_t chunk_samples, void* workspace, size_t workspace_bytes);
+
+/* Derivatives of the forward dynamics (no reference counterpart): the linearisation of DDq = FD_c(q, Dq, tau).  Per sample, with FD_c the
+ * function of rdyn_forward_dynamics_components for the chain AS CONFIGURED (input-joint selection and order, locked joints, the reduced
+ * companion, gravity; n_comps = 0 is rdyn_forward_dynamics),
+ *     ddq            = FD_c(q, Dq, tau)                                   required; layout of batch->q; may alias tau
+ *     dddq_dq[i][k]  = d DDq_i / d q_k   = -M^-1 (dtau_dq + diag d tau_c / d q)
+ *     dddq_dv[i][k]  = d DDq_i / d Dq_k  = -M^-1 (dtau_dv + diag d tau_c / d Dq)
+ *     minv           = d DDq / d tau     = M^-1, both triangles (the same bits in both)
+ * dtau_dq, dtau_dv the matrices of rdyn_joint_torque_derivatives evaluated at this sample's own ddq.  Each matrix has the record shape
+ * and layouts of rdyn_joint_torque_derivatives (n x n column-major per sample in RDYN_LAYOUT_SAMPLE_MAJOR, x[e][s] with e = i + n k in
+ * RDYN_LAYOUT_ELEMENT_MAJOR, rows and columns in input order), is optional and is not computed when NULL; all three NULL with
+ * n_samples > 0 is RDYN_ERR_INVALID_ARGUMENT.  batch->q and dq are required, batch->ddq is ignored.
+ * Component slopes, with the constants rdyn_components_regressor uses (min_velocity, max_velocity as sanitised there): a spring adds
+ * parameters[0] to d tau_c / d q of its joint.  Friction at x = Dq_j, omega = clamp(x, +-max_velocity): omega' = 1 for |x| < max_velocity,
+ * else 0; sg' = 1 / min_velocity for |omega| < min_velocity, else 0; RDYN_COMP_FRICTION1 adds omega' (p0 sg' + p1), RDYN_COMP_FRICTION2
+ * omega' (p0 sg' + p1 + p2 (2 omega sg + omega^2 sg')) to d tau_c / d Dq.  Several components on one joint add in list order.  EXACTLY AT
+ * A KINK (|x| = max_velocity, |omega| = min_velocity) the slope is the OUTER one-sided one: that of the saturated side.
+ * status (may be NULL) is 1 or -1 by the pivot rule of rdyn_forward_dynamics; a -1 sample gets quiet NaN in ddq and in every matrix
+ * requested; no sample affects another.
+ * Up to RDYN_MAX_SWEPT_JOINTS input joints (longer chains through their rigid-body reduction): ONE launch, one lane per sample; nothing
+ * touches device memory between the inputs and the outputs; the workspace query returns 0.  More input joints: per chunk the chunked
+ * route of rdyn_forward_dynamics, the derivative kernel of rdyn_joint_torque_derivatives at that ddq into the caller's matrices, and one
+ * launch that solves them in place; the workspace is the forward-dynamics image plus one status word per sample of a chunk
+ * (chunk_samples as in rdyn_forward_dynamics; results do not depend on it); RDYN_ERR_UNSUPPORTED where rdyn_joint_torque_derivatives
+ * answers so.
+ * Errors, all RDYN_ERR_INVALID_ARGUMENT before any device work: every argument error of rdyn_forward_dynamics_components with the same
+ * rules for the component list; NULL ddq or tau with samples; all matrices NULL; a workspace smaller than this call's own query.
+ * n_samples = 0 is RDYN_OK.  No allocation, no synchronisation: capturable into a graph once the chain has been used on the device.
+ * A semi-implicit-Euler rollout linearises in one call: feed the T N trajectory records of rdyn_rollout through it as one batch;
+ * A_t, B_t are I + dt (...) of its outputs. */
+size_t rdyn_forward_dynamics_derivatives_workspace_bytes(const rdyn_chain* chain, int64_t chunk_samples);
+int rdyn_forward_dynamics_derivatives(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_component* comps, int n_comps,
+                                      const double* tau, double* ddq, double* dddq_dq, double* dddq_dv, double* minv, int32_t* status,
+                                      int64_t chunk_samples, void* workspace, size_t workspace_bytes);
 
 /* ---- mixed-chain batch (BASELINE.json configs[4]: 256 distinct 6-7-DOF chains x 4 096 samples) --------------
  * One launch per group of chains with equal joint count (and output-layout kind) evaluates rdyn_regressor for MANY

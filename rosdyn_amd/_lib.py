@@ -105,6 +105,8 @@ SYMBOLS = {
     "rdyn_forward_dynamics_components": (_I, [_VP, _BP, _VP, _I, _VP, _VP, _VP, C.c_int64, _VP, C.c_size_t]),
     "rdyn_rollout_components": (_I, [_VP, _BP, C.POINTER(RolloutDesc), _VP, _I, C.c_int64, _VP, C.c_size_t]),
     "rdyn_joint_torque_derivatives": (_I, [_VP, _BP, _VP, _VP, _VP]),
+    "rdyn_forward_dynamics_derivatives_workspace_bytes": (C.c_size_t, [_VP, C.c_int64]),
+    "rdyn_forward_dynamics_derivatives": (_I, [_VP, _BP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP, C.c_size_t]),
     "rdyn_local_ik": (_I, [_VP, _BP, _VP, _DP, C.c_double, _I, _VP, _VP, _VP]),
     "rdyn_local_ik_damped": (_I, [_VP, _BP, _VP, _DP, C.c_double, C.c_double, _I, _VP, _VP, _VP]),
     "rdyn_frame_distance": (_I, [C.c_int64, _VP, _VP, _I, _I, _VP, _VP, _I, _VP]),

@@ -456,6 +456,35 @@ class Chain(object):
         check(lib().rdyn_joint_torque_derivatives(self._h, C.byref(b), *ptr))
         return res[names[0]] if single else tuple(res[k] for k in names)
 
+    def getJointAccelerationDerivatives(self, q, Dq, tau, layout="sample", want=("dq", "dv", "dtau"), out=None, components=None,
+                                        chunk_samples=0, workspace=None):
+        """Derivatives of getJointAcceleration (include/rdyn.h: rdyn_forward_dynamics_derivatives; no reference counterpart).  want: any
+        non-empty selection of "dq" (d DDq / d q), "dv" (d DDq / d Dq) and "dtau" (d DDq / d tau = the inverse of getJointInertia); returns
+        (DDq, status, *wanted) with the matrices in the order of `want` (a single name may be given as a string).  DDq and status are
+        getJointAcceleration's (components included); a sample with status -1 is NaN everywhere.  Records as getJointTorqueDerivatives':
+        (N, n, n) with t[s, k, i] = d DDq_i / d x_k for layout="sample", (n, n, N) with t[k, i, s] for "element".
+        out: None, or a dict name -> preallocated tensor; the key "ddq" names DDq, which may be tau itself."""
+        single = isinstance(want, str)
+        names = (want,) if single else tuple(want)
+        if not names or len(set(names)) != len(names) or any(k not in ("dq", "dv", "dtau") for k in names):
+            raise ValueError('want must be a non-empty selection of "dq", "dv", "dtau"')
+        torch = _torch()
+        b, N, lay = self._batch(layout, q, Dq, tau)
+        b.ddq = None
+        n = self.getActiveJointsNumber()
+        DDq = self._out(q, N, lay, (n,), (out or {}).get("ddq"))
+        res = {k: self._out(q, N, lay, (n, n), (out or {}).get(k)) for k in names}
+        ptr = [res[k].data_ptr() if k in res else None for k in ("dq", "dv", "dtau")]
+        status = torch.empty((N,), dtype=torch.int32, device=q.device)
+        nbytes = lib().rdyn_forward_dynamics_derivatives_workspace_bytes(self._h, chunk_samples)
+        if workspace is None and nbytes > 0:
+            workspace = torch.empty((nbytes,), dtype=torch.uint8, device=q.device)
+        ws = (workspace.data_ptr() if workspace is not None else None, workspace.numel() if workspace is not None else 0)
+        comps, n_comps = self._component_list(components) if components is not None else (None, 0)
+        check(lib().rdyn_forward_dynamics_derivatives(self._h, C.byref(b), comps, n_comps, tau.data_ptr(), DDq.data_ptr(), *ptr,
+                                                      status.data_ptr(), chunk_samples, *ws))
+        return (DDq, status) + tuple(res[k] for k in names)
+
     def getRegressor(self, q, Dq, DDq, layout="sample", y_layout=None, out=None, tau_out=None, with_torque=False):
         """Regressor (and optionally the fused joint torque).
 

@@ -964,6 +964,149 @@ int rdyn_joint_torque_derivatives(const rdyn_chain* c, const rdyn_batch* b, doub
   return RDYN_OK;
 }
 
+// ---- derivatives of the forward dynamics: dDDq/dq, dDDq/dDq, M^-1 (rdyn_fwd_dyn_deriv.hip) ----------------------
+// Chains the unrolled kernels sweep (long ones through their reduced companion): one launch, no workspace.  More input joints: per chunk
+// the pass of the chunked forward dynamics (it leaves the factor of M in the image and ddq), k_long_torque_deriv at that ddq straight
+// into the caller's matrices, k_fwd_solve_columns on them in place.  Behind the image the workspace holds the chunk's status words (the
+// caller's status may be null; the column kernel needs them).
+static size_t fwd_dyn_deriv_status_bytes(const rdyn_chain* c, int64_t chunk_samples)
+{
+  return ((size_t)fwd_dyn_chunk(c, chunk_samples) * sizeof(int32_t) + 255) & ~(size_t)255;
+}
+
+size_t rdyn_forward_dynamics_derivatives_workspace_bytes(const rdyn_chain* c, int64_t chunk_samples)
+{
+  const size_t image = rdyn_forward_dynamics_workspace_bytes(c, chunk_samples);
+  return image ? image + fwd_dyn_deriv_status_bytes(c, chunk_samples) : 0;
+}
+
+int rdyn_forward_dynamics_derivatives(const rdyn_chain* c, const rdyn_batch* b, const rdyn_component* comps, int n_comps, const double* tau,
+                                      double* ddq, double* dddq_dq, double* dddq_dv, double* minv, int32_t* status, int64_t chunk_samples,
+                                      void* workspace, size_t workspace_bytes)
+{
+  const char* const who = "rdyn_forward_dynamics_derivatives";
+  int st = check_batch(c, b, true, false, who, LONG_KERNELS);
+  if (st != RDYN_OK) return st;
+  if (b->n_samples > 0 && (!tau || !ddq))
+  {
+    rdyn_set_error("%s: null torque or acceleration pointer", who);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  if (b->n_samples > 0 && !dddq_dq && !dddq_dv && !minv)
+  {
+    rdyn_set_error("%s: every matrix output is null", who);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  if (chunk_samples < 0)
+  {
+    rdyn_set_error("%s: negative chunk_samples", who);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  const size_t need = rdyn_forward_dynamics_derivatives_workspace_bytes(c, chunk_samples);
+  if (b->n_samples > 0 && need > 0 && (!workspace || workspace_bytes < need))
+  {
+    rdyn_set_error("%s: workspace too small (%zu < %zu bytes)", who, workspace ? workspace_bytes : (size_t)0, need);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  RdynComponentTable table;
+  st = fill_component_table(comps, n_comps, c->n_active(), who, &table);
+  if (st != RDYN_OK) return st;
+  if (b->n_samples == 0 || c->n_active() < 1) return RDYN_OK;
+  DeviceGuard g;
+  st = g.enter(b->device);
+  if (st != RDYN_OK) return st;
+  hipStream_t stream = (hipStream_t)b->stream;
+  const int n = c->n_active();
+  int64_t in_ss, in_sj, m_ss, m_se;
+  rec_strides(b, n, &in_ss, &in_sj);
+  rec_strides(b, (int64_t)n * n, &m_ss, &m_se);
+  if (!fwd_dyn_by_chunks(c))
+  {
+    const rdyn_chain* const sw = c->long_chain() ? c->reduced.get() : c;
+    RdynFwdDynDerivArgs a;
+    memset(&a, 0, sizeof a);
+    st = device_const(sw, &a.f.chain);
+    if (st != RDYN_OK) return st;
+    a.f.q = b->q;
+    a.f.dq = b->dq;
+    a.f.tau = tau;
+    a.f.ddq = ddq;
+    a.f.status = status;
+    a.f.n_samples = b->n_samples;
+    a.f.in_ss = in_ss;
+    a.f.in_sj = in_sj;
+    a.dddq_dq = dddq_dq;
+    a.dddq_dv = dddq_dv;
+    a.minv = minv;
+    a.m_ss = m_ss;
+    a.m_se = m_se;
+    a.staged = (b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(dddq_dq, dddq_dv, minv) && !probe_env("RDYN_NO_RECORD_STAGING")) ? n * n : 0;
+    a.t = table;
+    RDYN_HIP_TRY(rdyn_launch_forward_dynamics_derivatives(sw->n_joints(), a, stream));
+    return RDYN_OK;
+  }
+  if ((dddq_dq || dddq_dv) && rdyn_long_torque_deriv_lanes(c->n_joints()) == 0)
+  {
+    rdyn_set_error("%s: the per-joint state of a chain of %d joints (%zu bytes for 16 samples) exceeds the LDS a workgroup may use on this "
+                   "device",
+                   who, c->n_joints(), rdyn_long_torque_deriv_lds_bytes(c->n_joints(), 16));
+    return RDYN_ERR_UNSUPPORTED;
+  }
+  const int64_t chunk = fwd_dyn_chunk(c, chunk_samples);
+  double* const image = (double*)workspace;
+  int32_t* const st_chunk = (int32_t*)((char*)workspace + rdyn_forward_dynamics_workspace_bytes(c, chunk_samples));
+  RdynTorqueDerivArgs ta;
+  memset(&ta, 0, sizeof ta);
+  if (dddq_dq || dddq_dv)
+  {
+    st = device_const_long(c, &ta.chain_long);
+    if (st != RDYN_OK) return st;
+  }
+  for (int64_t s0 = 0; s0 < b->n_samples; s0 += chunk)
+  {
+    const int64_t cnt = (b->n_samples - s0 < chunk) ? b->n_samples - s0 : chunk;
+    const double* const q = b->q + s0 * in_ss;
+    const double* const dq = b->dq + s0 * in_ss;
+    double* const ddq_c = ddq + s0 * in_ss;
+    int32_t* const st_c = status ? status + s0 : st_chunk;
+    st = fwd_dyn_chunks(c, q, dq, tau + s0 * in_ss, ddq_c, st_c, cnt, in_ss, in_sj, chunk, image, stream, n_comps ? &table : nullptr);
+    if (st != RDYN_OK) return st;
+    if (dddq_dq || dddq_dv)
+    {
+      ta.q = q;
+      ta.dq = dq;
+      ta.ddq = ddq_c;
+      ta.n_samples = cnt;
+      ta.in_ss = in_ss;
+      ta.in_sj = in_sj;
+      ta.dtau_dq = dddq_dq ? dddq_dq + s0 * m_ss : nullptr;
+      ta.dtau_dv = dddq_dv ? dddq_dv + s0 * m_ss : nullptr;
+      ta.m_ss = m_ss;
+      ta.m_se = m_se;
+      RDYN_HIP_TRY(rdyn_launch_long_torque_derivatives(c->n_joints(), ta, stream));
+    }
+    RdynFwdSolveColumnsArgs ca;
+    memset(&ca, 0, sizeof ca);
+    ca.image = image;
+    ca.ld = cnt;
+    ca.n = n;
+    ca.status = st_c;
+    ca.q = q;
+    ca.dq = dq;
+    ca.n_samples = cnt;
+    ca.in_ss = in_ss;
+    ca.in_sj = in_sj;
+    ca.dddq_dq = dddq_dq ? dddq_dq + s0 * m_ss : nullptr;
+    ca.dddq_dv = dddq_dv ? dddq_dv + s0 * m_ss : nullptr;
+    ca.minv = minv ? minv + s0 * m_ss : nullptr;
+    ca.m_ss = m_ss;
+    ca.m_se = m_se;
+    ca.t = table;
+    RDYN_HIP_TRY(rdyn_launch_forward_solve_columns(ca, stream));
+  }
+  return RDYN_OK;
+}
+
 static int run_base(const rdyn_chain* c, const rdyn_batch* b, double* T_bt, double* T_links, double* J, double* tw, double* dtw,
                     int j_link = -1)
 {

@@ -540,6 +540,35 @@ struct RdynFwdSolveCompArgs
   RdynComponentTable t;
 };
 hipError_t rdyn_launch_forward_solve_components(const RdynFwdSolveCompArgs& a, hipStream_t st);
+// derivatives of the forward dynamics (rdyn_fwd_dyn_deriv.hip): ddq = FD_c(q, dq, tau) as rdyn_launch_forward_dynamics_components computes
+// it (f.staged is not used: ddq leaves by 8-byte stores), and dddq_dq = -M^-1 (dtau_dq + d tau_c / d q), dddq_dv = -M^-1 (dtau_dv +
+// d tau_c / d dq), minv = M^-1 at that ddq: n x n per sample, element e = i + n k of sample s at X[s * m_ss + e * m_se]; any matrix may be
+// null (not all three)
+struct RdynFwdDynDerivArgs
+{
+  RdynFwdDynArgs f;
+  double *dddq_dq, *dddq_dv, *minv;
+  int64_t m_ss, m_se;
+  int staged;  // doubles per record (n n): sample-major records through the wave's LDS tile (natural strides, every matrix line-aligned); 0 = 8-byte stores
+  RdynComponentTable t;
+};
+hipError_t rdyn_launch_forward_dynamics_derivatives(int n_joints, const RdynFwdDynDerivArgs& a, hipStream_t st);
+// ... of a chain with more input joints than the unrolled kernels sweep: the chunk image holds the factor k_fwd_solve left (L in the lower
+// triangle, 1 / L_jj on the diagonal); dddq_dq and dddq_dv hold dtau_dq and dtau_dv of the chunk's samples on entry and are solved in
+// place, column by column; minv is written from unit columns.  status = what k_fwd_solve wrote for the chunk (not null).
+struct RdynFwdSolveColumnsArgs
+{
+  const double* image;
+  int64_t ld;
+  int n;
+  const int32_t* status;
+  const double *q, *dq;  // the chunk's first sample
+  int64_t n_samples, in_ss, in_sj;
+  double *dddq_dq, *dddq_dv, *minv;
+  int64_t m_ss, m_se;
+  RdynComponentTable t;
+};
+hipError_t rdyn_launch_forward_solve_columns(const RdynFwdSolveColumnsArgs& a, hipStream_t st);
 struct RdynRolloutCompArgs
 {
   RdynRolloutArgs r;

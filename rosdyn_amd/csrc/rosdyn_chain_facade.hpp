@@ -642,6 +642,53 @@ public:
     std::memcpy(dtau_dDq.data(), m_host.data() + (size_t)n * n, sizeof(double) * n * n);
   }
 
+  // Derivatives of getJointAcceleration (no reference counterpart; include/rdyn.h: rdyn_forward_dynamics_derivatives): returns
+  // DDq = getJointAcceleration(q, Dq, tau) and fills dDDq_dq(i, k) = d DDq_i / d q_k, dDDq_dDq(i, k) = d DDq_i / d Dq_k and
+  // dDDq_dtau = the inverse of getJointInertia(q).  Throws std::runtime_error when the inertia matrix is not positive definite.
+  VectorXd getJointAccelerationDerivatives(const VectorXd& q, const VectorXd& Dq, const VectorXd& tau, MatrixXd& dDDq_dq, MatrixXd& dDDq_dDq,
+                                           MatrixXd& dDDq_dtau)
+  {
+    return jointAccelerationDerivatives(q, Dq, tau, nullptr, dDDq_dq, dDDq_dDq, dDDq_dtau);
+  }
+  // ... with friction and spring components: DDq as getJointAcceleration(q, Dq, tau, comps), the components' slopes on the diagonals
+  VectorXd getJointAccelerationDerivatives(const VectorXd& q, const VectorXd& Dq, const VectorXd& tau, const std::vector<rdyn_component>& comps,
+                                           MatrixXd& dDDq_dq, MatrixXd& dDDq_dDq, MatrixXd& dDDq_dtau)
+  {
+    return jointAccelerationDerivatives(q, Dq, tau, &comps, dDDq_dq, dDDq_dDq, dDDq_dtau);
+  }
+
+private:
+  VectorXd jointAccelerationDerivatives(const VectorXd& q, const VectorXd& Dq, const VectorXd& tau, const std::vector<rdyn_component>* comps,
+                                        MatrixXd& dDDq_dq, MatrixXd& dDDq_dDq, MatrixXd& dDDq_dtau)
+  {
+    if (q.rows() != Dq.rows() || Dq.rows() != tau.rows()) throw std::invalid_argument("Input data dimensions mismatch");
+    const size_t n = m_active_joints_number, nn = n * n;
+    stage(&q, &Dq, &tau);  // tau rides in the DDq slot of the staging buffer
+    // device record after the inputs: DDq (n) | status (int32 in one double) | three matrices | the one-sample workspace of the chunked route
+    const size_t ws_bytes = rdyn_forward_dynamics_derivatives_workspace_bytes(m_h, 1);
+    if (n + 1 + 3 * nn + (ws_bytes + 7) / 8 > m_host.size()) throw std::runtime_error("getJointAccelerationDerivatives: staging buffer too small");
+    int32_t* const flag = reinterpret_cast<int32_t*>(out(n));
+    const double* const d_tau = m_b.ddq;
+    m_b.ddq = nullptr;
+    void* const ws = ws_bytes ? out(n + 1 + 3 * nn) : nullptr;
+    chk(rdyn_forward_dynamics_derivatives(m_h, &m_b, comps ? comps->data() : nullptr, comps ? (int)comps->size() : 0, d_tau, out(0), out(n + 1),
+                                          out(n + 1 + nn), out(n + 1 + 2 * nn), flag, 1, ws, ws_bytes));
+    wait_done();
+    int32_t st;
+    std::memcpy(&st, hout(n), sizeof st);
+    if (st != 1) throw std::runtime_error("getJointAccelerationDerivatives: the joint inertia matrix is not positive definite");
+    VectorXd ddq((int)n);
+    for (size_t i = 0; i < n; ++i) ddq((int)i) = hout(0)[i];
+    MatrixXd* const mats[3] = {&dDDq_dq, &dDDq_dDq, &dDDq_dtau};
+    for (int m = 0; m < 3; ++m)
+    {
+      mats[m]->resize((int)n, (int)n);
+      std::memcpy(mats[m]->data(), hout(n + 1 + (size_t)m * nn), sizeof(double) * nn);
+    }
+    return ddq;
+  }
+
+public:
   // ---- local inverse kinematics (primitives.h:510, 526).  The reference's wall-clock budget `max_time` becomes an
   // iteration cap; returns the reference's bool (false also when the QP of an iterate is not positive definite).
   bool computeLocalIk(VectorXd& sol, const Affine3d& T_b_t, const VectorXd& seed, const double& toll = 1e-4, int max_iterations = 100)
@@ -860,6 +907,19 @@ public:
   void getJointTorqueDerivativesBatch(const rdyn_batch& b, double* dtau_dq, double* dtau_dDq, double* M = nullptr) const
   {
     chk(rdyn_joint_torque_derivatives(m_h, &b, dtau_dq, dtau_dDq, M));
+  }
+  // derivatives of the forward dynamics of a batch (b.q, b.dq; tau, ddq in the layout of b.q, ddq may alias tau; every matrix n x n per
+  // sample, any may be null, not all three; status may be null; comps may be empty): rdyn_forward_dynamics_derivatives
+  size_t getJointAccelerationDerivativesWorkspaceBytes(int64_t chunk_samples = 0) const
+  {
+    return rdyn_forward_dynamics_derivatives_workspace_bytes(m_h, chunk_samples);
+  }
+  void getJointAccelerationDerivativesBatch(const std::vector<rdyn_component>& comps, const rdyn_batch& b, const double* tau, double* ddq,
+                                            double* dDDq_dq, double* dDDq_dDq, double* dDDq_dtau, int32_t* status, int64_t chunk_samples,
+                                            void* workspace, size_t workspace_bytes) const
+  {
+    chk(rdyn_forward_dynamics_derivatives(m_h, &b, comps.empty() ? nullptr : comps.data(), (int)comps.size(), tau, ddq, dDDq_dq, dDDq_dDq, dDDq_dtau,
+                                          status, chunk_samples, workspace, workspace_bytes));
   }
   void getTransformationBatch(const rdyn_batch& b, double* T_bt, double* T_links) const { chk(rdyn_transformation(m_h, &b, T_bt, T_links)); }
   void getJacobianBatch(const rdyn_batch& b, double* J) const { chk(rdyn_jacobian(m_h, &b, J)); }
