@@ -482,11 +482,96 @@ int rdyn_rollout_components(const rdyn_chain* chain, const rdyn_batch* batch, co
  * rules for the component list; NULL ddq or tau with samples; all matrices NULL; a workspace smaller than this call's own query.
  * n_samples = 0 is RDYN_OK.  No allocation, no synchronisation: capturable into a graph once the chain has been used on the device.
  * A semi-implicit-Euler rollout linearises in one call: feed the T N trajectory records of rdyn_rollout through it as one batch;
- * A_t, B_t are I + dt (...) of its outputs. */
+ * A_t, B_t are I + dt (...) of its outputs.  (A gradient through a rollout, either integrator, needs none of the matrices:
+ * rdyn_rollout_adjoint below.) */
 size_t rdyn_forward_dynamics_derivatives_workspace_bytes(const rdyn_chain* chain, int64_t chunk_samples);
 int rdyn_forward_dynamics_derivatives(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_component* comps, int n_comps,
                                       const double* tau, double* ddq, double* dddq_dq, double* dddq_dv, double* minv, int32_t* status,
                                       int64_t chunk_samples, void* workspace, size_t workspace_bytes);
+
+/* Reverse-mode product of the forward dynamics (no reference counterpart): what a gradient needs of the linearisation above, without the
+ * matrices.  Per sample, with FD_c exactly the function of rdyn_forward_dynamics_components for the chain AS CONFIGURED and dddq_dq,
+ * dddq_dv, M^-1 exactly the matrices rdyn_forward_dynamics_derivatives defines (component slopes and the outer-side rule at a kink
+ * included), for a seed ddq_bar on DDq
+ *     q_bar   = dddq_dq' ddq_bar        dq_bar  = dddq_dv' ddq_bar        tau_bar = M^-1 ddq_bar
+ *     ddq     = FD_c(q, Dq, tau)        optional; the bits of rdyn_forward_dynamics_components
+ * All vectors hold n doubles per sample in the layout of batch->q.  Each of q_bar, dq_bar, tau_bar is optional and is not computed when
+ * NULL; all three NULL with n_samples > 0 is RDYN_ERR_INVALID_ARGUMENT.  tau_bar may alias ddq_bar.  batch->q and dq are required,
+ * batch->ddq is ignored.
+ * status (may be NULL) is 1 or -1 by the pivot rule of rdyn_forward_dynamics; a sample with a non-finite entry in q, Dq, tau or ddq_bar
+ * is -1 too.  A -1 sample gets quiet NaN in every output requested; no sample affects another.
+ * Up to RDYN_MAX_SWEPT_JOINTS input joints (longer chains through their rigid-body reduction): ONE launch, one lane per sample, ONE pair of
+ * triangular solves per sample (w = M^-1 ddq_bar, with the factor still in registers) where the derivative call needs 3 n, and every
+ * column of dtau / d(q, Dq) collapses into its dot product with w while its rows appear: 4 n doubles in, at most 4 n out, no n x n object
+ * anywhere; the workspace query returns 0.  More input joints (up to RDYN_MAX_JOINTS, any order): CORRECT, NOT FAST -- per chunk the
+ * chunked rdyn_forward_dynamics_derivatives into element-major matrices in the workspace and one launch that forms the three
+ * transposed products; the workspace is that call's plus (3 n n + n) doubles per sample of a chunk (chunk_samples as in
+ * rdyn_forward_dynamics; results do not depend on it); RDYN_ERR_UNSUPPORTED where rdyn_joint_torque_derivatives answers so.
+ * Errors, all RDYN_ERR_INVALID_ARGUMENT before any device work: every argument error of rdyn_forward_dynamics_components with the same
+ * rules for the component list (its ddq is optional here); NULL tau or ddq_bar with samples; all three products NULL; a negative
+ * chunk_samples; a workspace smaller than this call's own query.  n_samples = 0 is RDYN_OK.  No allocation, no synchronisation:
+ * capturable into a graph once the chain has been used on the device. */
+size_t rdyn_forward_dynamics_vjp_workspace_bytes(const rdyn_chain* chain, int64_t chunk_samples);
+int rdyn_forward_dynamics_vjp(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_component* comps, int n_comps, const double* tau,
+                              const double* ddq_bar, double* q_bar, double* dq_bar, double* tau_bar, double* ddq, int32_t* status,
+                              int64_t chunk_samples, void* workspace, size_t workspace_bytes);
+
+/* Adjoint of a rollout (no reference counterpart): the exact transpose of the discrete scheme rdyn_rollout / rdyn_rollout_components
+ * implement, backwards over the whole horizon -- both integrators; the RK4 stage states are rebuilt inside.  (The forward-mode recipe at
+ * the end of rdyn_forward_dynamics_derivatives' comment still holds for semi-implicit Euler; this call replaces it where a gradient,
+ * not the matrices A_t, B_t, is wanted.)  With x_t = (q_t, Dq_t), x_0 = the batch's q, dq and T = n_steps:
+ *     lambda_T = g_end + g_traj[T - 1]
+ *     for t = T - 1 .. 0:   (lambda_t, gtau_t) = step'(x_t, tau_t; lambda_{t + 1});   for t >= 1: lambda_t += g_traj[t - 1]
+ *     gq0, gdq0 = lambda_0
+ * T = 1 reads no trajectory; T = 0 copies the end seeds to gq0, gdq0.  With vjp(q, v, tau; a_bar) -> (q_bar, v_bar, tau_bar) the product
+ * of rdyn_forward_dynamics_vjp, the step transposes are, in this order,
+ *   semi-implicit Euler (v' = v + dt a, q' = q + dt v'):   lv* = lv' + dt lq';   mu = dt lv*;   (q_bar, v_bar, tau_bar) = vjp(x_t, tau_t; mu);
+ *       lq = lq' + q_bar;   lv = lv* + v_bar;   gtau_t = tau_bar
+ *   RK4:   the stage states X1 .. X4 from x_t as the forward call builds them (three plain evaluations);   kq_i = dt b_i lq',
+ *       kv_i = dt b_i lv' with b = 1/6, 1/3, 1/3, 1/6;   x_bar = lambda';   for i = 4, 3, 2, 1:   (q_bar, v_bar, tau_bar) = vjp(X_i, tau_t; kv_i),
+ *       X_bar_i = (q_bar, kq_i + v_bar),   gtau_t += tau_bar,   x_bar += X_bar_i,   for i > 1: k_{i-1} += c_i X_bar_i with c = ., dt/2, dt/2, dt;
+ *       lambda_t = x_bar.
+ * Component torques and their slopes are taken at each stage's own state, as in the forward call.
+ * status (may be NULL): -1 if any evaluation of the sample fails the pivot rule or meets a non-finite value; from that backward step on
+ * every output of the sample is quiet NaN (gtau of the later steps, already written, stays).  A sample whose forward rollout reported
+ * -1 has NaN records and is NaN in every gradient output.
+ * Split horizons: with gtau_step_stride >= n N a horizon split anywhere into two chained calls -- the later part's gq0, gdq0 are the
+ * earlier part's end seeds -- gives bitwise the single call's result, running seeds or not.  gtau_step_stride = 0 (the sum over the
+ * steps) is for a single call.
+ * Up to RDYN_MAX_SWEPT_JOINTS input joints (longer chains through their rigid-body reduction): ONE launch for the horizon, lambda in
+ * registers between the steps; the workspace query returns 0.  More input joints: CORRECT, NOT FAST -- a host loop over steps and
+ * stages on the batch's stream (the chunked product above, the chunked forward dynamics for the RK4 stage rebuild, one element-wise
+ * kernel); state, stage and seed buffers live in the workspace behind the images; results do not depend on chunk_samples;
+ * RDYN_ERR_UNSUPPORTED where rdyn_joint_torque_derivatives answers so.
+ * Errors, all RDYN_ERR_INVALID_ARGUMENT before any device work: a NULL descriptor; the forward call's errors for n_steps, dt,
+ * integrator and tau; a NULL trajectory pointer with T >= 2; traj_step_stride (T >= 2), gtraj_step_stride (with running seeds) or a
+ * non-zero gtau_step_stride (with gtau) below n N; gq0, gdq0 and gtau all NULL with samples; the component-list rules; a negative
+ * chunk_samples; a workspace smaller than the query's answer.  n_samples = 0 is RDYN_OK.  No allocation, no synchronisation: capturable
+ * into a graph once the chain has been used on the device. */
+typedef struct rdyn_rollout_adjoint_desc
+{
+  int32_t n_steps, integrator;       /* as in the forward call                                                                  */
+  double dt;
+  const double* tau;                 /* the forward call's torques                                                              */
+  int64_t tau_step_stride;
+  const double* q_traj;              /* the forward call's trajectory with traj_every = 1: record k = x_{k+1}; records           */
+  const double* dq_traj;             /*   0 .. T - 2 are read                                                                   */
+  int64_t traj_step_stride;
+  const double* gq_end;              /* dL/dx_T; each may be NULL (= 0)                                                         */
+  const double* gdq_end;
+  const double* gq_traj;             /* optional running seeds: record k = dL/dx_{k+1}, k < T                                   */
+  const double* gdq_traj;
+  int64_t gtraj_step_stride;
+  double* gq0;                       /* dL/dx_0; each may be NULL; may alias gq_end / gdq_end                                   */
+  double* gdq0;
+  double* gtau;                      /* may be NULL; step t at + t * gtau_step_stride (>= n N), 0 = the sum over the steps      */
+  int64_t gtau_step_stride;
+  int32_t* status;                   /* may be NULL                                                                             */
+} rdyn_rollout_adjoint_desc;
+size_t rdyn_rollout_adjoint_workspace_bytes(const rdyn_chain* chain, const rdyn_rollout_adjoint_desc* desc, int64_t n_samples,
+                                            int64_t chunk_samples);
+int rdyn_rollout_adjoint(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_rollout_adjoint_desc* desc,
+                         const rdyn_component* comps, int n_comps, int64_t chunk_samples, void* workspace, size_t workspace_bytes);
 
 /* ---- mixed-chain batch (BASELINE.json configs[4]: 256 distinct 6-7-DOF chains x 4 096 samples) --------------
  * One launch per group of chains with equal joint count (and output-layout kind) evaluates rdyn_regressor for MANY

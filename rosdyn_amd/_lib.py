@@ -32,6 +32,14 @@ class RolloutDesc(C.Structure):
                 ("traj_step_stride", C.c_int64), ("traj_every", C.c_int32), ("status", C.c_void_p)]
 
 
+class RolloutAdjointDesc(C.Structure):
+    _fields_ = [("n_steps", C.c_int32), ("integrator", C.c_int32), ("dt", C.c_double), ("tau", C.c_void_p), ("tau_step_stride", C.c_int64),
+                ("q_traj", C.c_void_p), ("dq_traj", C.c_void_p), ("traj_step_stride", C.c_int64),
+                ("gq_end", C.c_void_p), ("gdq_end", C.c_void_p), ("gq_traj", C.c_void_p), ("gdq_traj", C.c_void_p),
+                ("gtraj_step_stride", C.c_int64), ("gq0", C.c_void_p), ("gdq0", C.c_void_p), ("gtau", C.c_void_p),
+                ("gtau_step_stride", C.c_int64), ("status", C.c_void_p)]
+
+
 INTEGRATORS = {"semi_implicit_euler": 0, "euler": 0, "rk4": 1}
 
 
@@ -107,6 +115,10 @@ SYMBOLS = {
     "rdyn_joint_torque_derivatives": (_I, [_VP, _BP, _VP, _VP, _VP]),
     "rdyn_forward_dynamics_derivatives_workspace_bytes": (C.c_size_t, [_VP, C.c_int64]),
     "rdyn_forward_dynamics_derivatives": (_I, [_VP, _BP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP, C.c_size_t]),
+    "rdyn_forward_dynamics_vjp_workspace_bytes": (C.c_size_t, [_VP, C.c_int64]),
+    "rdyn_forward_dynamics_vjp": (_I, [_VP, _BP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP, C.c_size_t]),
+    "rdyn_rollout_adjoint_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(RolloutAdjointDesc), C.c_int64, C.c_int64]),
+    "rdyn_rollout_adjoint": (_I, [_VP, _BP, C.POINTER(RolloutAdjointDesc), _VP, _I, C.c_int64, _VP, C.c_size_t]),
     "rdyn_local_ik": (_I, [_VP, _BP, _VP, _DP, C.c_double, _I, _VP, _VP, _VP]),
     "rdyn_local_ik_damped": (_I, [_VP, _BP, _VP, _DP, C.c_double, C.c_double, _I, _VP, _VP, _VP]),
     "rdyn_frame_distance": (_I, [C.c_int64, _VP, _VP, _I, _I, _VP, _VP, _I, _VP]),

@@ -485,6 +485,108 @@ class Chain(object):
                                                       status.data_ptr(), chunk_samples, *ws))
         return (DDq, status) + tuple(res[k] for k in names)
 
+    def getJointAccelerationVjp(self, q, Dq, tau, DDq_bar, layout="sample", want=("q", "dq", "tau"), components=None, out=None,
+                                chunk_samples=0, workspace=None):
+        """Reverse-mode product of getJointAcceleration (include/rdyn.h: rdyn_forward_dynamics_vjp; no reference counterpart): for the seed
+        DDq_bar on DDq, "q" -> (d DDq / d q)' DDq_bar, "dq" -> (d DDq / d Dq)' DDq_bar, "tau" -> M^-1 DDq_bar, the matrices those of
+        getJointAccelerationDerivatives (components and their slopes included) -- never formed.  want: a selection with at least one of the
+        three; "ddq" may be added and names DDq itself (getJointAcceleration's bits).  Returns (status, *wanted) in the order of `want` (a
+        single name may be given as a string); every vector is shaped like q.  status (N,) int32: 1, or -1 (the inertia matrix is not
+        positive definite, or q, Dq, tau or DDq_bar of the sample is not finite): that sample is NaN in every output.
+        out: None, or a dict name -> preallocated tensor; out["tau"] may be DDq_bar itself."""
+        single = isinstance(want, str)
+        names = (want,) if single else tuple(want)
+        if (not names or len(set(names)) != len(names) or any(k not in ("q", "dq", "tau", "ddq") for k in names)
+                or not any(k != "ddq" for k in names)):
+            raise ValueError('want must be a selection of "q", "dq", "tau" (at least one) and "ddq"')
+        torch = _torch()
+        b, N, lay = self._batch(layout, q, Dq, tau)
+        b.ddq = None
+        if (DDq_bar.shape != q.shape or DDq_bar.dtype != torch.float64 or not DDq_bar.is_cuda or not DDq_bar.is_contiguous()
+                or DDq_bar.device != q.device):
+            raise ValueError("Input data dimensions mismatch")
+        n = self.getActiveJointsNumber()
+        res = {k: self._out(q, N, lay, (n,), (out or {}).get(k)) for k in names}
+        ptr = [res[k].data_ptr() if k in res else None for k in ("q", "dq", "tau", "ddq")]
+        status = torch.empty((N,), dtype=torch.int32, device=q.device)
+        nbytes = lib().rdyn_forward_dynamics_vjp_workspace_bytes(self._h, chunk_samples)
+        if workspace is None and nbytes > 0:
+            workspace = torch.empty((nbytes,), dtype=torch.uint8, device=q.device)
+        ws = (workspace.data_ptr() if workspace is not None else None, workspace.numel() if workspace is not None else 0)
+        comps, n_comps = self._component_list(components) if components is not None else (None, 0)
+        check(lib().rdyn_forward_dynamics_vjp(self._h, C.byref(b), comps, n_comps, tau.data_ptr(), DDq_bar.data_ptr(), *ptr,
+                                              status.data_ptr(), chunk_samples, *ws))
+        return (status,) + tuple(res[k] for k in names)
+
+    def rolloutAdjoint(self, q0, Dq0, tau, dt, q_traj, Dq_traj, gq_end=None, gDq_end=None, gq_traj=None, gDq_traj=None, integrator="rk4",
+                       n_steps=None, layout="sample", components=None, sum_tau=False, out=None, chunk_samples=0, workspace=None):
+        """Adjoint of rollout (include/rdyn.h: rdyn_rollout_adjoint; no reference counterpart): the exact transpose of the n_steps
+        integrator steps rollout takes, from the seeds on the end state (gq_end, gDq_end, shaped like q0; None = 0) and, optionally, on
+        every trajectory record (gq_traj, gDq_traj: (>= n_steps,) + q0.shape, record k seeds the state after step k + 1) back to the
+        gradients with respect to (q0, Dq0) and the torques.  q0, Dq0, tau, dt, integrator, n_steps, layout, components: the forward
+        call's, with rollout's shape rules.  q_traj, Dq_traj: that call's trajectory with trajectory_every=1 ((>= n_steps - 1,) + q0.shape;
+        None is allowed for n_steps <= 1).
+        Returns (gq0, gDq0, gtau, status).  gtau: (n_steps,) + q0.shape, one gradient per step, or shaped like q0 with sum_tau=True (the
+        sum over the steps: the gradient of torques held over the whole horizon).  status (N,) int32: 1, or -1 when an evaluation of the
+        sample failed or met a non-finite value -- a sample whose forward rollout reported -1 in particular: NaN in every gradient.
+        out: None, or a dict with any of "gq0", "gDq0", "gtau" -> preallocated tensor; out["gq0"] / out["gDq0"] may be gq_end / gDq_end."""
+        torch = _torch()
+        b, N, lay = self._batch(layout, q0, Dq0)
+        if integrator not in _lib.INTEGRATORS:
+            raise ValueError("unknown integrator %r" % (integrator,))
+
+        def ok(t, lead=None):
+            return (t.dtype == torch.float64 and t.is_cuda and t.is_contiguous() and t.device == q0.device
+                    and (tuple(t.shape) == tuple(q0.shape) if lead is None
+                         else t.dim() == 3 and tuple(t.shape[1:]) == tuple(q0.shape) and t.shape[0] >= lead))
+
+        if tau.dim() == 3 and ok(tau, 0):
+            stride = q0.numel()
+            if n_steps is None:
+                n_steps = tau.shape[0]
+            elif n_steps > tau.shape[0]:
+                raise ValueError("Input data dimensions mismatch")
+        elif tau.dim() == 2 and ok(tau) and n_steps is not None:
+            stride = 0
+        else:
+            raise ValueError("Input data dimensions mismatch")
+        T = int(n_steps)
+        if T >= 2 and (q_traj is None or Dq_traj is None):
+            raise ValueError("two or more steps need the forward call's trajectory (trajectory_every=1)")
+        for t, lead in ((q_traj, T - 1), (Dq_traj, T - 1), (gq_traj, T), (gDq_traj, T)):
+            if t is not None and not ok(t, max(lead, 0)):
+                raise ValueError("Input data dimensions mismatch")
+        for t in (gq_end, gDq_end):
+            if t is not None and not ok(t):
+                raise ValueError("Input data dimensions mismatch")
+        n = self.getActiveJointsNumber()
+        out = out or {}
+        gq0, gdq0 = self._out(q0, N, lay, (n,), out.get("gq0")), self._out(q0, N, lay, (n,), out.get("gDq0"))
+        gshape = tuple(q0.shape) if sum_tau else (max(T, 0),) + tuple(q0.shape)
+        gtau = out.get("gtau")
+        if gtau is None:
+            gtau = torch.empty(gshape, dtype=torch.float64, device=q0.device)
+        elif tuple(gtau.shape) != gshape or gtau.dtype != torch.float64 or not gtau.is_contiguous() or gtau.device != q0.device:
+            raise ValueError("out['gtau'] must be a contiguous float64 tensor of shape %s" % (gshape,))
+        status = torch.empty((N,), dtype=torch.int32, device=q0.device)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() > 0 else None
+        d = _lib.RolloutAdjointDesc()
+        d.n_steps, d.integrator, d.dt = T, _lib.INTEGRATORS[integrator], float(dt)
+        d.tau, d.tau_step_stride = tau.data_ptr(), stride
+        d.q_traj, d.dq_traj, d.traj_step_stride = ptr(q_traj), ptr(Dq_traj), q0.numel()
+        d.gq_end, d.gdq_end = ptr(gq_end), ptr(gDq_end)
+        d.gq_traj, d.gdq_traj, d.gtraj_step_stride = ptr(gq_traj), ptr(gDq_traj), q0.numel()
+        d.gq0, d.gdq0 = gq0.data_ptr(), gdq0.data_ptr()
+        d.gtau, d.gtau_step_stride = ptr(gtau), 0 if sum_tau else q0.numel()
+        d.status = status.data_ptr()
+        nbytes = lib().rdyn_rollout_adjoint_workspace_bytes(self._h, C.byref(d), N, chunk_samples)
+        if workspace is None and nbytes > 0:
+            workspace = torch.empty((nbytes,), dtype=torch.uint8, device=q0.device)
+        ws = (workspace.data_ptr() if workspace is not None else None, workspace.numel() if workspace is not None else 0)
+        comps, n_comps = self._component_list(components) if components is not None else (None, 0)
+        check(lib().rdyn_rollout_adjoint(self._h, C.byref(b), C.byref(d), comps, n_comps, chunk_samples, *ws))
+        return gq0, gdq0, gtau, status
+
     def getRegressor(self, q, Dq, DDq, layout="sample", y_layout=None, out=None, tau_out=None, with_torque=False):
         """Regressor (and optionally the fused joint torque).
 

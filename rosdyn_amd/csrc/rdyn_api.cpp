@@ -974,6 +974,67 @@ static size_t fwd_dyn_deriv_status_bytes(const rdyn_chain* c, int64_t chunk_samp
   return ((size_t)fwd_dyn_chunk(c, chunk_samples) * sizeof(int32_t) + 255) & ~(size_t)255;
 }
 
+// the chunked route of rdyn_forward_dynamics_derivatives over n_samples samples (status may be null: st_chunk, one word per sample of a
+// chunk, stands in; comps null = no components)
+static int fwd_dyn_deriv_chunks(const rdyn_chain* c, const double* q_all, const double* dq_all, const double* tau, double* ddq, double* dddq_dq,
+                                double* dddq_dv, double* minv, int32_t* status, int32_t* st_chunk, int64_t n_samples, int64_t in_ss,
+                                int64_t in_sj, int64_t m_ss, int64_t m_se, int64_t chunk, double* image, const RdynComponentTable* comps,
+                                hipStream_t stream)
+{
+  const int n = c->n_active();
+  int st;
+  RdynTorqueDerivArgs ta;
+  memset(&ta, 0, sizeof ta);
+  if (dddq_dq || dddq_dv)
+  {
+    st = device_const_long(c, &ta.chain_long);
+    if (st != RDYN_OK) return st;
+  }
+  for (int64_t s0 = 0; s0 < n_samples; s0 += chunk)
+  {
+    const int64_t cnt = (n_samples - s0 < chunk) ? n_samples - s0 : chunk;
+    const double* const q = q_all + s0 * in_ss;
+    const double* const dq = dq_all + s0 * in_ss;
+    double* const ddq_c = ddq + s0 * in_ss;
+    int32_t* const st_c = status ? status + s0 : st_chunk;
+    st = fwd_dyn_chunks(c, q, dq, tau + s0 * in_ss, ddq_c, st_c, cnt, in_ss, in_sj, chunk, image, stream, comps);
+    if (st != RDYN_OK) return st;
+    if (dddq_dq || dddq_dv)
+    {
+      ta.q = q;
+      ta.dq = dq;
+      ta.ddq = ddq_c;
+      ta.n_samples = cnt;
+      ta.in_ss = in_ss;
+      ta.in_sj = in_sj;
+      ta.dtau_dq = dddq_dq ? dddq_dq + s0 * m_ss : nullptr;
+      ta.dtau_dv = dddq_dv ? dddq_dv + s0 * m_ss : nullptr;
+      ta.m_ss = m_ss;
+      ta.m_se = m_se;
+      RDYN_HIP_TRY(rdyn_launch_long_torque_derivatives(c->n_joints(), ta, stream));
+    }
+    RdynFwdSolveColumnsArgs ca;
+    memset(&ca, 0, sizeof ca);
+    ca.image = image;
+    ca.ld = cnt;
+    ca.n = n;
+    ca.status = st_c;
+    ca.q = q;
+    ca.dq = dq;
+    ca.n_samples = cnt;
+    ca.in_ss = in_ss;
+    ca.in_sj = in_sj;
+    ca.dddq_dq = dddq_dq ? dddq_dq + s0 * m_ss : nullptr;
+    ca.dddq_dv = dddq_dv ? dddq_dv + s0 * m_ss : nullptr;
+    ca.minv = minv ? minv + s0 * m_ss : nullptr;
+    ca.m_ss = m_ss;
+    ca.m_se = m_se;
+    if (comps) ca.t = *comps;
+    RDYN_HIP_TRY(rdyn_launch_forward_solve_columns(ca, stream));
+  }
+  return RDYN_OK;
+}
+
 size_t rdyn_forward_dynamics_derivatives_workspace_bytes(const rdyn_chain* c, int64_t chunk_samples)
 {
   const size_t image = rdyn_forward_dynamics_workspace_bytes(c, chunk_samples);
@@ -1052,59 +1113,9 @@ int rdyn_forward_dynamics_derivatives(const rdyn_chain* c, const rdyn_batch* b, 
                    who, c->n_joints(), rdyn_long_torque_deriv_lds_bytes(c->n_joints(), 16));
     return RDYN_ERR_UNSUPPORTED;
   }
-  const int64_t chunk = fwd_dyn_chunk(c, chunk_samples);
-  double* const image = (double*)workspace;
-  int32_t* const st_chunk = (int32_t*)((char*)workspace + rdyn_forward_dynamics_workspace_bytes(c, chunk_samples));
-  RdynTorqueDerivArgs ta;
-  memset(&ta, 0, sizeof ta);
-  if (dddq_dq || dddq_dv)
-  {
-    st = device_const_long(c, &ta.chain_long);
-    if (st != RDYN_OK) return st;
-  }
-  for (int64_t s0 = 0; s0 < b->n_samples; s0 += chunk)
-  {
-    const int64_t cnt = (b->n_samples - s0 < chunk) ? b->n_samples - s0 : chunk;
-    const double* const q = b->q + s0 * in_ss;
-    const double* const dq = b->dq + s0 * in_ss;
-    double* const ddq_c = ddq + s0 * in_ss;
-    int32_t* const st_c = status ? status + s0 : st_chunk;
-    st = fwd_dyn_chunks(c, q, dq, tau + s0 * in_ss, ddq_c, st_c, cnt, in_ss, in_sj, chunk, image, stream, n_comps ? &table : nullptr);
-    if (st != RDYN_OK) return st;
-    if (dddq_dq || dddq_dv)
-    {
-      ta.q = q;
-      ta.dq = dq;
-      ta.ddq = ddq_c;
-      ta.n_samples = cnt;
-      ta.in_ss = in_ss;
-      ta.in_sj = in_sj;
-      ta.dtau_dq = dddq_dq ? dddq_dq + s0 * m_ss : nullptr;
-      ta.dtau_dv = dddq_dv ? dddq_dv + s0 * m_ss : nullptr;
-      ta.m_ss = m_ss;
-      ta.m_se = m_se;
-      RDYN_HIP_TRY(rdyn_launch_long_torque_derivatives(c->n_joints(), ta, stream));
-    }
-    RdynFwdSolveColumnsArgs ca;
-    memset(&ca, 0, sizeof ca);
-    ca.image = image;
-    ca.ld = cnt;
-    ca.n = n;
-    ca.status = st_c;
-    ca.q = q;
-    ca.dq = dq;
-    ca.n_samples = cnt;
-    ca.in_ss = in_ss;
-    ca.in_sj = in_sj;
-    ca.dddq_dq = dddq_dq ? dddq_dq + s0 * m_ss : nullptr;
-    ca.dddq_dv = dddq_dv ? dddq_dv + s0 * m_ss : nullptr;
-    ca.minv = minv ? minv + s0 * m_ss : nullptr;
-    ca.m_ss = m_ss;
-    ca.m_se = m_se;
-    ca.t = table;
-    RDYN_HIP_TRY(rdyn_launch_forward_solve_columns(ca, stream));
-  }
-  return RDYN_OK;
+  return fwd_dyn_deriv_chunks(c, b->q, b->dq, tau, ddq, dddq_dq, dddq_dv, minv, status,
+                              (int32_t*)((char*)workspace + rdyn_forward_dynamics_workspace_bytes(c, chunk_samples)), b->n_samples, in_ss, in_sj, m_ss,
+                              m_se, fwd_dyn_chunk(c, chunk_samples), (double*)workspace, n_comps ? &table : nullptr, stream);
 }
 
 static int run_base(const rdyn_chain* c, const rdyn_batch* b, double* T_bt, double* T_links, double* J, double* tw, double* dtw,
@@ -1146,6 +1157,388 @@ static int run_base(const rdyn_chain* c, const rdyn_batch* b, double* T_bt, doub
   }
   else
     RDYN_HIP_TRY(rdyn_launch_base_sweep(c->n_joints(), a, (hipStream_t)b->stream));
+  return RDYN_OK;
+}
+
+// ---- reverse-mode product of the forward dynamics (rdyn_fwd_dyn_vjp.hip) -----------------------------------------
+// Chains the unrolled kernels sweep (long ones through their reduced companion): one launch, no workspace.  More input joints: per chunk
+// the chunked route of the derivative call into element-major matrices in the workspace, then k_vjp_products.  Behind the derivative
+// call's own workspace (image, status words): dddq_dq | dddq_dv | minv of one chunk, then the chunk's seeds (copied before the first pass:
+// tau_bar may alias them, and when the caller wants no ddq an output array takes the pass's ddq).
+static size_t vjp_matrix_bytes(const rdyn_chain* c, int64_t chunk_samples)
+{
+  const size_t n = (size_t)c->n_active();
+  return align256((size_t)fwd_dyn_chunk(c, chunk_samples) * n * n * sizeof(double));
+}
+
+size_t rdyn_forward_dynamics_vjp_workspace_bytes(const rdyn_chain* c, int64_t chunk_samples)
+{
+  const size_t base = rdyn_forward_dynamics_derivatives_workspace_bytes(c, chunk_samples);
+  if (!base) return 0;
+  return base + 3 * vjp_matrix_bytes(c, chunk_samples) +
+         align256((size_t)fwd_dyn_chunk(c, chunk_samples) * (size_t)c->n_active() * sizeof(double));
+}
+
+// the chunked route over n_samples samples; at least one of q_bar, dq_bar, tau_bar; status and ddq may be null
+static int vjp_chunks(const rdyn_chain* c, const double* q, const double* dq, const double* tau, const double* ddq_bar, double* q_bar,
+                      double* dq_bar, double* tau_bar, double* ddq, int32_t* status, int64_t n_samples, int64_t in_ss, int64_t in_sj,
+                      int64_t chunk_samples, void* workspace, const RdynComponentTable* comps, hipStream_t stream)
+{
+  const int n = c->n_active();
+  const int64_t chunk = fwd_dyn_chunk(c, chunk_samples);
+  char* p = (char*)workspace;
+  double* const image = (double*)p;
+  p += rdyn_forward_dynamics_workspace_bytes(c, chunk_samples);
+  int32_t* const st_chunk = (int32_t*)p;
+  p += fwd_dyn_deriv_status_bytes(c, chunk_samples);
+  const size_t mb = vjp_matrix_bytes(c, chunk_samples);
+  double* const Dq = (double*)p;
+  double* const Dv = (double*)(p + mb);
+  double* const Mi = (double*)(p + 2 * mb);
+  double* const seed = (double*)(p + 3 * mb);
+  double* const ddq_pass = ddq ? ddq : (q_bar ? q_bar : (dq_bar ? dq_bar : tau_bar));  // (overwritten by the products of the same chunk)
+  for (int64_t s0 = 0; s0 < n_samples; s0 += chunk)
+  {
+    const int64_t cnt = (n_samples - s0 < chunk) ? n_samples - s0 : chunk;
+    const int64_t o = s0 * in_ss;
+    int32_t* const st_c = status ? status + s0 : st_chunk;
+    RDYN_HIP_TRY(rdyn_launch_vjp_seed_copy(ddq_bar + o, seed, n, cnt, cnt, in_ss, in_sj, stream));
+    const int st = fwd_dyn_deriv_chunks(c, q + o, dq + o, tau + o, ddq_pass + o, q_bar ? Dq : nullptr, dq_bar ? Dv : nullptr, tau_bar ? Mi : nullptr,
+                                        st_c, st_chunk, cnt, in_ss, in_sj, 1, cnt, chunk, image, comps, stream);
+    if (st != RDYN_OK) return st;
+    RdynVjpProductArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.dddq_dq = Dq;
+    pa.dddq_dv = Dv;
+    pa.minv = Mi;
+    pa.ld = cnt;
+    pa.n = n;
+    pa.q = q + o;
+    pa.dq = dq + o;
+    pa.tau = tau + o;
+    pa.ddq_bar = seed;
+    pa.seed_ss = 1;
+    pa.seed_sj = cnt;
+    pa.q_bar = q_bar ? q_bar + o : nullptr;
+    pa.dq_bar = dq_bar ? dq_bar + o : nullptr;
+    pa.tau_bar = tau_bar ? tau_bar + o : nullptr;
+    pa.ddq = ddq ? ddq + o : nullptr;
+    pa.status = st_c;
+    pa.n_samples = cnt;
+    pa.in_ss = in_ss;
+    pa.in_sj = in_sj;
+    RDYN_HIP_TRY(rdyn_launch_vjp_products(pa, stream));
+  }
+  return RDYN_OK;
+}
+
+static int vjp_lds_refusal(const rdyn_chain* c, const char* who)
+{
+  if (rdyn_long_torque_deriv_lanes(c->n_joints()) != 0) return RDYN_OK;
+  rdyn_set_error("%s: the per-joint state of a chain of %d joints (%zu bytes for 16 samples) exceeds the LDS a workgroup may use on this device",
+                 who, c->n_joints(), rdyn_long_torque_deriv_lds_bytes(c->n_joints(), 16));
+  return RDYN_ERR_UNSUPPORTED;
+}
+
+int rdyn_forward_dynamics_vjp(const rdyn_chain* c, const rdyn_batch* b, const rdyn_component* comps, int n_comps, const double* tau,
+                              const double* ddq_bar, double* q_bar, double* dq_bar, double* tau_bar, double* ddq, int32_t* status,
+                              int64_t chunk_samples, void* workspace, size_t workspace_bytes)
+{
+  const char* const who = "rdyn_forward_dynamics_vjp";
+  int st = check_batch(c, b, true, false, who, LONG_KERNELS);
+  if (st != RDYN_OK) return st;
+  if (b->n_samples > 0 && (!tau || !ddq_bar))
+  {
+    rdyn_set_error("%s: null torque or seed pointer", who);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  if (b->n_samples > 0 && !q_bar && !dq_bar && !tau_bar)
+  {
+    rdyn_set_error("%s: every product is null", who);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  if (chunk_samples < 0)
+  {
+    rdyn_set_error("%s: negative chunk_samples", who);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  const size_t need = rdyn_forward_dynamics_vjp_workspace_bytes(c, chunk_samples);
+  if (b->n_samples > 0 && need > 0 && (!workspace || workspace_bytes < need))
+  {
+    rdyn_set_error("%s: workspace too small (%zu < %zu bytes)", who, workspace ? workspace_bytes : (size_t)0, need);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  RdynComponentTable table;
+  st = fill_component_table(comps, n_comps, c->n_active(), who, &table);
+  if (st != RDYN_OK) return st;
+  if (b->n_samples == 0 || c->n_active() < 1) return RDYN_OK;
+  DeviceGuard g;
+  st = g.enter(b->device);
+  if (st != RDYN_OK) return st;
+  hipStream_t stream = (hipStream_t)b->stream;
+  const int n = c->n_active();
+  int64_t in_ss, in_sj;
+  rec_strides(b, n, &in_ss, &in_sj);
+  if (!fwd_dyn_by_chunks(c))
+  {
+    const rdyn_chain* const sw = c->long_chain() ? c->reduced.get() : c;
+    RdynFwdDynVjpArgs a;
+    memset(&a, 0, sizeof a);
+    st = device_const(sw, &a.chain);
+    if (st != RDYN_OK) return st;
+    a.q = b->q;
+    a.dq = b->dq;
+    a.tau = tau;
+    a.ddq_bar = ddq_bar;
+    a.q_bar = q_bar;
+    a.dq_bar = dq_bar;
+    a.tau_bar = tau_bar;
+    a.ddq = ddq;
+    a.status = status;
+    a.n_samples = b->n_samples;
+    a.in_ss = in_ss;
+    a.in_sj = in_sj;
+    a.staged = (b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(q_bar, dq_bar, tau_bar, ddq) && !probe_env("RDYN_NO_RECORD_STAGING")) ? n : 0;
+    a.t = table;
+    RDYN_HIP_TRY(rdyn_launch_forward_dynamics_vjp(sw->n_joints(), a, stream));
+    return RDYN_OK;
+  }
+  if (q_bar || dq_bar)
+  {
+    st = vjp_lds_refusal(c, who);
+    if (st != RDYN_OK) return st;
+  }
+  return vjp_chunks(c, b->q, b->dq, tau, ddq_bar, q_bar, dq_bar, tau_bar, ddq, status, b->n_samples, in_ss, in_sj, chunk_samples, workspace,
+                    n_comps ? &table : nullptr, stream);
+}
+
+// ---- adjoint of a rollout (rdyn_rollout_adjoint.hip) ------------------------------------------------------------
+// Chains the unrolled kernels sweep: one launch for the whole horizon.  More input joints: a host loop over steps and stages; behind the
+// workspace of the product the workspace holds, each n N doubles in the batch's layout, lq | lv | mu | qb | vb | tb and for RK4 xq | xv | kq |
+// kv | gt | x2q | x2v | x3q | x3v | x4q | x4v | acc, then two int32 per sample (the pass's status, the running minimum).
+static size_t adjoint_state_arrays(int integrator) { return integrator == RDYN_INTEGRATOR_RK4 ? 18 : 6; }
+
+size_t rdyn_rollout_adjoint_workspace_bytes(const rdyn_chain* c, const rdyn_rollout_adjoint_desc* d, int64_t n_samples, int64_t chunk_samples)
+{
+  if (!c || !d || c->n_active() < 1 || n_samples < 0 || chunk_samples < 0 || !fwd_dyn_by_chunks(c)) return 0;
+  const size_t arr = align256((size_t)n_samples * (size_t)c->n_active() * sizeof(double));
+  return rdyn_forward_dynamics_vjp_workspace_bytes(c, chunk_samples) + adjoint_state_arrays(d->integrator) * arr +
+         2 * align256((size_t)n_samples * sizeof(int32_t));
+}
+
+int rdyn_rollout_adjoint(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_adjoint_desc* d, const rdyn_component* comps, int n_comps,
+                         int64_t chunk_samples, void* workspace, size_t workspace_bytes)
+{
+  const char* const who = "rdyn_rollout_adjoint";
+  int st = check_batch(c, b, true, false, who, LONG_KERNELS);
+  if (st != RDYN_OK) return st;
+  if (!d)
+  {
+    rdyn_set_error("%s: null descriptor", who);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  const int n = c->n_active();
+  const int64_t N = b->n_samples;
+  const int T = d->n_steps;
+  if (T < 0 || !std::isfinite(d->dt) || d->dt == 0.0 ||
+      (d->integrator != RDYN_INTEGRATOR_SEMI_IMPLICIT_EULER && d->integrator != RDYN_INTEGRATOR_RK4))
+  {
+    rdyn_set_error("%s: negative n_steps, a step size that is zero or not finite, or an unknown integrator", who);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  if (T > 0 && !d->tau)
+  {
+    rdyn_set_error("%s: null torque pointer", who);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  if (T >= 2 && (!d->q_traj || !d->dq_traj))
+  {
+    rdyn_set_error("%s: two or more steps need the forward call's trajectory (q_traj and dq_traj, traj_every = 1)", who);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  const int64_t nN = (int64_t)n * N;
+  const bool running = d->gq_traj || d->gdq_traj;
+  if ((T >= 2 && d->traj_step_stride < nN) || (running && d->gtraj_step_stride < nN) ||
+      (d->gtau && d->gtau_step_stride != 0 && d->gtau_step_stride < nN))
+  {
+    rdyn_set_error("%s: traj_step_stride, gtraj_step_stride and a non-zero gtau_step_stride must be >= n * n_samples", who);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  if (N > 0 && !d->gq0 && !d->gdq0 && !d->gtau)
+  {
+    rdyn_set_error("%s: every output is null", who);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  if (chunk_samples < 0)
+  {
+    rdyn_set_error("%s: negative chunk_samples", who);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  const size_t need = rdyn_rollout_adjoint_workspace_bytes(c, d, N, chunk_samples);
+  if (N > 0 && need > 0 && (!workspace || workspace_bytes < need))
+  {
+    rdyn_set_error("%s: workspace too small (%zu < %zu bytes)", who, workspace ? workspace_bytes : (size_t)0, need);
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  RdynComponentTable table;
+  st = fill_component_table(comps, n_comps, n, who, &table);
+  if (st != RDYN_OK) return st;
+  if (N == 0 || n < 1) return RDYN_OK;
+  DeviceGuard g;
+  st = g.enter(b->device);
+  if (st != RDYN_OK) return st;
+  hipStream_t stream = (hipStream_t)b->stream;
+  int64_t in_ss, in_sj;
+  rec_strides(b, n, &in_ss, &in_sj);
+  if (!fwd_dyn_by_chunks(c))
+  {
+    const rdyn_chain* const sw = c->long_chain() ? c->reduced.get() : c;
+    RdynRolloutAdjointArgs a;
+    memset(&a, 0, sizeof a);
+    st = device_const(sw, &a.chain);
+    if (st != RDYN_OK) return st;
+    a.q = b->q;
+    a.dq = b->dq;
+    a.tau = d->tau;
+    a.tau_step = d->tau_step_stride;
+    a.q_traj = d->q_traj;
+    a.dq_traj = d->dq_traj;
+    a.traj_step = d->traj_step_stride;
+    a.gq_end = d->gq_end;
+    a.gdq_end = d->gdq_end;
+    a.gq_traj = d->gq_traj;
+    a.gdq_traj = d->gdq_traj;
+    a.gtraj_step = d->gtraj_step_stride;
+    a.gq0 = d->gq0;
+    a.gdq0 = d->gdq0;
+    a.gtau = d->gtau;
+    a.gtau_step = d->gtau_step_stride;
+    a.status = d->status;
+    a.n_samples = N;
+    a.in_ss = in_ss;
+    a.in_sj = in_sj;
+    a.dt = d->dt;
+    a.n_steps = T;
+    a.integrator = d->integrator;
+    a.n_active = n;
+    if (b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && !probe_env("RDYN_NO_RECORD_STAGING"))
+    {
+      // whole lines: every record of the kind starts on a line (the step stride keeps the alignment of the first record)
+      if ((d->gq0 || d->gdq0) && lines_aligned(d->gq0, d->gdq0)) a.staged |= 1;
+      if (d->gtau && lines_aligned(d->gtau) && (d->gtau_step_stride * (int64_t)sizeof(double)) % 128 == 0) a.staged |= 2;
+    }
+    a.t = table;
+    RDYN_HIP_TRY(rdyn_launch_rollout_adjoint(sw->n_joints(), a, stream));
+    return RDYN_OK;
+  }
+  if (T > 0)
+  {
+    st = vjp_lds_refusal(c, who);
+    if (st != RDYN_OK) return st;
+  }
+  const RdynComponentTable* const tbl = n_comps ? &table : nullptr;
+  const int64_t chunk = fwd_dyn_chunk(c, chunk_samples);
+  const size_t arr = align256((size_t)nN * sizeof(double));
+  char* p = (char*)workspace + rdyn_forward_dynamics_vjp_workspace_bytes(c, chunk_samples);
+  double* ws[18];
+  for (size_t i = 0; i < 18; ++i) ws[i] = nullptr;
+  for (size_t i = 0; i < adjoint_state_arrays(d->integrator); ++i, p += arr) ws[i] = (double*)p;
+  int32_t* const st_stage = (int32_t*)p;
+  int32_t* const st_run = (int32_t*)(p + align256((size_t)N * sizeof(int32_t)));
+  double *const lq = ws[0], *const lv = ws[1], *const mu = ws[2], *const qb = ws[3], *const vb = ws[4], *const tb = ws[5];
+  double* const acc = ws[17];
+  RdynAdjointUpdateArgs u;
+  memset(&u, 0, sizeof u);
+  u.lq = lq;
+  u.lv = lv;
+  u.mv = mu;
+  u.qb = qb;
+  u.vb = vb;
+  u.tb = tb;
+  u.xq = ws[6];
+  u.xv = ws[7];
+  u.kq = ws[8];
+  u.kv = ws[9];
+  u.mq = ws[10];
+  u.st_stage = st_stage;
+  u.st_run = st_run;
+  u.count = nN;
+  u.n_samples = N;
+  u.n = n;
+  u.element_major = b->layout == RDYN_LAYOUT_ELEMENT_MAJOR;
+  u.dt = d->dt;
+  const bool gsum = d->gtau && d->gtau_step_stride == 0;
+  auto update = [&](int op) -> hipError_t {
+    u.op = op;
+    return rdyn_launch_adjoint_update(u, stream);
+  };
+  const int64_t last = (int64_t)(T - 1) * d->gtraj_step_stride;
+  u.a = d->gq_end;
+  u.b = (T > 0 && d->gq_traj) ? d->gq_traj + last : nullptr;
+  u.c = d->gdq_end;
+  u.d = (T > 0 && d->gdq_traj) ? d->gdq_traj + last : nullptr;
+  RDYN_HIP_TRY(update(RDYN_ADJ_OP_INIT));
+  if (gsum)
+  {
+    u.gtau = d->gtau;
+    RDYN_HIP_TRY(update(RDYN_ADJ_OP_ZERO));
+  }
+  for (int t = T - 1; t >= 0; --t)
+  {
+    const double* const xq_t = t == 0 ? b->q : d->q_traj + (int64_t)(t - 1) * d->traj_step_stride;
+    const double* const xv_t = t == 0 ? b->dq : d->dq_traj + (int64_t)(t - 1) * d->traj_step_stride;
+    const double* const tau_t = d->tau + (int64_t)t * d->tau_step_stride;
+    u.gtau = d->gtau ? d->gtau + (int64_t)t * d->gtau_step_stride : nullptr;
+    u.gtau_add = gsum;
+    if (d->integrator == RDYN_INTEGRATOR_SEMI_IMPLICIT_EULER)
+    {
+      RDYN_HIP_TRY(update(RDYN_ADJ_OP_EULER_PRE));
+      st = vjp_chunks(c, xq_t, xv_t, tau_t, mu, qb, vb, tb, nullptr, st_stage, N, in_ss, in_sj, chunk_samples, workspace, tbl, stream);
+      if (st != RDYN_OK) return st;
+      RDYN_HIP_TRY(update(RDYN_ADJ_OP_EULER_POST));
+    }
+    else
+    {
+      // the stage states X2 .. X4 (X1 = x_t): ws[11 + 2 (i - 2)], ws[12 + 2 (i - 2)]
+      for (int stage = 0; stage < 3; ++stage)
+      {
+        const double* const sq = stage ? ws[11 + 2 * (stage - 1)] : xq_t;
+        const double* const sv = stage ? ws[12 + 2 * (stage - 1)] : xv_t;
+        st = fwd_dyn_chunks(c, sq, sv, tau_t, acc, st_stage, N, in_ss, in_sj, chunk, (double*)workspace, stream, tbl);
+        if (st != RDYN_OK) return st;
+        u.a = xq_t;
+        u.b = xv_t;
+        u.c = sv;
+        u.d = acc;
+        u.sq = ws[11 + 2 * stage];
+        u.sv = ws[12 + 2 * stage];
+        u.cdt = stage == 2 ? d->dt : 0.5 * d->dt;  // of the NEXT stage
+        RDYN_HIP_TRY(update(RDYN_ADJ_OP_RK4_FWD));
+      }
+      RDYN_HIP_TRY(update(RDYN_ADJ_OP_RK4_PRE));
+      for (int i = 3; i >= 0; --i)
+      {
+        u.wgt = (i == 0 || i == 3) ? 1.0 / 6.0 : 1.0 / 3.0;
+        u.cdt = i == 3 ? d->dt : 0.5 * d->dt;
+        RDYN_HIP_TRY(update(RDYN_ADJ_OP_RK4_SEED));
+        st = vjp_chunks(c, i ? ws[11 + 2 * (i - 1)] : xq_t, i ? ws[12 + 2 * (i - 1)] : xv_t, tau_t, mu, qb, vb, tb, nullptr, st_stage, N, in_ss,
+                        in_sj, chunk_samples, workspace, tbl, stream);
+        if (st != RDYN_OK) return st;
+        RDYN_HIP_TRY(update(RDYN_ADJ_OP_RK4_POST));
+      }
+      RDYN_HIP_TRY(update(RDYN_ADJ_OP_RK4_END));
+    }
+    if (t >= 1 && running)
+    {
+      u.a = d->gq_traj ? d->gq_traj + (int64_t)(t - 1) * d->gtraj_step_stride : nullptr;
+      u.b = d->gdq_traj ? d->gdq_traj + (int64_t)(t - 1) * d->gtraj_step_stride : nullptr;
+      RDYN_HIP_TRY(update(RDYN_ADJ_OP_ADD_SEED));
+    }
+  }
+  u.out_q = d->gq0;
+  u.out_v = d->gdq0;
+  u.status = d->status;
+  RDYN_HIP_TRY(update(RDYN_ADJ_OP_OUT));
   return RDYN_OK;
 }
 

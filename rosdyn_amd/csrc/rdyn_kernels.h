@@ -576,6 +576,102 @@ struct RdynRolloutCompArgs
 };
 hipError_t rdyn_launch_rollout_components(int n_joints, const RdynRolloutCompArgs& a, hipStream_t st);
 
+// reverse-mode product of the forward dynamics (rdyn_fwd_dyn_vjp.hip): with ddq = FD_c(q, dq, tau) and the seed ddq_bar per sample,
+// tau_bar = M^-1 ddq_bar, q_bar = dddq_dq' ddq_bar, dq_bar = dddq_dv' ddq_bar (the matrices of RdynFwdDynDerivArgs).  Every vector is
+// addressed like q; any output may be null (not all three of the products); tau_bar may alias ddq_bar.
+struct RdynFwdDynVjpArgs
+{
+  const RdynChainConst* chain;
+  const double *q, *dq, *tau, *ddq_bar;
+  double *q_bar, *dq_bar, *tau_bar, *ddq;
+  int32_t* status;  // may be null: 1, or -1 (a pivot failed or an input of the sample is not finite: every output of the sample is NaN)
+  int64_t n_samples, in_ss, in_sj;
+  int staged;       // doubles per record (n_active): sample-major records through the wave's LDS tile (natural strides, every output line-aligned); 0 = 8-byte stores
+  RdynComponentTable t;
+};
+hipError_t rdyn_launch_forward_dynamics_vjp(int n_joints, const RdynFwdDynVjpArgs& a, hipStream_t st);
+// ... of a chain with more input joints than the unrolled kernels sweep: the three transposed products from the matrices
+// rdyn_forward_dynamics_derivatives left element-major in the workspace (element e = i + n k of sample s of the chunk at X[e * ld + s]);
+// status = what that call wrote for the chunk (not null)
+struct RdynVjpProductArgs
+{
+  const double *dddq_dq, *dddq_dv, *minv;  // dddq_dq / dddq_dv may be null with q_bar / dq_bar
+  int64_t ld;
+  int n;
+  const double *q, *dq, *tau, *ddq_bar;  // the chunk's first sample: a sample with a non-finite entry gets -1
+  int64_t seed_ss, seed_sj;              // ... of ddq_bar (the host hands over a copy: tau_bar may alias the caller's)
+  double *q_bar, *dq_bar, *tau_bar;
+  double* ddq;          // may be null: gets NaN where the sample fails here
+  int32_t* status;      // the chunk's, read and updated
+  int32_t* status_out;  // may be null: the caller's
+  int64_t n_samples, in_ss, in_sj;
+};
+hipError_t rdyn_launch_vjp_products(const RdynVjpProductArgs& a, hipStream_t st);
+// dst[i * ld + s] = src[s * in_ss + i * in_sj], i < n, s < n_samples: the chunk's seeds into the workspace
+hipError_t rdyn_launch_vjp_seed_copy(const double* src, double* dst, int n, int64_t n_samples, int64_t ld, int64_t in_ss, int64_t in_sj, hipStream_t st);
+
+// adjoint of a rollout (rdyn_rollout_adjoint.hip): the transpose of the T steps RdynRolloutArgs describes, backwards from the seeds on the
+// end state (and on every trajectory record) to the gradients with respect to the initial state and the torques
+struct RdynRolloutAdjointArgs
+{
+  const RdynChainConst* chain;
+  const double *q, *dq, *tau;          // x_0 and the forward call's torques
+  int64_t tau_step;
+  const double *q_traj, *dq_traj;      // record k = x_{k + 1}
+  int64_t traj_step;
+  const double *gq_end, *gdq_end;      // may be null (0)
+  const double *gq_traj, *gdq_traj;    // may be null: record k = the seed on x_{k + 1}
+  int64_t gtraj_step;
+  double *gq0, *gdq0;                  // may be null; may alias gq_end / gdq_end
+  double* gtau;                        // may be null
+  int64_t gtau_step;                   // 0: the sum over the steps
+  int32_t* status;                     // may be null
+  int64_t n_samples, in_ss, in_sj;
+  double dt;
+  int n_steps, integrator, n_active;
+  int staged;  // sample-major records through the wave's LDS tile in whole lines: bit 0 gq0 / gdq0, bit 1 gtau
+  RdynComponentTable t;
+};
+hipError_t rdyn_launch_rollout_adjoint(int n_joints, const RdynRolloutAdjointArgs& a, hipStream_t st);
+// ... of a chain with more input joints than the unrolled kernels sweep: the element-wise updates between the passes of the host loop
+// (rdyn_api.cpp).  Every array holds count = n * n_samples doubles in the batch's layout; op selects the update (the formulas are at the
+// head of rdyn_rollout_adjoint.hip).
+enum
+{
+  RDYN_ADJ_OP_INIT = 0,        // lq = a + b, lv = c + d (null = 0); st_run = 1
+  RDYN_ADJ_OP_EULER_PRE = 1,   // lv = lv + dt lq; mv = dt lv (the seed of the product)
+  RDYN_ADJ_OP_EULER_POST = 2,  // lq += qb, lv += vb, gtau (= | +=) tb; st_run = min(st_run, st_stage); NaN for a failed sample
+  RDYN_ADJ_OP_RK4_FWD = 3,     // sq = a + cdt c, sv = b + cdt d: the next stage state from x_t = (a, b), the stage velocity c and acceleration d
+  RDYN_ADJ_OP_RK4_PRE = 4,     // xq = lq, xv = lv, kq = kv = mq = 0
+  RDYN_ADJ_OP_RK4_SEED = 5,    // kq = dt wgt lq + kq, mv = dt wgt lv + kv (the seed of the product)
+  RDYN_ADJ_OP_RK4_POST = 6,    // mq += tb, xq += qb, xv += kq + vb, (kq, kv) = cdt (qb, kq + vb); st_run = min(st_run, st_stage)
+  RDYN_ADJ_OP_RK4_END = 7,     // lq = xq, lv = xv, gtau (= | +=) mq; NaN for a failed sample
+  RDYN_ADJ_OP_ADD_SEED = 8,    // lq += a, lv += b (null = 0): the running seeds that are due
+  RDYN_ADJ_OP_OUT = 9,         // lq -> out_q, lv -> out_v, st_run -> status (each may be null)
+  RDYN_ADJ_OP_ZERO = 10        // gtau = 0
+};
+struct RdynAdjointUpdateArgs
+{
+  int op;
+  double *lq, *lv;              // the adjoint state
+  double *xq, *xv;              // RK4: x_bar
+  double *kq, *kv;              // RK4: the carry into the next-lower stage's seed, then that stage's kq
+  double *mq, *mv;              // RK4: the step's torque gradient; the seed handed to the product
+  const double *qb, *vb, *tb;   // what the product returned
+  const double *a, *b, *c, *d;  // op-specific inputs
+  double *sq, *sv;              // RDYN_ADJ_OP_RK4_FWD: the next stage's state
+  double *out_q, *out_v;        // RDYN_ADJ_OP_OUT
+  double* gtau;                 // may be null
+  int gtau_add;                 // gtau += instead of =
+  const int32_t* st_stage;      // the product's status
+  int32_t* st_run;              // the running minimum
+  int32_t* status;              // RDYN_ADJ_OP_OUT
+  int64_t count, n_samples;
+  int n, element_major;
+  double dt, wgt, cdt;          // b_i and c_i of the stage
+};
+hipError_t rdyn_launch_adjoint_update(const RdynAdjointUpdateArgs& a, hipStream_t st);
+
 // pieces of rdyn_identification_tsqr for the multi-device form (rdyn_api.cpp): widths of the swept / the chain's factor, the factor of
 // the swept chain alone, the expansion (+ accumulation) of a swept factor
 int rdyn_internal_tsqr_widths(const rdyn_chain* c, const rdyn_component* comps, int n_comps, int* n1s, int* n1, int* expands);

@@ -903,6 +903,29 @@ public:
   {
     chk(rdyn_rollout_components(m_h, &b, &desc, comps.data(), (int)comps.size(), chunk_samples, workspace, workspace_bytes));
   }
+  // adjoint of a rollout of a batch (b.q, b.dq = the forward call's initial state; every pointer of desc a device pointer in the layout of
+  // b.q; comps may be empty): the gradients with respect to the initial state and the torques from the seeds on the end state and on the
+  // trajectory records, both integrators: rdyn_rollout_adjoint
+  size_t rolloutAdjointWorkspaceBytes(const rdyn_rollout_adjoint_desc& desc, int64_t n_samples, int64_t chunk_samples = 0) const
+  {
+    return rdyn_rollout_adjoint_workspace_bytes(m_h, &desc, n_samples, chunk_samples);
+  }
+  void rolloutAdjointBatch(const std::vector<rdyn_component>& comps, const rdyn_batch& b, const rdyn_rollout_adjoint_desc& desc,
+                           int64_t chunk_samples, void* workspace, size_t workspace_bytes) const
+  {
+    chk(rdyn_rollout_adjoint(m_h, &b, &desc, comps.empty() ? nullptr : comps.data(), (int)comps.size(), chunk_samples, workspace, workspace_bytes));
+  }
+  // reverse-mode product of the forward dynamics of a batch (b.q, b.dq; tau, the seed DDq_bar and every output n per sample in the layout of
+  // b.q; q_bar, Dq_bar, tau_bar may be null, not all three; tau_bar may alias DDq_bar; ddq and status may be null; comps may be empty):
+  // rdyn_forward_dynamics_vjp
+  size_t getJointAccelerationVjpWorkspaceBytes(int64_t chunk_samples = 0) const { return rdyn_forward_dynamics_vjp_workspace_bytes(m_h, chunk_samples); }
+  void getJointAccelerationVjpBatch(const std::vector<rdyn_component>& comps, const rdyn_batch& b, const double* tau, const double* DDq_bar,
+                                    double* q_bar, double* Dq_bar, double* tau_bar, double* ddq, int32_t* status, int64_t chunk_samples,
+                                    void* workspace, size_t workspace_bytes) const
+  {
+    chk(rdyn_forward_dynamics_vjp(m_h, &b, comps.empty() ? nullptr : comps.data(), (int)comps.size(), tau, DDq_bar, q_bar, Dq_bar, tau_bar, ddq, status,
+                                  chunk_samples, workspace, workspace_bytes));
+  }
   // derivatives of the joint torque of a batch (b.q, b.dq, b.ddq; every output n x n per sample, any may be null): rdyn_joint_torque_derivatives
   void getJointTorqueDerivativesBatch(const rdyn_batch& b, double* dtau_dq, double* dtau_dDq, double* M = nullptr) const
   {
