@@ -60,17 +60,23 @@ def _norm_inf(M):
     return np.abs(M).sum(axis=2).max(axis=1)
 
 
-def _residual_ratios(ref, types, q, dq, ddq, Xq, Xv, Minv, slopes=None):
-    """worst ratio residual / scale per output over the samples given, and the construction gap of the reference"""
+def _residual_ratios(ref, types, q, dq, ddq, Xq, Xv, Minv, slopes=None, cached=None):
+    """worst ratio residual / scale per output over the samples given, and the construction gap of the reference.
+    cached: None, or what test_gpu_forward_dynamics_vjp._cached_reference returns for these very (q, dq, ddq) -- (M_ref, Dq_ref, Dv_ref,
+    tau_ref, gscale), its construction gap asserted there -- so that the reference is computed once for both modules' residuals."""
     N, n = q.shape
-    Dq_ref, Dv_ref, tau_ref, gap = _reference(ref, types, q, dq, ddq)
-    gscale = np.maximum(_inf(Dq_ref), _inf(Dv_ref)) + _inf(tau_ref)
-    assert (gap <= 1e-12 * gscale).all(), ("spectral reference, 8 against 16 points", float((gap / gscale).max()))
+    if cached is None:
+        Dq_ref, Dv_ref, tau_ref, gap = _reference(ref, types, q, dq, ddq)
+        gscale = np.maximum(_inf(Dq_ref), _inf(Dv_ref)) + _inf(tau_ref)
+        assert (gap <= 1e-12 * gscale).all(), ("spectral reference, 8 against 16 points", float((gap / gscale).max()))
+        M = ref.joint_inertia(q)
+    else:
+        M, Dq_ref, Dv_ref, tau_ref = cached[:4]
+        Dq_ref, Dv_ref = Dq_ref.copy(), Dv_ref.copy()
     if slopes is not None:
         idx = np.arange(n)
         Dq_ref[:, idx, idx] += slopes[0]
         Dv_ref[:, idx, idx] += slopes[1]
-    M = ref.joint_inertia(q)
     mn = _norm_inf(M)
     out = {}
     for what, X, D in (("dddq_dq", Xq, Dq_ref), ("dddq_dv", Xv, Dv_ref)):

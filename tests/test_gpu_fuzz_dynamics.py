@@ -8,6 +8,7 @@ Every sample is classified from the oracle alone (classify): regular -- the smal
 a hundred times the kernels' 1e-10 trace rule and a lower bound of every pivot in any elimination order -- or singular -- a diagonal
 entry of M_ref at most 1e-14 trace(M_ref), or a zero trace.  A sample in neither class fails the test; none is excused.
 tests/test_fuzz_dynamics_inputs.py pins, without a GPU, what these tests rest on.
+tests/test_gpu_fuzz_gradients.py runs the entry points merged since on the same cases: components, derivatives, VJP, rollout adjoint.
 
 Bounds, each per sample:
   forward dynamics   the residual bound of test_gpu_forward_dynamics.py (1e-11) against the oracle and its 64 eps cond2 solver bound
