@@ -839,7 +839,7 @@ __device__ __forceinline__ void chol_with_inverse_regs(double* M, double* E, int
 //                    What the later columns keep of direction k is left to the Cholesky factorisation of Q'Q over ALL rows.
 //   gamma            max_j gamma_j is evaluated on the finished T, W.  Above 1e4 (round 1; round 0, which may still serve as the
 //                    preconditioner of round 1: 1e10) the round is not run: flags say so and the Householder factorisation of all
-//                    rows (the stand-by call of rdyn_api.cpp) takes over.
+//                    rows (the stand-by call of rdyn_api_tsqr.cpp) takes over.
 // flags: [0] run round 1, [1] run the stand-by, [2] run round 0 (written here in round 0).  zmask <- Z (for the factor kernel).
 // W is written in the MFMA operand order of k_regressor_pgram.
 constexpr double kCholqrGammaMax = 1e4;

@@ -1,4 +1,4 @@
-// rdyn_kernels.h -- launch interface between the C-ABI layer (rdyn_api.cpp) and the HIP kernels.
+// rdyn_kernels.h -- launch interface between the C-ABI layer (rdyn_api*.cpp) and the HIP kernels.
 #ifndef RDYN_KERNELS_H
 #define RDYN_KERNELS_H
 
@@ -634,7 +634,7 @@ struct RdynRolloutAdjointArgs
 };
 hipError_t rdyn_launch_rollout_adjoint(int n_joints, const RdynRolloutAdjointArgs& a, hipStream_t st);
 // ... of a chain with more input joints than the unrolled kernels sweep: the element-wise updates between the passes of the host loop
-// (rdyn_api.cpp).  Every array holds count = n * n_samples doubles in the batch's layout; op selects the update (the formulas are at the
+// (rdyn_api_dynamics.cpp).  Every array holds count = n * n_samples doubles in the batch's layout; op selects the update (the formulas are at the
 // head of rdyn_rollout_adjoint.hip).
 enum
 {
@@ -672,7 +672,7 @@ struct RdynAdjointUpdateArgs
 };
 hipError_t rdyn_launch_adjoint_update(const RdynAdjointUpdateArgs& a, hipStream_t st);
 
-// pieces of rdyn_identification_tsqr for the multi-device form (rdyn_api.cpp): widths of the swept / the chain's factor, the factor of
+// pieces of rdyn_identification_tsqr for the multi-device form (rdyn_api_tsqr.cpp): widths of the swept / the chain's factor, the factor of
 // the swept chain alone, the expansion (+ accumulation) of a swept factor
 int rdyn_internal_tsqr_widths(const rdyn_chain* c, const rdyn_component* comps, int n_comps, int* n1s, int* n1, int* expands);
 int rdyn_internal_tsqr_swept(const rdyn_chain* c, const rdyn_component* comps, int n_comps, const rdyn_batch* b, const double* tau_meas, double* R_swept,

@@ -16,7 +16,7 @@
 // PERSISTENT waves (a few workgroups per CU walking the batch in strides of the grid, the next tile's inputs requested while the current
 // one is swept; profiles/r6/sweep_sheet_persistent.txt) were built and measured too: slower everywhere (getTwist 91 -> 129 us,
 // getTransformations 129 -> 166 us) -- the hardware's own dispatch keeps more waves in flight than a fixed grid does.
-// Preconditions, checked by the host (rdyn_api.cpp: natural strides, base pointer
+// Preconditions, checked by the host (rdyn_api*.cpp: natural strides, base pointer
 // 128-byte aligned) and by the kernel (a full wave): everything else keeps the 8-byte stores.
 #ifndef RDYN_RECORD_STAGE_H
 #define RDYN_RECORD_STAGE_H

@@ -13,7 +13,7 @@
 //     Sample-major records (trajectory records, the end state) leave through SmallRecords (rdyn_record_stage.h) in whole lines under
 //     k_fwd_dyn's condition (the host found them line-aligned with natural strides, the wave is full); otherwise 8-byte stores.
 //   k_rollout_stage   more than RDYN_MAX_SWEPT_JOINTS input joints: the host runs the chunked forward dynamics once per stage on the
-//     stream (rdyn_api.cpp); this element-wise kernel forms the next stage state, accumulates the weighted sums, at the last stage
+//     stream (rdyn_api_dynamics.cpp); this element-wise kernel forms the next stage state, accumulates the weighted sums, at the last stage
 //     advances the state, writes the trajectory record that is due and keeps the status as the running minimum.  State and stage buffers are
 //     in the caller's workspace in the batch's layout, so one thread per double, every access contiguous.
 //   k_rollout_copy    the same route: initial state -> workspace (status 1), workspace -> end state (status out).

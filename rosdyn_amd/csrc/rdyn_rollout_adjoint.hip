@@ -22,7 +22,7 @@
 //     plain evaluations, six per step on top of the three, against registers that the 9- and 10-joint kernels spill either way
 //     (DESIGN.md section 3 has the compiler's figures).
 //   k_adjoint_update   more than RDYN_MAX_SWEPT_JOINTS input joints: CORRECT BUT NOT FAST.  The host loops over steps and stages on the
-//     stream (rdyn_api.cpp): the chunked rdyn_forward_dynamics_vjp route for every product, the chunked forward dynamics for the RK4
+//     stream (rdyn_api_dynamics.cpp): the chunked rdyn_forward_dynamics_vjp route for every product, the chunked forward dynamics for the RK4
 //     stage rebuild, and this element-wise kernel for everything between them.  State, stage and seed buffers are in the caller's
 //     workspace in the batch's layout: one thread per double, every access contiguous.
 // A sample with a failed pivot or a non-finite value in any evaluation gets status -1 and, from that backward step on, quiet NaN in every

@@ -463,7 +463,7 @@ __global__ __launch_bounds__(256) void k_tsqr_rows(const double* __restrict__ A,
 
 // ---------------------------------------------------------------- tree: every wave folds `fan` factors into one
 // (2 : 1 by default -- a fold is 61 .. 71 dependent column steps whatever the block holds, so the DEPTH of the tree is its cost: 4 : 1
-// levels fold three blocks one after the other per level.  A larger fan trades time for launches: the stand-by call of rdyn_api.cpp)
+// levels fold three blocks one after the other per level.  A larger fan trades time for launches: the stand-by call of rdyn_api_tsqr.cpp)
 template <int NC>
 __global__ __launch_bounds__(64) void k_tsqr_combine(const double* __restrict__ in, int count, int fan, double* __restrict__ out, int out_ld, int out_cols,
                                                      const double* __restrict__ extra /* one more factor (accumulate), or null */, int extra_ld,

@@ -140,7 +140,7 @@ __device__ __forceinline__ void store_packed_factor(const double* Rp, double* ou
 }
 
 // ---------------------------------------------------------------- leaf: regressor rows from the workgroup's own sweep
-// fa: the RECTANGULAR tile layout of rdyn_api.cpp (build_rect_tile): every column 16 n_active rows + 4 doubles of padding; link f at
+// fa: the RECTANGULAR tile layout of rdyn_api_tsqr.cpp (build_rect_tile): every column 16 n_active rows + 4 doubles of padding; link f at
 // lds_off[f], component column k at lds_off_c + k * comp_stride + (its joint) * comp_row_step, tau_meas at lds_off_b.
 // n1 = 10 n_joints + n_comp_cols + 1 columns.  factors: [gridDim.x][n1 * n1].
 __global__ __launch_bounds__(NTW) void k_regressor_tsqr_wide(const RdynLdsGramArgs fa, int n_joints, int n1, double* __restrict__ factors)

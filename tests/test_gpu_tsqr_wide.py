@@ -329,7 +329,7 @@ def test_doctored_wide_matrices_on_the_matrix_cores(seed):
     A[:, dep[0]] = A[:, dep[1]] - 0.5 * A[:, dep[2]]
     if seed % 2:
         A[:, dep[3]] = 0.0
-    # the rows the subsample sees: every gs-th 16-row group (rdyn_api.cpp: 8 192 groups, odd stride)
+    # the rows the subsample sees: every gs-th 16-row group (rdyn_api_tsqr.cpp: 8 192 groups, odd stride)
     groups = (rows + 15) // 16
     gs = max(1, groups // 8192)
     gs += 1 if (gs > 1 and gs % 2 == 0) else 0
