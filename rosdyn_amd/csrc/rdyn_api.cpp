@@ -156,8 +156,8 @@ int image_route(const rdyn_chain* c, const rdyn_regressor_layout* yl, int64_t n_
   if (mapped) *mapped = false;
   const int n = c->n_active(), nJ = c->n_joints();
   const bool lay_image = yl->stride_row == 1 && yl->stride_col == n && yl->stride_sample >= (int64_t)n * 10 * nJ;
-  const bool lay_stacked = yl->stride_row == 1 && yl->stride_sample == n && yl->stride_col >= n_samples * n && !probe_env("RDYN_NO_STACKED_LDS");
-  if (!(lay_image || lay_stacked) || probe_env("RDYN_NO_IMAGE")) return 0;
+  const bool lay_stacked = yl->stride_row == 1 && yl->stride_sample == n && yl->stride_col >= n_samples * n;
+  if (!(lay_image || lay_stacked)) return 0;
   // less than one wave of samples (the facade's single-sample getRegressor): the staging machinery costs more than it saves (19.5 us per
   // call at N = 1 against 11 for the kernels that store from the computing lane, profiles/r6/perf_sheet.txt) -- the row-pair / strided kernels
   if (n_samples < 64 && !multi) return 0;
@@ -174,8 +174,7 @@ int image_route(const rdyn_chain* c, const rdyn_regressor_layout* yl, int64_t n_
   if (ordered_inputs && rdyn_image_supported(nJ, fix, yl->stride_sample, multi)) return lay_stacked ? 2 : 1;
   // input joints out of chain order, or joints that are not input joints somewhere else than the compiled head / tail patterns:
   // per-sample images go through the run-time row map (k_image_sweep<.., MAP>); everything else keeps the row-pair / strided kernels
-  if (mapped && !multi && lay_image && !lay_stacked && (ordered_inputs || c->sorted) && rdyn_image_map_supported(nJ, fix, yl->stride_sample) &&
-      !probe_env("RDYN_NO_IMAGE_MAP"))
+  if (mapped && !multi && lay_image && !lay_stacked && (ordered_inputs || c->sorted) && rdyn_image_map_supported(nJ, fix, yl->stride_sample))
   {
     *mapped = true;
     return 1;
@@ -225,7 +224,7 @@ int run_local(const rdyn_chain* c, const rdyn_batch* b, int mode, double* tau, d
     a.y_sr = yl->stride_row;
     a.y_sc = yl->stride_col;
   }
-  if (mode == RDYN_MODE_REGRESSOR_EXPAND && yl && yl->stride_row == 1 && ((uintptr_t)Y & 15) == 0 && !probe_env("RDYN_NO_EXPAND_STAGING"))
+  if (mode == RDYN_MODE_REGRESSOR_EXPAND && yl && yl->stride_row == 1 && ((uintptr_t)Y & 15) == 0)
   {
     // row-contiguous layouts: every link's block through the wave's LDS tile, copied out 16 bytes per lane (k_expand_staged)
     if (yl->stride_col == n && yl->stride_sample % 2 == 0) a.expand_stage = 1;        // per-sample images
@@ -235,7 +234,7 @@ int run_local(const rdyn_chain* c, const rdyn_batch* b, int mode, double* tau, d
   // per-sample images of a long chain whose companion has up to 6 joints: the image kernel (whole-line copy-out through the per-sample
   // ring) forms the blocks of the riding links one at a time (k_image_sweep<.., EXPAND>)
   bool expand_image = false;
-  if (mode == RDYN_MODE_REGRESSOR_EXPAND_STAGED && a.expand_stage == 1 && c->n_active() == c->n_joints() && !probe_env("RDYN_NO_EXPAND_IMAGE") &&
+  if (mode == RDYN_MODE_REGRESSOR_EXPAND_STAGED && a.expand_stage == 1 && c->n_active() == c->n_joints() &&
       rdyn_image_expand_supported(c->n_joints(), full->n_joints(), yl->stride_sample))
   {
     const int nr = c->n_joints(), nf = full->n_joints();
@@ -266,14 +265,12 @@ int run_local(const rdyn_chain* c, const rdyn_batch* b, int mode, double* tau, d
   a.M = M;
   rec_strides(b, (int64_t)n * n, &a.m_ss, &a.m_se);
   // torque / inertia records in the drop-in layout: through the wave's LDS tile, whole lines (rdyn_record_stage.h)
-  if ((mode == RDYN_MODE_TORQUE || mode == RDYN_MODE_INERTIA) && b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(tau, M) &&
-      !probe_env("RDYN_NO_RECORD_STAGING"))
+  if ((mode == RDYN_MODE_TORQUE || mode == RDYN_MODE_INERTIA) && b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(tau, M))
     a.staged = mode == RDYN_MODE_INERTIA ? n * n : n;
   // Row-contiguous regressor layouts (stacked column-major, per-sample Eigen image) with sample-major inputs:
   // ceil(n/2) lanes per sample, 16-byte row-pair stores (k_rowpair_sweep) instead of 8-byte strided stores.
   const bool rowpair = mode == RDYN_MODE_REGRESSOR && yl && yl->stride_row == 1 && n >= 2 && n <= 10 &&
-                       b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && b->n_samples * ((n + 1) / 2) < (int64_t)0xFFFFFF00ll &&
-                       !probe_env("RDYN_NO_ROWPAIR");
+                       b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && b->n_samples * ((n + 1) / 2) < (int64_t)0xFFFFFF00ll;
   // the drop-in per-sample image (either input layout): one thread per sample, link blocks staged through LDS (rdyn_image.hip)
   // and the stacked column-major (N n) x P matrix (stride_sample == n): same kernel, column-major staging tile per link
   unsigned fix_mask = 0;
@@ -286,7 +283,7 @@ int run_local(const rdyn_chain* c, const rdyn_batch* b, int mode, double* tau, d
     auto gcd = [](unsigned x, unsigned y) { while (y) { const unsigned t = x % y; x = y; y = t; } return x; };
     unsigned m = 257;
     while (gcd(m, grid) != 1) ++m;
-    a.blk_mul = (grid > 4 * m && !probe_env("RDYN_NO_IMAGE_SCATTER")) ? m : 0;
+    a.blk_mul = (grid > 4 * m) ? m : 0;
     RDYN_HIP_TRY(rdyn_launch_image_sweep(c->n_joints(), 0u, a, (hipStream_t)b->stream, 2));
   }
   else if (image)
@@ -305,7 +302,7 @@ int run_local(const rdyn_chain* c, const rdyn_batch* b, int mode, double* tau, d
     // tools/probe_scatter.py, profiles/r6/probe_scatter.txt: ten 2.88 GB output allocations per process): 516-523 -> 450-455 us per 1e6
     // evaluations in half of the allocations, 537-547 -> 508-520 in most others, never slower; multipliers 17 .. 4097 alike.  The stacked
     // matrix (60 column fronts already) loses 2-5 % with it and keeps the workgroups in order.
-    if (image_route(c, yl, b->n_samples, Y, false, &fix_mask, &mapped) == 1 && !probe_env("RDYN_NO_IMAGE_SCATTER"))
+    if (image_route(c, yl, b->n_samples, Y, false, &fix_mask, &mapped) == 1)
     {
       const unsigned grid = (unsigned)((b->n_samples + 63) / 64);
       auto gcd = [](unsigned x, unsigned y) { while (y) { const unsigned t = x % y; x = y; y = t; } return x; };
@@ -371,7 +368,7 @@ int run_long_local(const rdyn_chain* c, const rdyn_batch* b, int mode, double* t
     a.y_sr = yl->stride_row;
     a.y_sc = yl->stride_col;
     // row-contiguous layouts: every link's block through the wave's LDS tile, copied out 16 bytes per lane
-    if (yl->stride_row == 1 && ((uintptr_t)Y & 15) == 0 && !probe_env("RDYN_NO_EXPAND_STAGING"))
+    if (yl->stride_row == 1 && ((uintptr_t)Y & 15) == 0)
     {
       if (yl->stride_col == n && yl->stride_sample % 2 == 0 && yl->stride_sample >= (int64_t)n * 10 * c->n_joints()) a.stage = 1;
       else if (yl->stride_sample == n && yl->stride_col % 2 == 0 && yl->stride_col >= b->n_samples * n) a.stage = 2;
@@ -409,7 +406,7 @@ static int long_chain_torque(const rdyn_chain* c, const rdyn_batch* b, double* t
   e.tau = tau;
   e.tau_ss = e.in_ss;
   e.tau_sj = e.in_sj;
-  e.staged = b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(tau) && !probe_env("RDYN_NO_RECORD_STAGING");
+  e.staged = b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(tau);
   RDYN_HIP_TRY(rdyn_launch_long_ext(c->n_joints(), e, (hipStream_t)b->stream));
   return RDYN_OK;
 }
@@ -503,7 +500,7 @@ int rdyn_joint_torque_derivatives(const rdyn_chain* c, const rdyn_batch* b, doub
     const rdyn_chain* const sw = c->long_chain() ? c->reduced.get() : c;
     st = device_const(sw, &a.chain);
     if (st != RDYN_OK) return st;
-    a.staged = (b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(dtau_dq, dtau_dv, M) && !probe_env("RDYN_NO_RECORD_STAGING")) ? n * n : 0;
+    a.staged = (b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(dtau_dq, dtau_dv, M)) ? n * n : 0;
     RDYN_HIP_TRY(rdyn_launch_torque_derivatives(sw->n_joints(), a, (hipStream_t)b->stream));
     return RDYN_OK;
   }
@@ -548,7 +545,7 @@ static int run_base(const rdyn_chain* c, const rdyn_batch* b, double* T_bt, doub
   a.out_se = se;
   a.n_active = n;
   // the drop-in layout: records leave through wave-private LDS in whole lines (rdyn_record_stage.h) when every output starts on a line
-  a.staged = b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(T_bt, T_links, J, tw, dtw) && !probe_env("RDYN_NO_RECORD_STAGING");
+  a.staged = b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(T_bt, T_links, J, tw, dtw);
   if (c->long_chain())
   {
     for (int l = 0; l < a.j_link; ++l) a.j_up += c->host_joints[l].in_idx >= 0 ? 1 : 0;
@@ -734,7 +731,7 @@ int rdyn_twist_parts(const rdyn_chain* c, const rdyn_batch* b, const double* ddd
   a.dtw_lin = dtw_lin;
   a.dtw_nonlin = dtw_nonlin;
   a.ddtw = ddtw;
-  a.staged = b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(dtw_lin, dtw_nonlin, ddtw) && !probe_env("RDYN_NO_RECORD_STAGING");
+  a.staged = b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(dtw_lin, dtw_nonlin, ddtw);
   if (c->long_chain())
     RDYN_HIP_TRY(rdyn_launch_long_ext(c->n_joints(), a, (hipStream_t)b->stream));
   else
@@ -768,7 +765,7 @@ int rdyn_jerk_parts(const rdyn_chain* c, const rdyn_batch* b, const double* dddq
   rec_strides(b, 6 * (int64_t)(c->n_joints() + 1), &a.out_ss, &a.out_se);
   a.ddtw_lin = ddtw_lin;
   a.ddtw_nonlin = ddtw_nonlin;
-  a.staged = b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(ddtw_lin, ddtw_nonlin) && !probe_env("RDYN_NO_RECORD_STAGING");
+  a.staged = b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(ddtw_lin, ddtw_nonlin);
   if (c->long_chain())
     RDYN_HIP_TRY(rdyn_launch_long_ext(c->n_joints(), a, (hipStream_t)b->stream));
   else
@@ -803,8 +800,8 @@ int rdyn_wrench(const rdyn_chain* c, const rdyn_batch* b, const double* ext, dou
   a.ext = ext;
   a.ext_ss = a.out_ss;
   a.ext_se = a.out_se;
-  a.staged = b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(wrenches) && !probe_env("RDYN_NO_RECORD_STAGING");
-  a.ext_staged = a.staged && ext && ((uintptr_t)ext & 15u) == 0 && !probe_env("RDYN_NO_EXT_STAGING");
+  a.staged = b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(wrenches);
+  a.ext_staged = a.staged && ext && ((uintptr_t)ext & 15u) == 0;
   if (c->long_chain())
     RDYN_HIP_TRY(rdyn_launch_long_ext(c->n_joints(), a, (hipStream_t)b->stream));
   else
@@ -842,7 +839,7 @@ int rdyn_joint_torque_ext(const rdyn_chain* c, const rdyn_batch* b, const double
     e.tau_sj = e.in_sj;
     e.ext = ext;
     rec_strides(b, 6 * (int64_t)(c->n_joints() + 1), &e.ext_ss, &e.ext_se);
-    e.staged = b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(tau) && !probe_env("RDYN_NO_RECORD_STAGING");
+    e.staged = b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(tau);
     RDYN_HIP_TRY(rdyn_launch_long_ext(c->n_joints(), e, (hipStream_t)b->stream));
     return RDYN_OK;
   }

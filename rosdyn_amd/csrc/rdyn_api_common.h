@@ -3,16 +3,11 @@
 // of the Gram and factor calls.  Every item is declared here once and defined inline or in the one file named beside it; nothing here
 // is exported.
 //
-// Diagnostic environment switches exist ONLY in builds compiled with -DRDYN_ENABLE_PROBES (tools/build_variant.sh; A/B
-// measurements, tools/probe_*.py and tools/kbench).  The shipped library never reads the environment: a variable left over
-// from a profiling shell cannot change results.
-//   RDYN_NO_ROWPAIR=1       regressor in row-contiguous layouts through the one-thread-per-sample kernel
-//   RDYN_GRAM_PATH=pipe|lds0|image|two   regressor->Gram kernel: single-wave pipelined LDS tile / two-phase LDS tile /
-//                           global image / two kernels (default: wave-pair kernel where eligible, then the single-wave LDS
-//                           kernels, then the global image)
-//   RDYN_GRAM_UNFUSED=1     same as RDYN_GRAM_PATH=two
-//   RDYN_FUSED_BLOCKS=n     persistent workgroups of the fused Gram kernels (default 256 = one per CU)
-//   RDYN_FUSED_DEBUG=bits   phase ablation of the fused Gram kernels (timing only: results are then wrong)
+// Diagnostic environment switches exist ONLY in builds compiled with -DRDYN_ENABLE_PROBES (tools/build_variant.sh).  The shipped
+// library never reads the environment: a variable left over from a profiling shell cannot change results
+// (tests/test_release_object.py).  A switch lives here only while a tool outside tools/archive/ sets it; this is the whole list:
+//   RDYN_GRAM_PATH=image    rdyn_regressor_gram: the global-image kernel (rdyn_fused_gram.hip) where the wave-pair kernel would
+//                           run (tools/probe_gram_paths.py; the third route, two kernels, is the chunk_samples argument)
 #ifndef RDYN_API_COMMON_H
 #define RDYN_API_COMMON_H
 
@@ -176,10 +171,10 @@ void fill_in_map(const rdyn_chain* c, RdynLdsGramArgs* la);
 // the one-lane-per-sample sweepers of the wave-pair Gram kernel serve this chain (every joint an input joint): the tile padding they
 // use (4, or 2 = the compact layout), 0 = no
 int kin_sweeper_pad(const rdyn_chain* c, int n_comp_cols);
-// Tile layout of the LDS-resident regressor -> Gram kernels (rdyn_lds_gram.hip, rdyn_pipe_gram.hip, rdyn_duo_gram.hip): the columns
+// Tile layout of the LDS-resident regressor -> Gram and R-factor kernels (rdyn_duo_gram.hip, rdyn_cholqr.hip, rdyn_tsqr.hip): the columns
 // of link f keep the rows of the input joints at chain index <= f; K component columns (one 16-row group each) and the measured
 // torque follow.  Returns false when the input joints are not in chain order (the packed rows must be a prefix).
-bool build_lds_tile(const rdyn_chain* c, int n_comp_cols, bool dummy_slot, RdynLdsGramArgs* la, bool compact = false);
+bool build_lds_tile(const rdyn_chain* c, int n_comp_cols, RdynLdsGramArgs* la, bool compact = false);
 
 #pragma GCC visibility pop
 

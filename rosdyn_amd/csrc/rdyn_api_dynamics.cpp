@@ -174,7 +174,7 @@ static int dyn_prepare(const rdyn_chain* c, const rdyn_batch* b, const rdyn_comp
 template <class... P>
 static bool stage_records(const rdyn_batch* b, P... out)
 {
-  return b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(out...) && !probe_env("RDYN_NO_RECORD_STAGING");
+  return b->layout == RDYN_LAYOUT_SAMPLE_MAJOR && lines_aligned(out...);
 }
 
 // the descriptor fields a rollout and its adjoint share

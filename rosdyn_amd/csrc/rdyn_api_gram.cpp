@@ -66,8 +66,7 @@ int rdyn_gram(const double* A, int64_t rows, int64_t lda, int n_cols, const doub
 
 // Fused regressor->Gram kernel: persistent workgroups, each with its own 256-sample tile image (rewritten per tile, so
 // it stays in L2 / Infinity Cache): 256 workgroups x 256 samples x n x (P + 1) doubles = 192 MB at n = 6, P = 60.
-static int fused_blocks_env() { const char* e = probe_env("RDYN_FUSED_BLOCKS"); return e ? atoi(e) : 256; }
-static const int kFusedBlocks = 256;  // upper bound used for the workspace size; the launch uses fused_blocks_env()
+static const int kFusedBlocks = 256;  // persistent workgroups (one per CU); the workspace is sized for them
 
 // A chain whose own columns exceed what the Gram kernels hold (111) but whose REDUCED companion does not (fixed frames: 10 joints with
 // 7 input joints = 100 columns + friction columns) is served through the companion like a chain longer than the kernels sweep.
@@ -245,16 +244,15 @@ void fill_in_map(const rdyn_chain* c, RdynLdsGramArgs* la)
 {
   const int n = c->n_active();
   for (int r = 0; r < 8; ++r) la->in_map[r] = (r < n && r < (int)c->row_input.size()) ? c->row_input[r] : r;
-  fill_sw_rows(la, n, 7, 2, !probe_env("RDYN_KIN_ROW4") && n <= 6 ? 3 : -1);
+  fill_sw_rows(la, n, 7, 2, n <= 6 ? 3 : -1);
   la->sweep_lanes = 0;
 }
 int kin_sweeper_pad(const rdyn_chain* c, int n_comp_cols)
 {
-  if (probe_env("RDYN_GRAM_SWEEPER") && !strcmp(probe_env("RDYN_GRAM_SWEEPER"), "pair")) return 0;
   if (c->n_active() != c->n_joints()) return 0;
   return rdyn_regressor_gram_duo_kin_pad(c->n_joints(), n_comp_cols);
 }
-bool build_lds_tile(const rdyn_chain* c, int n_comp_cols, bool dummy_slot, RdynLdsGramArgs* la, bool compact)
+bool build_lds_tile(const rdyn_chain* c, int n_comp_cols, RdynLdsGramArgs* la, bool compact)
 {
   // column padding: 4 doubles keep the 16 lanes of an MFMA operand read on disjoint banks; the compact layout (2 doubles, 2-way
   // conflicts on the consumer's reads, which has slack) is what lets four 7-joint tiles WITH component columns fit 160 KB
@@ -262,7 +260,7 @@ bool build_lds_tile(const rdyn_chain* c, int n_comp_cols, bool dummy_slot, RdynL
   const int n = c->n_active(), nJ = c->n_joints();
   bool monotonic = true;
   for (int j = 1; j < n; ++j) monotonic = monotonic && c->active[j] > c->active[j - 1];
-  la->all_revolute = probe_env("RDYN_DUO_NO_ALLREV") ? 0 : 1;
+  la->all_revolute = 1;
   for (int f = 0; f < nJ; ++f)
     if (c->host_joints[f].type != RDYN_REVOLUTE) la->all_revolute = 0;
   int off = 0;
@@ -280,8 +278,6 @@ bool build_lds_tile(const rdyn_chain* c, int n_comp_cols, bool dummy_slot, RdynL
   off += n_comp_cols * la->comp_stride;
   la->lds_off_b = off;
   off += (16 * n + pad) * 8;
-  la->lds_dummy_off = off;
-  if (dummy_slot) off += 64 * 8;
   la->tile_bytes = (int)align256(off);
   la->n_active = n;
   for (int j = 0; j < n; ++j) la->first_col[j] = 10 * c->active[j];
@@ -371,26 +367,23 @@ int rdyn_regressor_gram(const rdyn_chain* c, const rdyn_batch* b, const double* 
   const int64_t N = b->n_samples;
   if (N == 0) return zero_normal_equations(G, cvec, bb, P, accumulate, stream);
   // (chunk_samples > 0 keeps the chain as it is: the reference ordering of the two-kernel path)
-  if (c->reduced && chunk_samples <= 0 && !probe_env("RDYN_GRAM_NO_REDUCE"))
+  if (c->reduced && chunk_samples <= 0)
     return gram_through_reduced(c, 0, b, G, cvec, bb, accumulate, workspace, rdyn_regressor_gram_workspace_bytes(c, chunk), companion);
   // structural zero band of every row block (input joint j): columns < 10 * chain index of joint j
   int first_col[RDYN_MAX_SWEPT_JOINTS];
   for (int j = 0; j < n; ++j) first_col[j] = 10 * c->active[j];
-  const char* path_env = probe_env("RDYN_GRAM_PATH");  // A/B only: "lds" (default when eligible), "image", "two"
-  const bool want_lds = !path_env || !strcmp(path_env, "lds") || !strcmp(path_env, "lds0") || !strcmp(path_env, "pipe") || !strcmp(path_env, "duo");
-  if (chunk_samples <= 0 && !probe_env("RDYN_GRAM_UNFUSED") && want_lds && n >= 2 && n <= 8)
+  // RDYN_GRAM_PATH=image (probe builds only, tools/probe_gram_paths.py): the global-image kernel where the wave-pair kernel would run
+  const char* path_env = probe_env("RDYN_GRAM_PATH");
+  if (chunk_samples <= 0 && n >= 2 && rdyn_regressor_gram_duo_supported(P) && !(path_env && !strcmp(path_env, "image")))
   {
-    // LDS-resident path (rdyn_lds_gram.hip): needs input joints in chain order (rows of a link's columns are a prefix)
-    // and four tiles inside 160 KB of LDS.
+    // wave-pair kernel (rdyn_duo_gram.hip), 2 .. 7 chain joints: needs input joints in chain order (rows of a link's columns are a
+    // prefix) and four tiles inside 160 KB of LDS.
     RdynLdsGramArgs la;
     memset(&la, 0, sizeof la);
-    // wave-pair kernel (rdyn_duo_gram.hip) by default; RDYN_GRAM_PATH=pipe / lds0 keep the single-wave kernels (A/B)
-    const bool duo = rdyn_regressor_gram_duo_supported(P) && !(path_env && (!strcmp(path_env, "lds0") || !strcmp(path_env, "pipe")));
-    const bool pipe = !duo && rdyn_regressor_gram_pipe_supported(P) && !(path_env && !strcmp(path_env, "lds0"));
     // input joints listed out of chain order: the sorted view is swept, every row's inputs read through its map
     const rdyn_chain* const co = ordered(c);
-    const int kin_pad = duo ? kin_sweeper_pad(co, 0) : 0;
-    const bool monotonic = build_lds_tile(co, 0, pipe, &la, kin_pad == 2);
+    const int kin_pad = kin_sweeper_pad(co, 0);
+    const bool monotonic = build_lds_tile(co, 0, &la, kin_pad == 2);
     const int nb = rdyn_gram_blocks_for(P);
     size_t lds_bytes = 4 * (size_t)la.tile_bytes + (kin_pad ? RDYN_KIN_XCH_BYTES(co->n_joints()) : 0);
     la.sweep_lanes = kin_pad != 0;
@@ -407,17 +400,9 @@ int rdyn_regressor_gram(const rdyn_chain* c, const rdyn_batch* b, const double* 
       la.n_samples = N;
       rec_strides(b, n, &la.in_ss, &la.in_sj);
       la.slabs = slabs;
-      if (const char* dbg = probe_env("RDYN_FUSED_DEBUG")) la.debug = atoi(dbg);
       const int64_t tiles = (N + 15) / 16;
-      int want = fused_blocks_env();
-      if (want < 1 || want > kFusedBlocks) want = kFusedBlocks;
-      const int blocks = (int)((tiles + 3) / 4 < want ? (tiles + 3) / 4 : want);
-      if (duo)
-        RDYN_HIP_TRY(rdyn_launch_regressor_gram_duo(P, la, blocks, lds_bytes, stream));
-      else if (pipe)
-        RDYN_HIP_TRY(rdyn_launch_regressor_gram_pipe(P, la, blocks, lds_bytes, stream));
-      else
-        RDYN_HIP_TRY(rdyn_launch_regressor_gram_lds(P, la, blocks, lds_bytes, stream));
+      const int blocks = (int)((tiles + 3) / 4 < kFusedBlocks ? (tiles + 3) / 4 : kFusedBlocks);
+      RDYN_HIP_TRY(rdyn_launch_regressor_gram_duo(P, la, blocks, lds_bytes, stream));
       RdynGramArgs ga;
       memset(&ga, 0, sizeof ga);
       ga.P = P;
@@ -426,14 +411,15 @@ int rdyn_regressor_gram(const rdyn_chain* c, const rdyn_batch* b, const double* 
       ga.G = G;
       ga.c = cvec;
       ga.bb = bb;
-      ga.desc_nj = duo ? c->n_joints() : 0;  // the wave-pair kernel accumulates in descending link order
+      ga.desc_nj = c->n_joints();  // the wave-pair kernel accumulates in descending link order
       RDYN_HIP_TRY(rdyn_launch_gram_finish(ga, blocks, stream));
       return RDYN_OK;
     }
   }
-  if (chunk_samples <= 0 && !probe_env("RDYN_GRAM_UNFUSED") && (!path_env || strcmp(path_env, "two")))
+  if (chunk_samples <= 0)
   {
-    // default: ONE persistent kernel, the regressor image never goes through HBM (rdyn_fused_gram.hip).
+    // chains the wave-pair kernel does not take (8 joints: four tiles do not fit the LDS): ONE persistent kernel, the regressor image
+    // stays in L2 / Infinity Cache (rdyn_fused_gram.hip).
     // chunk_samples > 0 selects the two-kernel chunked path below (kept for A/B and as the reference ordering).
     RdynFusedGramArgs fa;
     memset(&fa, 0, sizeof fa);
@@ -448,11 +434,8 @@ int rdyn_regressor_gram(const rdyn_chain* c, const rdyn_batch* b, const double* 
     for (int j = 0; j < n; ++j) fa.first_col[j] = first_col[j];
     fa.images = scratch;
     fa.slabs = slabs;
-    if (const char* dbg = probe_env("RDYN_FUSED_DEBUG")) fa.debug = atoi(dbg);
     const int64_t tiles = (N + 255) / 256;
-    int want = fused_blocks_env();
-    if (want < 1 || want > kFusedBlocks) want = kFusedBlocks;
-    const int blocks = (int)(tiles < want ? tiles : want);
+    const int blocks = (int)(tiles < kFusedBlocks ? tiles : kFusedBlocks);
     // structural zeros that the sweep never stores but the Gram still loads must read as zero
     RDYN_HIP_TRY(hipMemsetAsync(scratch, 0, sizeof(double) * (size_t)blocks * 256 * n * (P + 1), stream));
     RDYN_HIP_TRY(rdyn_launch_regressor_gram_fused(c->n_joints(), fa, blocks, stream));
@@ -557,16 +540,16 @@ int rdyn_identification_gram(const rdyn_chain* c, const rdyn_component* comps, i
   double* scratch = (double*)((char*)workspace + gram_slab_bytes(cols));
   const int64_t N = b->n_samples;
   if (N == 0) return zero_normal_equations(G, cvec, bb, cols, accumulate, stream);
-  if (c->reduced && !probe_env("RDYN_GRAM_NO_REDUCE"))
+  if (c->reduced)
     return gram_through_reduced(c, K, b, G, cvec, bb, accumulate, workspace, rdyn_identification_gram_workspace_bytes(c, comps, n_comps), companion);
   // ---- fused: regressor rows AND component columns stay in LDS (rdyn_duo_gram.hip); else the chunk image below
-  if (n >= 2 && n <= 8 && rdyn_regressor_gram_duo_supports_components(P, K) && !probe_env("RDYN_IDENT_UNFUSED"))
+  if (n >= 2 && n <= 8 && rdyn_regressor_gram_duo_supports_components(P, K))
   {
     RdynLdsGramArgs la;
     memset(&la, 0, sizeof la);
     const rdyn_chain* const co = ordered(c);  // (input joints out of chain order: the sorted view, rdyn_chain.hpp)
-    bool monotonic = build_lds_tile(co, K, false, &la);
-    if (4 * (size_t)la.tile_bytes > 160 * 1024) monotonic = build_lds_tile(co, K, false, &la, true);  // compact layout (7 joints + components)
+    bool monotonic = build_lds_tile(co, K, &la);
+    if (4 * (size_t)la.tile_bytes > 160 * 1024) monotonic = build_lds_tile(co, K, &la, true);  // compact layout (7 joints + components)
     const int nbt = K > 0 ? rdyn_gram_blocks_for(P) + 1 : rdyn_gram_blocks_for(P);  // the kernel's slab layout (XB = 1 with components)
     size_t lds_bytes = 4 * (size_t)la.tile_bytes;
     if (kin_sweeper_pad(co, K) == 4 && lds_bytes + RDYN_KIN_XCH_BYTES(co->n_joints()) <= 160 * 1024 && la.lds_stride[0] == (16 + 4) * 8)

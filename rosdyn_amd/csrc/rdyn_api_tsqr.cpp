@@ -69,7 +69,7 @@ static int cholqr_rounds(double* ws, const TsqrLayout& L, int n1, int col_shift,
   ga.bb = ga.c + (n1 - 1);
   ga.col_shift = col_shift;
   ga.slab_nb = slab_nb;
-  const int n_rounds = probe_env("RDYN_CHOLQR_ROUNDS") ? atoi(probe_env("RDYN_CHOLQR_ROUNDS")) : 2;  // A/B builds only
+  const int n_rounds = 2;
   double* const wide_sq = L.wide_doubles ? ws + L.wide : nullptr;  // factors beyond 96 columns: the dense kernels' two squares
   for (int round = 0; round < n_rounds; ++round)
   {
@@ -186,13 +186,11 @@ int rdyn_tsqr(const double* A, int64_t rows, int64_t lda, int n_cols, const doub
     return RDYN_OK;
   };
   const int64_t groups = (rows + 15) / 16;
-  const char* route_env = probe_env("RDYN_TSQR_ROUTE");  // A/B builds only: "householder" / "cholqr"
-  bool cholqr = p.cholqr_ok && groups >= kCholqrMinGroups;
-  if (route_env && p.cholqr_ok) cholqr = !strcmp(route_env, "cholqr");
+  const bool cholqr = p.cholqr_ok && groups >= kCholqrMinGroups;
   if (!cholqr) return householder(R, accumulate ? 1 : 0, nullptr, 2);
   // ---- preconditioned CholeskyQR on the matrix cores (rdyn_cholqr.hip), as the fused routes below: the Gram matrix of every S-th
   // 16-row group (about 8 192 groups), the rounds, the stand-by
-  const int64_t kSubGroups = probe_env("RDYN_CHOLQR_SUBTILES") ? atoll(probe_env("RDYN_CHOLQR_SUBTILES")) * 8 : 8192;
+  const int64_t kSubGroups = 8192;
   int64_t gs = groups / kSubGroups > 1 ? groups / kSubGroups : 1;
   if (gs > 1 && gs % 2 == 0) ++gs;  // odd: does not lock onto power-of-two periods of the rows
   const int64_t sub_groups = (groups + gs - 1) / gs;
@@ -274,7 +272,6 @@ static bool build_rect_tile(const rdyn_chain* c, int n_comp_cols, RdynLdsGramArg
   la->comp_stride = cs;
   la->comp_row_step = 128;
   la->lds_off_b = (10 * nJ + n_comp_cols) * cs;
-  la->lds_dummy_off = 0;
   la->tile_bytes = (10 * nJ + n_comp_cols + 1) * cs;
   la->n_active = n;
   for (int j = 0; j < n; ++j) la->first_col[j] = 10 * c->active[j];
@@ -371,7 +368,7 @@ static bool tsqr_plan(const rdyn_chain* c, const rdyn_component* comps, int n_co
     p->why = "chains of 1..10 input joints whose factor (after the reduction) has at most 112 columns are supported";
     return false;
   }
-  const bool tile_ok = build_lds_tile(cs, K, false, &p->la) && 4 * (size_t)p->la.tile_bytes <= 160 * 1024;
+  const bool tile_ok = build_lds_tile(cs, K, &p->la) && 4 * (size_t)p->la.tile_bytes <= 160 * 1024;
   // register-resident Householder folds: 2..7 joints, 2..6 with component columns (which must fit one 16-column slot)
   p->nc_reg = (tile_ok && p->nJ >= 2 && p->nJ <= 7) ? rdyn_regressor_tsqr_cols(p->nJ, K) : 0;
   // LDS-resident folds: the rectangular tile beside the packed factor
@@ -380,7 +377,7 @@ static bool tsqr_plan(const rdyn_chain* c, const rdyn_component* comps, int n_co
   // columns within the one extra column block, and a subsample kernel for the shape
   p->nb = (10 * p->nJ + 1 + 15) / 16 + p->xb;
   if (p->n == p->nJ && p->nJ >= 2 && p->nJ <= 7 && p->n1s <= rdyn_cholqr_max_cols_lds() && p->n1s <= 16 * p->nb &&
-      (K == 0 || rdyn_regressor_gram_duo_supports_components(10 * p->nJ, K)) && build_lds_tile(cs, K, false, &p->la))
+      (K == 0 || rdyn_regressor_gram_duo_supports_components(10 * p->nJ, K)) && build_lds_tile(cs, K, &p->la))
   {
     p->pairs = rdyn_cholqr_pairs(p->nJ, p->la.tile_bytes, p->xb);
     if (p->pairs == -1)
@@ -388,7 +385,7 @@ static bool tsqr_plan(const rdyn_chain* c, const rdyn_component* comps, int n_co
       // every wave sweeps and consumes its own COMPACT tile (k_regressor_pgram_solo): four of them fill the LDS, W stays in global memory
       RdynLdsGramArgs compact;
       memset(&compact, 0, sizeof compact);
-      build_lds_tile(cs, K, false, &compact, true);
+      build_lds_tile(cs, K, &compact, true);
       if (4 * (size_t)compact.tile_bytes <= 160 * 1024)
         p->la = compact;
       else
@@ -396,12 +393,12 @@ static bool tsqr_plan(const rdyn_chain* c, const rdyn_component* comps, int n_co
     }
     p->la_b = p->la;
     const int kin_pad = rdyn_cholqr_kin_pad(p->nJ, p->xb, p->pairs);
-    if (kin_pad && !(probe_env("RDYN_PGRAM_SWEEPER") && !strcmp(probe_env("RDYN_PGRAM_SWEEPER"), "pair")))
+    if (kin_pad)
     {
       // one lane per sample: wave 0 the link kinematics, three row waves (7 joints: four compact tiles + the exchange area, W in global memory)
       RdynLdsGramArgs kin;
       memset(&kin, 0, sizeof kin);
-      build_lds_tile(cs, K, false, &kin, kin_pad == 2);
+      build_lds_tile(cs, K, &kin, kin_pad == 2);
       const size_t need = (p->pairs == 4 ? rdyn_cholqr_w_doubles(p->nJ, p->xb) * 8 : 0) + 4 * (size_t)kin.tile_bytes + RDYN_KIN_XCH_BYTES_XV(p->nJ <= 6 ? 21 : 12);
       if (need <= 160 * 1024)
       {
@@ -412,10 +409,10 @@ static bool tsqr_plan(const rdyn_chain* c, const rdyn_component* comps, int n_co
     }
     if (p->pairs != 0)
     {
-      build_lds_tile(cs, K, false, &p->la_sub);
+      build_lds_tile(cs, K, &p->la_sub);
       if (4 * (size_t)p->la_sub.tile_bytes > 160 * 1024)
       {
-        build_lds_tile(cs, K, false, &p->la_sub, true);
+        build_lds_tile(cs, K, &p->la_sub, true);
         p->sub_compact = true;
         if (4 * (size_t)p->la_sub.tile_bytes > 160 * 1024) p->pairs = 0;
       }
@@ -574,10 +571,8 @@ static int regressor_tsqr_run(const rdyn_chain* c, const rdyn_component* comps, 
   };
   // ---- which route.  Preconditioned CholeskyQR (rdyn_cholqr.hip: the heavy pass on the matrix cores) for large batches of chains
   // whose swept form has every joint as an input joint; the Householder folds otherwise.
-  const char* route_env = probe_env("RDYN_TSQR_ROUTE");  // A/B builds only: "householder" / "cholqr"
   const int pairs = p.pairs;
-  bool cholqr = pairs != 0 && tiles >= kCholqrMinTiles;
-  if (route_env && pairs != 0) cholqr = !strcmp(route_env, "cholqr");
+  const bool cholqr = pairs != 0 && tiles >= kCholqrMinTiles;
   // where the factor of the swept chain goes: straight into R when nothing follows
   double* const R_swept = (expand || (cholqr && accumulate)) ? ws + L.r_swept : R;
   if (cholqr)
@@ -587,7 +582,7 @@ static int regressor_tsqr_run(const rdyn_chain* c, const rdyn_component* comps, 
     // A preconditioner does not have to be a backward-stable factor -- what it is worth is measured on all rows afterwards.
     RdynLdsGramArgs& la = p.la_b;
     RdynLdsGramArgs sub = p.la_sub;
-    const int64_t kSubTiles = probe_env("RDYN_CHOLQR_SUBTILES") ? atoll(probe_env("RDYN_CHOLQR_SUBTILES")) : 1024;
+    const int64_t kSubTiles = 1024;
     sub.tile_stride = (int)(tiles / kSubTiles > 1 ? tiles / kSubTiles : 1);
     if (sub.tile_stride > 1 && sub.tile_stride % 2 == 0) ++sub.tile_stride;  // odd: does not lock onto power-of-two periods of a trajectory
     const int64_t sub_tiles = (tiles + sub.tile_stride - 1) / sub.tile_stride;

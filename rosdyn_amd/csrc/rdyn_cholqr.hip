@@ -49,8 +49,8 @@ namespace
 
 typedef const __attribute__((address_space(1))) double* GlobalD;
 
-// pass B.  NPAIR wave pairs per workgroup (4, or 3 when four LDS tiles do not fit beside W: 7 joints).  Waves are dealt to the four
-// SIMDs cyclically: with 8 waves pair p = (wave p, wave p + 4) shares SIMD p; with 6 waves the pairs are (0, 4), (1, 5) and (2, 3).
+// pass B.  NPAIR wave pairs per workgroup (4, or 2).  Waves are dealt to the four SIMDs cyclically: with 8 waves pair
+// p = (wave p, wave p + 4) shares SIMD p.
 // NPAIR = 2 (7 joints + component columns: 21 accumulator tiles + 6 product tiles do not fit the 256 registers of a wave that shares
 // its SIMD): four waves, every wave alone on its SIMD with up to 512 registers, pairs (0, 2) and (1, 3); fp64 MFMA and fp64 VALU
 // exclude each other on a SIMD anyway, so two pairs on four SIMDs have the issue capacity of four pairs that
@@ -82,7 +82,8 @@ __global__ __launch_bounds__(128 * NPAIR) void k_regressor_pgram(const RdynLdsGr
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const bool sweeper = wave < NPAIR;
-  const int pair = NPAIR == 4 ? (wave & 3) : NPAIR == 2 ? (wave & 1) : (wave < 3 ? wave : (wave == 3 ? 2 : wave - 4));
+  static_assert(NPAIR == 4 || NPAIR == 2, "wave pairs per workgroup");
+  const int pair = NPAIR == 4 ? (wave & 3) : (wave & 1);
   if constexpr (!WGLOBAL)
   {
     double* const wl = (double*)lds_raw;
@@ -99,18 +100,6 @@ __global__ __launch_bounds__(128 * NPAIR) void k_regressor_pgram(const RdynLdsGr
   const int64_t trips_raw = (n_tiles - (int64_t)blockIdx.x * NPAIR + t_step - 1) / t_step;
   const int64_t trips = trips_raw > 0 ? trips_raw : 0;
 
-#ifndef RDYN_PGRAM_X_IDLE
-#define RDYN_PGRAM_X_IDLE(wave_) true
-#endif
-#ifdef RDYN_PGRAM_X_NOSWEEP  // timing experiment only (wrong numbers): the sweepers (those RDYN_PGRAM_X_IDLE names) keep the barriers and do nothing else
-  if (sweeper && RDYN_PGRAM_X_IDLE(wave))
-  {
-    if (KIN) DUO_BARRIER();
-    for (int64_t it = 0; it < trips; ++it)
-      for (int f = 0; f <= NJ; ++f) DUO_BARRIER_LDS();
-  }
-  else
-#endif
   if (sweeper && KIN)
   {
     // ================================================================ one lane per sample (doubles per sample and exchange buffer: 21 = R, the
@@ -190,9 +179,6 @@ __global__ __launch_bounds__(128 * NPAIR) void k_regressor_pgram(const RdynLdsGr
   else
   {
     // ================================================================ consumer: row group x W, then the Gram of the product
-#ifdef RDYN_CHOLQR_MFMA_PRIO
-    __builtin_amdgcn_s_setprio(RDYN_CHOLQR_MFMA_PRIO);  // A/B: the consumer is the bound of this kernel
-#endif
     const int cl = lane & 15, g = lane >> 4;
     // stage 1 operand A: lane (cl, g) supplies X[sample cl][column 16 cb1 + 4 kk + g] of the row group.  Direct chains: link f's first
     // column sits at byte 640 f^2 + 960 f of the tile, its columns are 128 f + 160 bytes apart and hold row groups 0 .. f; the measured
@@ -249,11 +235,7 @@ __global__ __launch_bounds__(128 * NPAIR) void k_regressor_pgram(const RdynLdsGr
     // the LDS -- counts on both wait counters and returns out of order with LDS reads: every wait then becomes vmcnt(0) lgkmcnt(0),
     // the rows requested ahead included)
     GlobalD wgp = (GlobalD)Wg;
-#ifdef RDYN_PGRAM_X_NOW  // timing experiment only (wrong numbers): no loads of W
-    auto wglob = [&](int blk_kk) -> double { return (double)(blk_kk + lane); };
-#else
     auto wglob = [&](int blk_kk) -> double { return (wgp + blk_kk * 64)[lane]; };
-#endif
     d4 D[NB];
     // Q(rows of group j, :) = X(rows of group j, :) W;  D[cb2] register r of lane (cl, g) = Q[sample g + 4 r][16 cb2 + cl]
     auto stage1 = [&](int j, int band) {
@@ -318,11 +300,7 @@ __global__ __launch_bounds__(128 * NPAIR) void k_regressor_pgram(const RdynLdsGr
     if (KIN) DUO_BARRIER();  // the prologue of the one-lane-per-sample sweepers (link 0 of the first tile is published)
     for (int64_t it = 0; it <= trips; ++it)
     {
-#ifdef RDYN_PGRAM_X_NOMFMA  // timing experiment only (wrong numbers): the consumers keep the barriers and do nothing else
-      const bool have = it > trips + 1;
-#else
       const bool have = it > 0;  // the tile in LDS is complete (nothing to consume while the first tile is being swept)
-#endif
 #pragma unroll
       for (int f = 0; f < NJ; ++f)
       {
@@ -491,11 +469,6 @@ constexpr int kMaxPanelN1 = 416;  // the column-panel route (rdyn_tsqr_wide, PAN
 #else
 #define STAMP(i) do { } while (0)
 #define STAMP_P(i) do { } while (0)
-#endif
-#ifdef RDYN_CHOLQR_CHOL_LDS  // A/B builds: the factorisation that keeps its matrices in LDS (rounds 3, 4)
-#define RDYN_CHOL_WITH_INVERSE chol_with_inverse_lds
-#else
-#define RDYN_CHOL_WITH_INVERSE chol_with_inverse_regs
 #endif
 constexpr int NTD = RDYN_CHOLQR_DENSE_THREADS;  // threads of the single-workgroup dense kernels (256 / 512 / 1024: 1.45 / 1.41 / 1.40 ms for the whole call at config-2 size; >= 128)
 
@@ -896,8 +869,8 @@ __global__ __launch_bounds__(NTD) void k_cholqr_precond(const double* __restrict
     STAMP_P(1);
     auto chol = [&](auto... args) {
       if constexpr (PANEL) chol_with_inverse_lds<7>(args...);
-      else if constexpr (WIDE) RDYN_CHOL_WITH_INVERSE<7>(args...);
-      else RDYN_CHOL_WITH_INVERSE<6>(args...);
+      else if constexpr (WIDE) chol_with_inverse_regs<7>(args...);
+      else chol_with_inverse_regs<6>(args...);
     };
     chol(B, A0, n1, tid, s_part, s_g, [&](int k, double d) {
       // the squared sine of the angle to the columns on the left: a Gram matrix resolves it down to ~1e-14; below 1e-10 (sine 1e-5, the
@@ -1110,8 +1083,8 @@ __global__ __launch_bounds__(NTD) void k_cholqr_factor(const double* __restrict_
   STAMP(1);
   auto chol = [&](auto... args) {
     if constexpr (PANEL) chol_with_inverse_lds<7>(args...);
-    else if constexpr (WIDE) RDYN_CHOL_WITH_INVERSE<7>(args...);
-    else RDYN_CHOL_WITH_INVERSE<6>(args...);
+    else if constexpr (WIDE) chol_with_inverse_regs<7>(args...);
+    else chol_with_inverse_regs<6>(args...);
   };
   chol(M, T, n1, tid, s_sc, s_xd, [&](int k, double d) {
     // d / g0 = the squared sine of the angle between Q(:, k) and the columns to its left; "resolved": >= 1e-12
@@ -1421,7 +1394,7 @@ hipError_t launch_pgram3(const RdynLdsGramArgs& a, const double* W, const int* r
   hipLaunchKernelGGL((k_regressor_pgram<NJ, ALLREV, NPAIR, WGLOBAL, XB, KIN>), dim3(blocks), dim3(128 * NPAIR), lds, st, a, W, run_flag);
   return hipGetLastError();
 }
-// pairs: 4 = W in LDS beside four tiles; 3 = W in LDS beside three tiles; -4 = four tiles, W read from global memory;
+// pairs: 4 = W in LDS beside four tiles; -4 = four tiles, W read from global memory;
 // 2 = two pairs on four SIMDs; 1 = no pairs: every wave sweeps and consumes its own (compact) tile (k_regressor_pgram_solo)
 template <int NJ>
 hipError_t launch_pgram(const RdynLdsGramArgs& a, const double* W, const int* run_flag, int blocks, int pairs, hipStream_t st)
@@ -1433,7 +1406,7 @@ hipError_t launch_pgram(const RdynLdsGramArgs& a, const double* W, const int* ru
     {
       if (pairs == 2)
         return a.all_revolute ? launch_pgram3<NJ, true, 2, false, 1>(a, W, run_flag, blocks, st) : launch_pgram3<NJ, false, 2, false, 1>(a, W, run_flag, blocks, st);
-      if (pairs == -1 || pairs == 1) return rdyn_launch_regressor_pgram_solo(a, W, run_flag, blocks, pairs, st);  // rdyn_pgram_solo.hip
+      if (pairs == -1) return rdyn_launch_regressor_pgram_solo(a, W, run_flag, blocks, pairs, st);  // rdyn_pgram_solo.hip
     }
     if constexpr (NJ <= 6)
     {
@@ -1460,8 +1433,6 @@ hipError_t launch_pgram(const RdynLdsGramArgs& a, const double* W, const int* ru
     return a.all_revolute ? launch_pgram3<NJ, true, 4, false>(a, W, run_flag, blocks, st) : launch_pgram3<NJ, false, 4, false>(a, W, run_flag, blocks, st);
   if constexpr (NJ >= 7)
   {
-    if (pairs == 3)
-      return a.all_revolute ? launch_pgram3<NJ, true, 3, false>(a, W, run_flag, blocks, st) : launch_pgram3<NJ, false, 3, false>(a, W, run_flag, blocks, st);
     if (pairs == -4)
       return a.all_revolute ? launch_pgram3<NJ, true, 4, true>(a, W, run_flag, blocks, st) : launch_pgram3<NJ, false, 4, true>(a, W, run_flag, blocks, st);
   }
@@ -1493,18 +1464,12 @@ int rdyn_cholqr_pairs(int n_joints, int tile_bytes, int xb)
     // -1: k_regressor_pgram_solo, four waves that sweep and consume their own COMPACT tile, W from global memory (the caller checks that
     // four compact tiles fit and asks again with tile_bytes < 0 if they do not); 2: two sweeper / consumer pairs on four SIMDs, W in LDS
     // beside two tiles.  Measured at 14 component columns, N = 1e6 (tools/r4_ab_ident.sh): 3.02 ms (-1), 3.48 (three waves + W in LDS), 3.62 (2)
-#ifndef RDYN_CHOLQR_TWO_PAIRS
     if (tile_bytes > 0) return -1;
-#endif
     const size_t tb = (size_t)(tile_bytes < 0 ? -tile_bytes : tile_bytes);
     return wb + 2 * tb <= 160 * 1024 ? 2 : 0;
   }
   if (wb + 4 * (size_t)tile_bytes <= 160 * 1024) return 4;
-#ifdef RDYN_CHOLQR_W_LDS3
-  if (wb + 3 * (size_t)tile_bytes <= 160 * 1024) return 3;
-#else
   if (4 * (size_t)tile_bytes <= 160 * 1024) return -4;  // W from global memory (7 joints)
-#endif
   return 0;
 }
 

@@ -1,7 +1,7 @@
 // rdyn_duo_gram.hip -- regressor rows -> fp64-MFMA Gram with the two instruction streams on TWO co-resident waves.
 //
-// rdyn_pipe_gram.hip interleaves the fp64 VALU sweep and the fp64 MFMA k-steps inside ONE wave.  Measured on gfx950
-// (tools/fp64_issue.hip, profiles/r2/fp64_issue.txt): a lone wave pays ~5 cycles per fp64 VALU instruction, 83 per
+// A kernel that interleaves the fp64 VALU sweep and the fp64 MFMA k-steps inside ONE wave (the retired single-wave kernels, see
+// CHANGELOG.md) loses to the issue rules of gfx950 (tools/fp64_issue.hip, profiles/r2/fp64_issue.txt): a lone wave pays ~5 cycles per fp64 VALU instruction, 83 per
 // v_mfma_f64_16x16x4_f64 and ~80 more every time its stream switches between the two, and every scalar / LDS / 32-bit
 // instruction of the sweep (40 % of its stream) takes an issue slot of its own: 31 k cycles per 16-sample tile.
 // Here a 512-thread workgroup holds four PAIRS of waves (wave p and wave p + 4 land on the same SIMD: a workgroup's waves are
@@ -14,9 +14,8 @@
 //     no later group reads (group j' > j only touches columns of links >= j').
 // One s_barrier per link plus one per tile keeps the two in step; the hardware interleaves the two streams cycle by cycle,
 // each role has its own register budget (the kernel fits 256 registers = two waves per SIMD), and scalar / LDS / address
-// instructions of one wave issue under the other's fp64 work.  Same tile layout, operand order and epilogue arithmetic as
-// rdyn_lds_gram.hip / rdyn_pipe_gram.hip: results are bit-identical to them.
-// Requirements (else rdyn_regressor_gram uses the single-wave kernels): 2 <= chain joints <= 7, input joints in chain order,
+// instructions of one wave issue under the other's fp64 work.
+// Requirements (else rdyn_regressor_gram uses rdyn_fused_gram.hip): 2 <= chain joints <= 7, input joints in chain order,
 // four tiles inside 160 KB of LDS.
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -109,9 +108,6 @@ __global__ __launch_bounds__(KIN ? 768 : 512) void k_regressor_gram_duo(const Rd
   {
     // ================================================================ sweeper: 16 samples x 4 lanes, rows 2k, 2k + 1
     ChainPtr c = as_const(fa.chain);
-#ifdef RDYN_DUO_SWEEP_PRIO
-    __builtin_amdgcn_s_setprio(RDYN_DUO_SWEEP_PRIO);
-#endif
     const int s_loc = lane >> 2, k = lane & 3;
     // lane k of a sample's quad owns regressor rows k (slot 0) and k + 4 (slot 1) -- the same split as the inputs it fetches.
     // Rows >= 4 belong to joints that sit at chain index >= fB: before link fB slot 1 is identically zero and is skipped
@@ -197,9 +193,6 @@ __global__ __launch_bounds__(KIN ? 768 : 512) void k_regressor_gram_duo(const Rd
   else
   {
     // ================================================================ consumer: MFMA k-steps of the previous tile
-#ifdef RDYN_DUO_MFMA_PRIO
-    __builtin_amdgcn_s_setprio(RDYN_DUO_MFMA_PRIO);
-#endif
     const int cl = lane & 15, g = lane >> 4;
     // per column block: LDS offset of MY column (for row group 0) and the row groups [collo, colm) it stores
     int colbase[NB], colm[NB], collo[NB];
@@ -261,17 +254,7 @@ __global__ __launch_bounds__(KIN ? 768 : 512) void k_regressor_gram_duo(const Rd
 #pragma unroll
           for (int rb = 0; rb <= cb; ++rb)
           {
-#ifdef RDYN_DUO_4X4_TIMING  // timing experiment only (wrong numbers): the issue cost of four (three on the diagonal) 4x4x4_4b MFMAs per tile k-step
-            if (cb <= band)
-            {
-              acc[ti][0] = __builtin_amdgcn_mfma_f64_4x4x4f64(op[rb][t], op[cb][t], acc[ti][0], 0, 0, 0);
-              acc[ti][1] = __builtin_amdgcn_mfma_f64_4x4x4f64(op[rb][t], op[cb][t], acc[ti][1], 0, 0, 0);
-              acc[ti][2] = __builtin_amdgcn_mfma_f64_4x4x4f64(op[rb][t], op[cb][t], acc[ti][2], 0, 0, 0);
-              if (rb != cb) acc[ti][3] = __builtin_amdgcn_mfma_f64_4x4x4f64(op[rb][t], op[cb][t], acc[ti][3], 0, 0, 0);
-            }
-#else
             if (cb <= band) acc[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(op[rb][t], op[cb][t], acc[ti], 0, 0, 0);
-#endif
             ++ti;
           }
       }

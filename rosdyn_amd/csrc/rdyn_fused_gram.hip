@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void k_regressor_gram_fused(const RdynFusedGra
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
   {
     // ---------------- phase 1: sweep of this tile's samples into the image
-    if (!(fa.debug & 1) || tile == (int64_t)blockIdx.x)  // debug bit 0: timing-only run of phase 2 (image written once)
+    if (!(fa.debug & 1) || tile == (int64_t)blockIdx.x)  // always taken: fa.debug is 0 (rdyn_kernels.h)
     {
       RdynSweepArgs a = fa.sweep;
       const int64_t s0 = tile * 256;
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void k_regressor_gram_fused(const RdynFusedGra
     __syncthreads();
 
     // ---------------- phase 2: Gram k-steps over the tile's n * 256 rows (16-row groups, 4 waves)
-    if (!(fa.debug & 2))  // debug bit 1: timing-only run of phase 1
+    if (!(fa.debug & 2))  // always taken, as above
     {
       const int n_groups = n * 16;
       // three 16-row groups in flight per wave (the image is read from L2 / Infinity Cache at one wave per SIMD:

@@ -1,5 +1,5 @@
-// rdyn_gram_common.h -- pieces shared by the Gram kernels (rdyn_gram.hip, rdyn_fused_gram.hip, rdyn_lds_gram.hip,
-// rdyn_pipe_gram.hip)
+// rdyn_gram_common.h -- pieces shared by the Gram kernels (rdyn_gram.hip, rdyn_fused_gram.hip, rdyn_panel_gram.hip,
+// rdyn_cholqr.hip)
 #ifndef RDYN_GRAM_COMMON_H
 #define RDYN_GRAM_COMMON_H
 #include <hip/hip_runtime.h>

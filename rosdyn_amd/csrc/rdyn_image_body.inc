@@ -26,9 +26,7 @@
   constexpr int SPI = 64 / MAXC;                     // samples one copy-out instruction covers
   constexpr int NIT = (64 + SPI - 1) / SPI;
   extern __shared__ __attribute__((aligned(16))) char stage_wg[];
-  // IMAGE_WAVES waves per workgroup (1 in the shipped build; 4 = A/B variant RDYN_STACKED_WG256: the four waves' pieces of a column
-  // are aligned in time by a workgroup barrier): every wave has its own staging area
-  char* const stage = stage_wg + (IMAGE_WAVES > 1 ? (threadIdx.x >> 6) * (STACKED ? CPF * 64 * NA * 8 : 64 * PITCH) : 0);
+  char* const stage = stage_wg;  // one wave per workgroup: the staging area is the wave's
   ChainPtr c = as_const(a.chain);
   const int lane = threadIdx.x & 63;
   const int64_t s_wave = (int64_t)blk * 64;
@@ -191,9 +189,6 @@
 #pragma unroll
   for (int f = 0; f < NJ; ++f)
   {
-#ifdef RDYN_IMAGE_LINK_SCHED_BARRIER
-    __builtin_amdgcn_sched_barrier(0);
-#endif
     JointRef J = c->j[f];
     const int type_rt = J.type;
     const bool mov = MAP >= 0 ? rmap[f] >= 0 : !((FIX >> f) & 1u);     // input joint (pattern checked by the launcher)
@@ -379,11 +374,9 @@
           *(double*)(stg + spos(f, p, l)) = y[p];
           if (!STACKED && f == 0 && l == 0) h0[p] = y[p];
         }
-#ifndef RDYN_IMAGE_NO_TAU_PIN
         // pin the running torque here: tau is only read in the conditional store at the very end, and LLVM otherwise SINKS the last
         // links' y * pi chains into that block, keeping their sixty y values alive (and spilled) across the copy-out
         asm volatile("" : "+v"(tl));
-#endif
         tau[l] = tl;
       }
       else
@@ -395,11 +388,7 @@
       }
     }
     // ---- copy out the lines completed by this link: image bytes [Fp, Fc), Fx = E - ((m + E) mod 128) (everything at the last link)
-#ifdef RDYN_STACKED_WG256_NOBARRIER
     wave_lds_fence();
-#else
-    if (IMAGE_WAVES > 1) __syncthreads(); else wave_lds_fence();
-#endif
     if constexpr (STACKED)
     {
       // the wave owns 64 NA consecutive doubles of every column: 512 NA bytes = 4 NA whole lines when the column is line aligned
@@ -407,25 +396,15 @@
 #pragma unroll
       for (int pq = 0; pq < CPF; ++pq)
       {
-#ifdef RDYN_STACKED_ROTATE
-        const int pr = (pq + (int)(blk % (unsigned)CPF)) % CPF;  // A/B variant: every workgroup starts the flush's columns somewhere else
-#else
-        const int pr = pq;
-#endif
-        const int pp = p_lo + pr;
+        const int pp = p_lo + pq;
         char* const ycol = (char*)(a.Y + (int64_t)(10 * f + pp) * a.y_sc + s_wave * NA);  // wave-uniform
 #pragma unroll
         for (int it = 0; it < (32 * NA + 63) / 64; ++it)
         {
           const uint32_t off = (uint32_t)(it * 64 + lane) * 16u;
-#ifdef RDYN_IMAGE_NO_COPYOUT
-          // timing experiment only (wrong results): how long does the one-thread-per-sample sweep + LDS staging take by itself?
-          if (off < lim && a.n_samples < 0)
-#else
           if (off < lim)
-#endif
           {
-            const d2a v = *(const d2a*)(stage + pr * (64 * NA * 8) + off);
+            const d2a v = *(const d2a*)(stage + pq * (64 * NA * 8) + off);
             if (off + 16u <= lim)
             {
               if (NT) __builtin_nontemporal_store((d2u)v, (d2u*)(ycol + off));

@@ -49,27 +49,14 @@ __device__ __forceinline__ void wave_lds_fence()
 // pieces a link's ten columns are flushed in (1, 2 or 5).  One piece when a copy-out instruction already covers >= 2 samples
 // (NA <= 6: 64 lanes / 8 * ceil(80 NA / 128) chunks); five pieces beyond, where the ring of a whole link leaves 3 waves per CU and
 // one sample per store instruction (measured, 1e6 samples, NA = 7: 1078 / 859 / 772 us with 1 / 2 / 5 pieces; NA = 6: 527 / 555 /
-// 540 us; NA = 8: 942 / 927 / 945 us -- profiles/r2/image_ab.txt).  -DRDYN_IMAGE_FLUSHES=k forces one value (A/B builds).
-constexpr int image_flushes(int na)
-{
-#ifdef RDYN_IMAGE_FLUSHES
-  (void)na;
-  return RDYN_IMAGE_FLUSHES;
-#else
-  return 64 / (((80 * na + 127) / 128) * 8) >= 2 ? 1 : 5;
-#endif
-}
+// 540 us; NA = 8: 942 / 927 / 945 us -- profiles/r2/image_ab.txt).
+constexpr int image_flushes(int na) { return 64 / (((80 * na + 127) / 128) * 8) >= 2 ? 1 : 5; }
 
 #ifndef RDYN_IMAGE_WAVES
 #define RDYN_IMAGE_WAVES(STACKED_, FIX_, NJ_) ((!(STACKED_) && (FIX_) == 0 && (NJ_) <= 8) ? 2 : 1)
 #endif
 #ifndef RDYN_STACKED_FLUSHES
 #define RDYN_STACKED_FLUSHES 1  // pieces a link's ten columns are staged and copied out in (stacked layout): 1, 2 or 5
-#endif
-#ifdef RDYN_STACKED_WG256
-#define RDYN_IMAGE_WG_WAVES(STACKED_) ((STACKED_) ? 4 : 1)
-#else
-#define RDYN_IMAGE_WG_WAVES(STACKED_) 1
 #endif
 // MAP >= 0 (per-sample images; FIX == 0): the input joints of the chain are described at RUN time -- a.row_map[f] = the caller's row of
 // chain joint f (where its q / Dq / DDq are read, its torque is written, and the row of the image its values land in), -1 for the MAP
@@ -80,20 +67,13 @@ constexpr int image_flushes(int na)
 // joint), the image holds the blocks of all a.expand_n links of the full chain: see rdyn_image_body.inc.
 template <int NJ, unsigned FIX, bool NT, bool STACKED, int MAP = -1, bool EXPAND = false>
 // (the row-mapped 7-joint chain does not fit the 256 registers of two waves per SIMD: 444 B of scratch, 868 us per 1e6 at 7 joints)
-__global__ __launch_bounds__(64 * RDYN_IMAGE_WG_WAVES(STACKED), (RDYN_IMAGE_WG_WAVES(STACKED) > 1 || (MAP == 0 && NJ == 7)) ? 1 : RDYN_IMAGE_WAVES(STACKED, FIX, NJ)) void k_image_sweep(const RdynSweepArgs a)
+__global__ __launch_bounds__(64, (MAP == 0 && NJ == 7) ? 1 : RDYN_IMAGE_WAVES(STACKED, FIX, NJ)) void k_image_sweep(const RdynSweepArgs a)
 {
   static_assert(MAP < 0 || (FIX == 0 && !STACKED && MAP < NJ), "row maps: per-sample images, the fixed joints in the map");
-  constexpr int IMAGE_WAVES = RDYN_IMAGE_WG_WAVES(STACKED);
-#ifdef RDYN_STACKED_XCD_REMAP
-  // A/B variant: workgroups are dealt to the 8 XCDs round-robin; give every XCD one contiguous eighth of the batch instead
-  const unsigned per = (gridDim.x + 7u) / 8u;
-  const unsigned bx = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-#else
   // a.blk_mul != 0: workgroup b sweeps the 64 samples of chunk (b * blk_mul) mod grid (blk_mul coprime to the grid: a bijection) -- the
-  // waves that run at the same time are then spread over the whole batch instead of one narrow window of it
-  const unsigned bx = a.blk_mul ? (unsigned)(((uint64_t)blockIdx.x * (uint64_t)a.blk_mul) % (uint64_t)gridDim.x) : blockIdx.x;
-#endif
-  const unsigned blk = bx * IMAGE_WAVES + (IMAGE_WAVES > 1 ? (threadIdx.x >> 6) : 0);
+  // waves that run at the same time are then spread over the whole batch instead of one narrow window of it.  (One wave per workgroup:
+  // the grid IS the number of 64-sample chunks the host chose blk_mul for.)
+  const unsigned blk = a.blk_mul ? (unsigned)(((uint64_t)blockIdx.x * (uint64_t)a.blk_mul) % (uint64_t)gridDim.x) : blockIdx.x;
 #include "rdyn_image_body.inc"
 }
 
@@ -106,7 +86,6 @@ __global__ __launch_bounds__(64, RDYN_IMAGE_WAVES(STACKED, FIX, NJ)) void k_imag
 #pragma clang diagnostic ignored "-Wold-style-cast"
   const RDYN_CONST_AS RdynSweepArgs& a = *((const RDYN_CONST_AS RdynSweepArgs*)table + blockIdx.y);
 #pragma clang diagnostic pop
-  constexpr int IMAGE_WAVES = 1;
   constexpr int MAP = -1;
   constexpr bool EXPAND = false;
   const unsigned blk = blockIdx.x;
@@ -117,25 +96,11 @@ template <int NJ, unsigned FIX, bool STACKED, int MAP = -1, bool EXPAND = false>
 hipError_t launch_image(const RdynSweepArgs& a, hipStream_t st)
 {
   constexpr int NA = MAP >= 0 ? NJ - MAP : NJ - __builtin_popcount(FIX);
-  constexpr int WV = RDYN_IMAGE_WG_WAVES(STACKED);
-  const dim3 grid((unsigned)((a.n_samples + 64 * WV - 1) / (64 * WV)));
+  const dim3 grid((unsigned)((a.n_samples + 63) / 64));
   constexpr int runf = (10 / image_flushes(NA)) * NA * 8, w = ((runf + 15) / 16) * 16 + 128, pitch = w + ((w / 16) % 2 ? 32 : 16);
-  size_t lds = (STACKED ? (size_t)(10 / RDYN_STACKED_FLUSHES) * 64 * NA * 8 : (size_t)64 * pitch) * WV;
-#ifdef RDYN_IMAGE_LDS_FORCE
-  lds = RDYN_IMAGE_LDS_FORCE;  // timing experiment: limits the waves per CU through the LDS request
-#endif
+  const size_t lds = STACKED ? (size_t)(10 / RDYN_STACKED_FLUSHES) * 64 * NA * 8 : (size_t)64 * pitch;
   // nontemporal copy-out: the lines are written whole, once, and never re-read (A/B, same box: 0.55 ms vs 0.72 ms per 1e6)
-#ifdef RDYN_IMAGE_PLAIN_STORES
-  constexpr bool kNT = false;
-#else
-  constexpr bool kNT = true;
-#endif
-  if constexpr (WV > 1)
-  {
-    hipError_t e = opt_in_lds_once<k_image_sweep<NJ, FIX, kNT, STACKED, MAP, EXPAND>>();
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL((k_image_sweep<NJ, FIX, kNT, STACKED, MAP, EXPAND>), grid, dim3(64 * WV), lds, st, a);
+  hipLaunchKernelGGL((k_image_sweep<NJ, FIX, true, STACKED, MAP, EXPAND>), grid, dim3(64), lds, st, a);
   return hipGetLastError();
 }
 template <int NJ, unsigned FIX, bool STACKED>

@@ -322,7 +322,8 @@ struct RdynFusedGramArgs
   int first_col[RDYN_MAX_SWEPT_JOINTS];
   double* images;        // [blocks][(P + 1) * n * 256] per-workgroup tile images
   double* slabs;         // [blocks][NT * 256] per-workgroup Gram slabs
-  int debug;             // timing experiments only (RDYN_FUSED_DEBUG): bit 0 skip phase 1 after the first tile, bit 1 skip phase 2
+  int debug;             // always 0 (no host code sets it; the phase ablation it steered is closed): the kernel's two reads stay because
+                         // without them hipcc allocates every instantiation differently (CHANGELOG.md, "Retire closed experiments")
 };
 hipError_t rdyn_launch_regressor_gram_fused(int n_joints, const RdynFusedGramArgs& a, int blocks, hipStream_t st);
 
@@ -334,7 +335,8 @@ struct RdynComponent
   double min_velocity, max_velocity;
   double parameters[3];
 };
-// LDS-resident regressor -> Gram kernel (rdyn_lds_gram.hip): 16 samples per wave, packed column-major tile in LDS
+// LDS-resident regressor -> Gram / R-factor kernels (rdyn_duo_gram.hip, rdyn_cholqr.hip, rdyn_pgram_solo.hip, rdyn_tsqr*.hip): 16 samples
+// per tile, packed column-major tile in LDS
 struct RdynLdsGramArgs
 {
   const RdynChainConst* chain;
@@ -355,10 +357,10 @@ struct RdynLdsGramArgs
   int lds_stride[RDYN_MAX_SWEPT_JOINTS];     // per link: bytes between its columns = (16 m_f + 4) * 8
   int lds_m[RDYN_MAX_SWEPT_JOINTS];          // per link: number of input joints whose rows can be non-zero (stored rows = 16 m_f)
   int lds_off_b;                       // byte offset of column P (measured torque), 16 n rows
-  int lds_dummy_off;                   // pipelined kernel only: 64 x 8 bytes where lanes drop rows a link does not store
+  int reserved0;                       // always 0, read by nothing: keeps the kernel-argument offsets of every kernel that takes the struct
   int tile_bytes;                      // one wave's tile
   double* slabs;
-  int debug;                           // timing experiments only (RDYN_FUSED_DEBUG): bit 0 sweep only the first tile, bit 1 no Gram phase
+  int reserved1;                       // as reserved0
   int tile_stride;                     // wave-pair kernels: sweep every tile_stride-th 16-sample tile only (0 / 1 = all): the subsample pass of the preconditioned route
   const int* run_flag;                 // k_regressor_tsqr and its tree only: null, or a device word -- 0 = leave at once
   // wave-pair kernel only (rdyn_duo_gram.hip): the per-joint component columns [Y | C | tau_meas] of rdyn_identification_gram.
@@ -371,11 +373,7 @@ struct RdynLdsGramArgs
   signed char comp_col_row[96];        // per component column: the input joint (row group) it belongs to
   RdynComponent comps[RDYN_MAX_COMPONENTS];
 };
-hipError_t rdyn_launch_regressor_gram_lds(int n_cols, const RdynLdsGramArgs& a, int blocks, size_t lds_bytes, hipStream_t st);
-// the same kernel software-pipelined inside the wave (rdyn_pipe_gram.hip): chains of 2..6 joints
-bool rdyn_regressor_gram_pipe_supported(int n_cols);
-hipError_t rdyn_launch_regressor_gram_pipe(int n_cols, const RdynLdsGramArgs& a, int blocks, size_t lds_bytes, hipStream_t st);
-// the two streams on two co-resident waves (rdyn_duo_gram.hip): chains of 2..7 joints, 512-thread workgroups
+// sweep and MFMA streams on two co-resident waves (rdyn_duo_gram.hip): chains of 2..7 joints, 512-thread workgroups
 bool rdyn_regressor_gram_duo_supported(int n_cols);
 // doubles per sample and exchange buffer: up to 6 joints 30 (the b-matrix too; the kernel uses 21 of them without component columns), 12 at 7
 #define RDYN_KIN_XCH_BYTES(n_joints) (2 * ((n_joints) <= 6 ? 30 : 12) * 64 * 8)

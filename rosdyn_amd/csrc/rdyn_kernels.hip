@@ -61,13 +61,8 @@ enum
 #define RDYN_BODY_EXIT return
 
 // one chain, one batch: grid.x = ceil(N / 256)
-#ifdef RDYN_LOCAL_WAVES  // A/B builds only: an occupancy target for the one-thread-per-sample sweeps
-#define RDYN_LOCAL_ATTR __attribute__((amdgpu_waves_per_eu(RDYN_LOCAL_WAVES, RDYN_LOCAL_WAVES)))
-#else
-#define RDYN_LOCAL_ATTR
-#endif
 template <int NJ, int MODE>
-__global__ __launch_bounds__(256) RDYN_LOCAL_ATTR void k_local_sweep(const RdynSweepArgs a)
+__global__ __launch_bounds__(256) void k_local_sweep(const RdynSweepArgs a)
 {
   const unsigned blk = blockIdx.x;
   constexpr double* expand_tile = nullptr;  // (the staged expanding sweep's LDS tile: k_expand_staged)
@@ -76,7 +71,7 @@ __global__ __launch_bounds__(256) RDYN_LOCAL_ATTR void k_local_sweep(const RdynS
 // torque / inertia in the sample-major layout (a.staged = doubles per record): one wave per workgroup, the wave's 64 records through its
 // LDS tile (64 (rec | 1) doubles of dynamic LDS), written in whole lines
 template <int NJ, int MODE>
-__global__ __launch_bounds__(64) RDYN_LOCAL_ATTR void k_local_sweep_rec(const RdynSweepArgs a)
+__global__ __launch_bounds__(64) void k_local_sweep_rec(const RdynSweepArgs a)
 {
   const unsigned blk = blockIdx.x;
   constexpr double* expand_tile = nullptr;
@@ -531,12 +526,9 @@ hipError_t launch_base_nj(const RdynKinArgs& a, hipStream_t st)
     if (a.J && (size_t)64 * (size_t)((6 * a.n_active) | 1) * 8 > small) small = (size_t)64 * (size_t)((6 * a.n_active) | 1) * 8;
     lds += small;
     // all frames (720 B per sample at 6 joints): FOUR waves per CU are the optimum -- 118-122 us per 1e6 against 129-133 at five to seven
-    // (tools/build_variant.sh ... -DRDYN_STAGE_LDS_PAD, profiles/r6/stage_occupancy.txt; the twist levels, a third of the bytes per wave
+    // (profiles/r6/stage_occupancy.txt; the twist levels, a third of the bytes per wave
     // behind a longer recursion, want every wave they can get: 90 / 99 / 122 us at 8 / 6 / 4 waves) -- asked for through the LDS request
     if (a.T_links && lds < kFramesStageLds) lds = kFramesStageLds;
-#ifdef RDYN_STAGE_LDS_PAD  // timing experiment: fewer waves per CU through the LDS request
-    lds += RDYN_STAGE_LDS_PAD;
-#endif
     const unsigned g64 = (unsigned)((a.n_samples + 63) / 64);
     if (a.dtwists) hipLaunchKernelGGL((k_base_sweep_staged<NJ, 3>), dim3(g64), dim3(64), lds, st, a);
     else if (a.twists) hipLaunchKernelGGL((k_base_sweep_staged<NJ, 2>), dim3(g64), dim3(64), lds, st, a);
@@ -549,11 +541,7 @@ hipError_t launch_base_nj(const RdynKinArgs& a, hipStream_t st)
   if (a.dtwists) hipLaunchKernelGGL((k_base_sweep<NJ, 3>), dim3(grid), dim3(256), 0, st, a);
   else if (a.twists) hipLaunchKernelGGL((k_base_sweep<NJ, 2>), dim3(grid), dim3(256), 0, st, a);
   else if (a.J) hipLaunchKernelGGL((k_base_sweep<NJ, 1>), dim3(grid), dim3(256), 0, st, a);
-#ifdef RDYN_BASE0_LDS_PAD  // timing experiment: fewer waves per CU for the frames-only level through an LDS request
-  else hipLaunchKernelGGL((k_base_sweep<NJ, 0>), dim3(grid), dim3(256), RDYN_BASE0_LDS_PAD, st, a);
-#else
   else hipLaunchKernelGGL((k_base_sweep<NJ, 0>), dim3(grid), dim3(256), 0, st, a);
-#endif
   return hipGetLastError();
 }
 

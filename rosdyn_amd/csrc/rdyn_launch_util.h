@@ -28,13 +28,6 @@
   RDYN_NJ_CASES_8_10(CALL)              \
   default: return hipErrorInvalidValue; \
   }
-#define RDYN_DISPATCH_JOINTS_2_10(nj, CALL) \
-  switch (nj)                               \
-  {                                         \
-  RDYN_NJ_CASES_2_7(CALL)                   \
-  RDYN_NJ_CASES_8_10(CALL)                  \
-  default: return hipErrorInvalidValue;     \
-  }
 #define RDYN_DISPATCH_JOINTS_2_7(nj, CALL) \
   switch (nj)                              \
   {                                        \

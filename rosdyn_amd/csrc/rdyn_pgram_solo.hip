@@ -294,15 +294,11 @@ int rdyn_cholqr_solo_col_shift(int n_joints, int n_comp_cols)
   return room >= 11 ? 11 : (room >= 4 ? 4 : 0);
 }
 
-// pairs: -1 = four waves, W from global memory; 1 = (A/B builds) three waves, W in LDS beside their tiles.  a.col_shift as above.
+// pairs: -1 = four waves, W from global memory.  a.col_shift as above.
 hipError_t rdyn_launch_regressor_pgram_solo(const RdynLdsGramArgs& a, const double* W, const int* run_flag, int blocks, int pairs, hipStream_t st)
 {
   constexpr int NJ = 7;
   if (a.n_active != NJ) return hipErrorInvalidValue;
-#ifdef RDYN_CHOLQR_SOLO3
-  if (pairs == 1)
-    return a.all_revolute ? launch_pgram_solo<NJ, true, 3, false, -1>(a, W, run_flag, blocks, st) : launch_pgram_solo<NJ, false, 3, false, -1>(a, W, run_flag, blocks, st);
-#endif
   if (pairs != -1) return hipErrorInvalidValue;
   if (a.all_revolute)
   {

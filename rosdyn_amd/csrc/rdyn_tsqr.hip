@@ -4,7 +4,7 @@
 //
 //   leaf     every wave keeps a running upper-triangular R in registers and folds row blocks into it by Householder reflections:
 //            R <- qr([R ; block]).  A block is the LDS tile of 16 samples that the wave's own row-pair sweep has just produced
-//            (rdyn_regressor_tsqr; packed column-major tile of rdyn_lds_gram.hip: the columns of link f only hold the rows of the
+//            (rdyn_regressor_tsqr; packed column-major tile of rdyn_duo_gram.hip: the columns of link f only hold the rows of the
 //            joints that can be non-zero there) or 64 rows of a device matrix (rdyn_tsqr).  Block and factor are spread over the
 //            wave in two dimensions (16 column slots x 4 row groups, tsqr_fold2d below); a column step exchanges one column
 //            through LDS and sums the row groups with v_permlane16/32_swap.  A wave never touches another wave's data in the loop.

@@ -42,7 +42,8 @@ def test_regressor_and_gram_replay_from_a_graph():
 
 
 def test_pipelined_gram_ik_and_wrench_replay_from_a_graph():
-    """The fused (LDS / pipelined) Gram path, the staged IK launches and the wrench sweep are capturable too."""
+    """The fused Gram path (6 joints: the wave-pair kernel k_regressor_gram_duo + k_gram_finish), the staged IK launches and the wrench
+    sweep are capturable too."""
     torch = pytest.importorskip("torch")
     from rosdyn_amd import Chain
     from rosdyn_amd._lib import lib

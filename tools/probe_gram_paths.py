@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""GPU probe: the Gram paths on the same box -- fused persistent kernel vs the two-kernel chunked path."""
+"""GPU probe: the three Gram routes on the same box -- wave-pair kernel (default), global-image persistent kernel, two-kernel chunked
+path.  The second needs a library whose rdyn_api_gram.cpp was built with -DRDYN_ENABLE_PROBES (tools/build_variant.sh, selected by
+RDYN_LIB_PATH): the shipped library ignores RDYN_GRAM_PATH and that row then repeats the default."""
 import os
 import sys
 
@@ -19,7 +21,7 @@ for name, urdf, base, tool, N in (("cfg2", "ur10_like.urdf", "base_link", "wrist
     ref = None
     # (a third variant -- the two kernels software-pipelined over two images and a helper stream -- measured 1.50 ms vs
     #  1.41 ms serial vs 1.12 ms fused at n = 6, N = 1e6 and was removed)
-    for label, chunk, env in (("lds tile (default)", 0, {}), ("global image", 0, {"RDYN_GRAM_PATH": "image"}),
+    for label, chunk, env in (("wave pair (default)", 0, {}), ("global image", 0, {"RDYN_GRAM_PATH": "image"}),
                               ("two kernels chunk=262144", 262144, {})):
         for k, v in env.items():
             os.environ[k] = v
@@ -28,7 +30,7 @@ for name, urdf, base, tool, N in (("cfg2", "ur10_like.urdf", "base_link", "wrist
         t = timeit(lambda: chain.getRegressorGram(q, dq, ddq, tm, layout="element", chunk_samples=chunk, out=out, workspace=ws), reps=5, warm=2)
         if ref is None:
             ref = out[0].clone()
-        print("%s %-26s %8.1f us -> %.3e evals/s   rel diff vs fused %.1e" % (name, label, t * 1e6, N / t, float((out[0] - ref).norm() / ref.norm())))
+        print("%s %-26s %8.1f us -> %.3e evals/s   rel diff vs default %.1e" % (name, label, t * 1e6, N / t, float((out[0] - ref).norm() / ref.norm())))
         for k in env:
             del os.environ[k]
         del ws
