@@ -128,6 +128,17 @@ int rdyn_chain_from_urdf(const char* urdf_xml, const char* base_link, const char
 int rdyn_chain_from_desc(const rdyn_chain_desc* desc, rdyn_chain** out);
 /* Chain::clone() primitives_impl.h:552 -- an independent deep copy */
 int rdyn_chain_clone(const rdyn_chain* chain, rdyn_chain** out);
+/* The chain with other inertial parameters (no reference counterpart: what an identification loop needs to try its next iterate).
+ * pi holds 10 * rdyn_chain_joints_number doubles (HOST pointer) in the order and convention of rdyn_nominal_parameters:
+ * [m, m c, Ixx Ixy Ixz Iyy Iyz Izz about the link origin] per child link.  *out is an independent chain equal to
+ * rdyn_chain_clone(chain) in everything else -- joints, limits, gravity, the base link, the current input-joint selection and order --
+ * with its own reduced companion, sorted view and expansion blocks; no device copy is shared and `chain` is not touched.
+ * The parameters are STORED AS GIVEN, not converted to a link description: rdyn_nominal_parameters of the new chain returns the very
+ * bits of pi, and a massless link with a first moment or an inertia (which rdyn_link_desc cannot express) is accepted.
+ * rdyn_chain_link_parameters then reports mass = pi[0] and cog = (m c) / m, the link origin for a massless link.
+ * Physical consistency (positive mass, positive-definite inertia) is not checked: the dynamics calls report -1 per sample where M is not
+ * positive definite.  A NULL argument or an entry that is not finite is RDYN_ERR_INVALID_ARGUMENT (the message names the link). */
+int rdyn_chain_with_parameters(const rdyn_chain* chain, const double* pi, rdyn_chain** out);
 void rdyn_chain_destroy(rdyn_chain* chain);
 const char* rdyn_last_error(void);
 
@@ -516,6 +527,42 @@ int rdyn_forward_dynamics_vjp(const rdyn_chain* chain, const rdyn_batch* batch, 
                               const double* ddq_bar, double* q_bar, double* dq_bar, double* tau_bar, double* ddq, int32_t* status,
                               int64_t chunk_samples, void* workspace, size_t workspace_bytes);
 
+/* Reverse-mode product of the forward dynamics with respect to the PARAMETERS of the model (no reference counterpart): the gradient
+ * output-error identification needs.  Per sample FD_c, w = tau_bar = M^-1 ddq_bar, ddq and the status are exactly those of
+ * rdyn_forward_dynamics_vjp (the same bits), and since tau = Y(q, Dq, DDq) pi + C(q, Dq) p at that ddq,
+ *     pi_bar   = -Y(q, Dq, ddq)' w     P = 10 joints_number doubles, the order of rdyn_nominal_parameters / the columns of rdyn_regressor
+ *     comp_bar = -C(q, Dq)' w          K = rdyn_components_columns doubles, the columns of rdyn_components_regressor (the saturated rows:
+ *                                      the same constants, the same clamps)
+ * Y and C are never formed: one more forward recursion over the links with the joint rates w, about 60 flops per link.
+ *   pi_bar, comp_bar          the per-sample rows: P (K) doubles per sample, contiguous per sample in RDYN_LAYOUT_SAMPLE_MAJOR, x[col][s] in
+ *                             RDYN_LAYOUT_ELEMENT_MAJOR (the batch's layout)
+ *   pi_bar_sum, comp_bar_sum  P (K) doubles: the sums of the rows over the samples with status 1; accumulate = 0 overwrites, 1 adds to
+ *                             what is there
+ *   tau_bar, ddq, status      as in rdyn_forward_dynamics_vjp; tau_bar may alias ddq_bar
+ * Every output may be NULL and is then not computed; pi_bar, comp_bar, both sums and tau_bar all NULL with n_samples > 0 is
+ * RDYN_ERR_INVALID_ARGUMENT.  A status -1 sample gets quiet NaN in its rows (and in tau_bar, ddq) and adds nothing to the sums; no sample
+ * affects another.
+ * The sums are reproducible bit for bit from run to run for the same n_samples and layout: every wave adds its 64 samples in a fixed
+ * butterfly, a second launch adds the waves' partials in a fixed order; no floating-point atomics.
+ * Up to RDYN_MAX_SWEPT_JOINTS input joints: ONE launch, plus two small ones when a sum is asked for.  A longer chain with at most that
+ * many input joints runs on its reduced companion; the rows and sums of its own links are X_f' (those of the body f rides on), X_f of
+ * rdyn_chain_reduction, links upstream of the first input joint 0 -- on the device, no host round trip.  More input joints (up to
+ * RDYN_MAX_JOINTS, any order): CORRECT, NOT FAST -- the chunked route of rdyn_forward_dynamics_vjp gives tau_bar, ddq and the status, then
+ * per chunk an element-major image [Y | C] at that ddq (the writer of rdyn_identification_gram_wide) and one launch that forms the rows;
+ * the sums are fixed-order column sums of the rows.  Neither rows nor sums depend on chunk_samples.
+ * Workspace, from the query below.  Swept chains (needed only when a sum is asked for): (ceil(n_samples / 64) + 1) (10 n_swept + K)
+ * doubles.  The chunked route (always needed): rdyn_forward_dynamics_vjp's, 2 n n_samples doubles and n_samples status words, the
+ * image of one chunk (n (P + K + 1) doubles per sample of it) and (P + K) (n_samples + 1) doubles for the rows and the totals.
+ * Errors, all RDYN_ERR_INVALID_ARGUMENT before any device work: those of rdyn_forward_dynamics_vjp; every product NULL; accumulate
+ * other than 0 or 1; a workspace smaller than the query's answer when a sum is asked for.  n_samples = 0 is RDYN_OK.  No allocation, no
+ * synchronisation: capturable into a graph once the chain has been used on the device. */
+size_t rdyn_forward_dynamics_parameter_vjp_workspace_bytes(const rdyn_chain* chain, const rdyn_component* comps, int n_comps,
+                                                           int64_t n_samples, int64_t chunk_samples);
+int rdyn_forward_dynamics_parameter_vjp(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_component* comps, int n_comps,
+                                        const double* tau, const double* ddq_bar, double* pi_bar, double* comp_bar, double* pi_bar_sum,
+                                        double* comp_bar_sum, int accumulate, double* tau_bar, double* ddq, int32_t* status,
+                                        int64_t chunk_samples, void* workspace, size_t workspace_bytes);
+
 /* Adjoint of a rollout (no reference counterpart): the exact transpose of the discrete scheme rdyn_rollout / rdyn_rollout_components
  * implement, backwards over the whole horizon -- both integrators; the RK4 stage states are rebuilt inside.  (The forward-mode recipe at
  * the end of rdyn_forward_dynamics_derivatives' comment still holds for semi-implicit Euler; this call replaces it where a gradient,
@@ -572,6 +619,36 @@ size_t rdyn_rollout_adjoint_workspace_bytes(const rdyn_chain* chain, const rdyn_
                                             int64_t chunk_samples);
 int rdyn_rollout_adjoint(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_rollout_adjoint_desc* desc,
                          const rdyn_component* comps, int n_comps, int64_t chunk_samples, void* workspace, size_t workspace_bytes);
+
+/* Adjoint of a rollout WITH the gradients with respect to the model's parameters (no reference counterpart): what loss.backward()
+ * through a rollout needs for output-error identification.  Everything rdyn_rollout_adjoint writes for the same descriptor this call
+ * writes with the same bits; gq0, gdq0 and gtau may all be NULL here.  The new outputs, selected by rdyn_parameter_gradient:
+ *     gpi[P]    P = 10 joints_number, the order of rdyn_nominal_parameters      gcomp[K]   K = rdyn_components_columns, column order
+ * = the sum, over the samples whose FINAL status is 1, of the one-evaluation products of rdyn_forward_dynamics_parameter_vjp
+ * (pi_bar = -Y' w, comp_bar = -C' w, w = M^-1 seed) at the very seeds the adjoint uses: semi-implicit Euler one product per step at
+ * (x_t, tau_t; mu); RK4 four per step, at (X_i, tau_t; kv_i), i = 4 .. 1.  A sample with status -1 contributes NOTHING, not even from
+ * the backward steps before it failed.  accumulate = 0 overwrites gpi / gcomp, 1 adds to what is there: a horizon split into two
+ * chained calls, the second with accumulate = 1, gives the single call's gpi to rounding (not bitwise: the order of the additions
+ * differs).  T = 0 gives zeros (accumulate = 1: leaves the outputs as they are).  gpi and gcomp are reproducible bit for bit from run to
+ * run: every lane adds into its own accumulators (element-major in the workspace, [10 n_swept + K][n_samples]) and one fixed-order
+ * reduction follows; no floating-point atomics.  A longer chain with at most RDYN_MAX_SWEPT_JOINTS input joints runs on its reduced
+ * companion and the sums are expanded by X_f' on the device.
+ * More than RDYN_MAX_SWEPT_JOINTS input joints: RDYN_ERR_UNSUPPORTED, before any device work (rdyn_rollout_adjoint serves such chains;
+ * their parameter gradients are the follow-up).
+ * Errors, all RDYN_ERR_INVALID_ARGUMENT before any device work: those of rdyn_rollout_adjoint (but for its "every output NULL"); a NULL
+ * pg, gpi and gcomp both NULL, accumulate other than 0 or 1; a workspace smaller than the query's answer.  n_samples = 0 is RDYN_OK.
+ * No allocation, no synchronisation: capturable into a graph once the chain has been used on the device. */
+typedef struct rdyn_parameter_gradient
+{
+  double* gpi;        /* [10 * joints_number], may be NULL */
+  double* gcomp;      /* [rdyn_components_columns], may be NULL */
+  int32_t accumulate; /* 0: overwrite, 1: add */
+} rdyn_parameter_gradient;
+size_t rdyn_rollout_adjoint_parameters_workspace_bytes(const rdyn_chain* chain, const rdyn_rollout_adjoint_desc* desc,
+                                                       const rdyn_component* comps, int n_comps, int64_t n_samples, int64_t chunk_samples);
+int rdyn_rollout_adjoint_parameters(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_rollout_adjoint_desc* desc,
+                                    const rdyn_component* comps, int n_comps, const rdyn_parameter_gradient* pg, int64_t chunk_samples,
+                                    void* workspace, size_t workspace_bytes);
 
 /* ---- mixed-chain batch (BASELINE.json configs[4]: 256 distinct 6-7-DOF chains x 4 096 samples) --------------
  * One launch per group of chains with equal joint count (and output-layout kind) evaluates rdyn_regressor for MANY

@@ -40,6 +40,10 @@ class RolloutAdjointDesc(C.Structure):
                 ("gtau_step_stride", C.c_int64), ("status", C.c_void_p)]
 
 
+class ParameterGradient(C.Structure):
+    _fields_ = [("gpi", C.c_void_p), ("gcomp", C.c_void_p), ("accumulate", C.c_int32)]
+
+
 INTEGRATORS = {"semi_implicit_euler": 0, "euler": 0, "rk4": 1}
 
 
@@ -76,6 +80,7 @@ SYMBOLS = {
     "rdyn_chain_from_urdf": (_I, [_CP, _CP, _CP, _DP, C.POINTER(_VP)]),
     "rdyn_chain_from_desc": (_I, [C.POINTER(ChainDesc), C.POINTER(_VP)]),
     "rdyn_chain_clone": (_I, [_VP, C.POINTER(_VP)]),
+    "rdyn_chain_with_parameters": (_I, [_VP, _DP, C.POINTER(_VP)]),
     "rdyn_chain_destroy": (None, [_VP]),
     "rdyn_last_error": (_CP, []),
     "rdyn_chain_links_number": (_I, [_VP]),
@@ -117,8 +122,14 @@ SYMBOLS = {
     "rdyn_forward_dynamics_derivatives": (_I, [_VP, _BP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP, C.c_size_t]),
     "rdyn_forward_dynamics_vjp_workspace_bytes": (C.c_size_t, [_VP, C.c_int64]),
     "rdyn_forward_dynamics_vjp": (_I, [_VP, _BP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP, C.c_size_t]),
+    "rdyn_forward_dynamics_parameter_vjp_workspace_bytes": (C.c_size_t, [_VP, _VP, _I, C.c_int64, C.c_int64]),
+    "rdyn_forward_dynamics_parameter_vjp": (_I, [_VP, _BP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, C.c_int64, _VP,
+                                                 C.c_size_t]),
     "rdyn_rollout_adjoint_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(RolloutAdjointDesc), C.c_int64, C.c_int64]),
     "rdyn_rollout_adjoint": (_I, [_VP, _BP, C.POINTER(RolloutAdjointDesc), _VP, _I, C.c_int64, _VP, C.c_size_t]),
+    "rdyn_rollout_adjoint_parameters_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(RolloutAdjointDesc), _VP, _I, C.c_int64, C.c_int64]),
+    "rdyn_rollout_adjoint_parameters": (_I, [_VP, _BP, C.POINTER(RolloutAdjointDesc), _VP, _I, C.POINTER(ParameterGradient), C.c_int64, _VP,
+                                             C.c_size_t]),
     "rdyn_local_ik": (_I, [_VP, _BP, _VP, _DP, C.c_double, _I, _VP, _VP, _VP]),
     "rdyn_local_ik_damped": (_I, [_VP, _BP, _VP, _DP, C.c_double, C.c_double, _I, _VP, _VP, _VP]),
     "rdyn_frame_distance": (_I, [C.c_int64, _VP, _VP, _I, _I, _VP, _VP, _I, _VP]),

@@ -14,10 +14,20 @@ Failed samples: a sample whose status is -1 (the inertia matrix is not positive 
 the forward call and yields NaN gradients for that sample -- and only for it.  Nothing is raised, and the status words are not returned:
 call ``Chain.getJointAcceleration`` / ``Chain.rollout`` directly where they are needed.
 Component kinks: friction components are piecewise linear; exactly at a kink the gradient is the outer one-sided slope.
+
+Gradients with respect to the MODEL (output-error identification): both helpers take ``parameters`` -- a float64 tensor of shape
+(10 chain.getJointsNumber(),), the inertial parameters in the order of ``Chain.getNominalParameters`` -- and ``component_parameters`` --
+a float64 tensor of shape (components.columns,), in column order.  Either may live on any device.  The forward then runs on
+``chain.withParameters(parameters)`` / ``components.withParameters(component_parameters)``: the values make a HOST ROUND TRIP (a
+device-to-host copy and a new chain per call; a chain is a host object) -- small against a rollout, but a synchronisation.  The backward
+returns dL/dparameters and dL/dcomponent_parameters on those tensors' devices, from ``Chain.getJointAccelerationParameterVjp`` (the sums)
+and ``Chain.rolloutParameterAdjoint``: sums over the samples whose status is 1 -- a failed sample is NaN in its own state gradients and
+adds NOTHING to the parameter gradients.  Without these arguments the two classes above are used, unchanged.
 """
 import torch
 
-__all__ = ["joint_acceleration", "rollout", "JointAccelerationFunction", "RolloutFunction"]
+__all__ = ["joint_acceleration", "rollout", "JointAccelerationFunction", "RolloutFunction", "JointAccelerationParametersFunction",
+           "RolloutParametersFunction"]
 
 
 class JointAccelerationFunction(torch.autograd.Function):
@@ -65,20 +75,113 @@ class RolloutFunction(torch.autograd.Function):
         return (None,) * 7 + (gq0 if need[0] else None, gdq0 if need[1] else None, gtau if need[2] else None)
 
 
-def joint_acceleration(chain, q, Dq, tau, components=None, layout="sample"):
+def _with_parameters(chain, components, parameters, component_parameters):
+    """the chain and the component set the forward runs on"""
+    if parameters is not None:
+        if parameters.dtype != torch.float64 or parameters.dim() != 1:
+            raise ValueError("parameters must be a float64 tensor of shape (10 * chain.getJointsNumber(),)")
+        chain = chain.withParameters(parameters.detach().cpu().numpy())
+    if component_parameters is not None:
+        if components is None:
+            raise ValueError("component_parameters need components")
+        if component_parameters.dtype != torch.float64 or component_parameters.dim() != 1:
+            raise ValueError("component_parameters must be a float64 tensor of shape (components.columns,)")
+        components = components.withParameters(component_parameters.detach().cpu().tolist())
+    return chain, components
+
+
+def _parameter_grads(ctx, gpi, gcomp, first):
+    """the last two entries of a backward's result"""
+    need = ctx.needs_input_grad[first:first + 2]
+    return (gpi.to(ctx.devices[0]) if need[0] and ctx.devices[0] is not None else None,
+            gcomp.to(ctx.devices[1]) if need[1] and ctx.devices[1] is not None and gcomp is not None else None)
+
+
+class JointAccelerationParametersFunction(torch.autograd.Function):
+    """JointAccelerationFunction with the model among the inputs (parameters and component_parameters: each a tensor or None)"""
+
+    @staticmethod
+    def forward(ctx, chain, components, layout, q, Dq, tau, parameters, component_parameters):
+        q, Dq, tau = q.detach().contiguous(), Dq.detach().contiguous(), tau.detach().contiguous()
+        chain, components = _with_parameters(chain, components, parameters, component_parameters)
+        ddq, _ = chain.getJointAcceleration(q, Dq, tau, layout=layout, components=components)
+        ctx.chain, ctx.components, ctx.layout = chain, components, layout
+        ctx.devices = tuple(t.device if t is not None else None for t in (parameters, component_parameters))
+        ctx.save_for_backward(q, Dq, tau)
+        return ddq
+
+    @staticmethod
+    def backward(ctx, g):
+        q, Dq, tau = ctx.saved_tensors
+        g = g.contiguous()
+        grads = {}
+        gpi = gcomp = None
+        if any(ctx.needs_input_grad[6:8]):
+            # (the parameter call returns tau_bar as well -- the same bits: the state product below is then asked for q and dq only)
+            gpi, gcomp, grads["tau"] = ctx.chain.getJointAccelerationParameterVjp(q, Dq, tau, g, components=ctx.components, layout=ctx.layout,
+                                                                                 reduce=True)[:3]
+        names = tuple(k for k, need in zip(("q", "dq", "tau"), ctx.needs_input_grad[3:6]) if need and k not in grads)
+        if names:
+            res = ctx.chain.getJointAccelerationVjp(q, Dq, tau, g, layout=ctx.layout, want=names, components=ctx.components)
+            grads.update(zip(names, res[1:]))
+        if not ctx.needs_input_grad[5]:
+            grads.pop("tau", None)
+        return (None, None, None, grads.get("q"), grads.get("dq"), grads.get("tau")) + _parameter_grads(ctx, gpi, gcomp, 6)
+
+
+class RolloutParametersFunction(torch.autograd.Function):
+    """RolloutFunction with the model among the inputs; the backward is ONE Chain.rolloutParameterAdjoint call"""
+
+    @staticmethod
+    def forward(ctx, chain, components, layout, integrator, dt, n_steps, trajectory, q0, Dq0, tau, parameters, component_parameters):
+        q0, Dq0, tau = q0.detach().contiguous(), Dq0.detach().contiguous(), tau.detach().contiguous()
+        chain, components = _with_parameters(chain, components, parameters, component_parameters)
+        q_end, dq_end, _, q_traj, dq_traj = chain.rollout(q0, Dq0, tau, dt, integrator=integrator, n_steps=n_steps, layout=layout,
+                                                          trajectory_every=1, components=components)
+        ctx.chain, ctx.components, ctx.layout, ctx.integrator, ctx.dt = chain, components, layout, integrator, dt
+        ctx.n_steps, ctx.trajectory, ctx.sum_tau = q_traj.shape[0], trajectory, tau.dim() == 2
+        ctx.devices = tuple(t.device if t is not None else None for t in (parameters, component_parameters))
+        ctx.save_for_backward(q0, Dq0, tau, q_traj, dq_traj)
+        if trajectory:
+            return q_end, dq_end, q_traj.clone(), dq_traj.clone()  # (the saved records must not be written to by the caller)
+        return q_end, dq_end
+
+    @staticmethod
+    def backward(ctx, gq_end, gdq_end, gq_traj=None, gdq_traj=None):
+        q0, Dq0, tau, q_traj, dq_traj = ctx.saved_tensors
+        c = lambda t: t.contiguous() if t is not None else None
+        gq0, gdq0, gtau, gpi, gcomp, _ = ctx.chain.rolloutParameterAdjoint(q0, Dq0, tau, ctx.dt, q_traj, dq_traj, gq_end=c(gq_end),
+                                                                           gDq_end=c(gdq_end), gq_traj=c(gq_traj), gDq_traj=c(gdq_traj),
+                                                                           integrator=ctx.integrator, n_steps=ctx.n_steps, layout=ctx.layout,
+                                                                           components=ctx.components, sum_tau=ctx.sum_tau)
+        need = ctx.needs_input_grad[7:10]
+        return ((None,) * 7 + (gq0 if need[0] else None, gdq0 if need[1] else None, gtau if need[2] else None)
+                + _parameter_grads(ctx, gpi, gcomp, 10))
+
+
+def joint_acceleration(chain, q, Dq, tau, components=None, layout="sample", parameters=None, component_parameters=None):
     """Differentiable ``Chain.getJointAcceleration``: DDq = FD_c(q, Dq, tau), shaped like q.  Gradients flow to q, Dq and tau through
-    ``Chain.getJointAccelerationVjp``.  A sample with status -1 is NaN in DDq and in its gradients; nothing is raised."""
-    return JointAccelerationFunction.apply(chain, components, layout, q, Dq, tau)
+    ``Chain.getJointAccelerationVjp``.  A sample with status -1 is NaN in DDq and in its gradients; nothing is raised.
+    parameters / component_parameters (the module docstring): the model to evaluate, differentiable as well."""
+    if parameters is None and component_parameters is None:
+        return JointAccelerationFunction.apply(chain, components, layout, q, Dq, tau)
+    return JointAccelerationParametersFunction.apply(chain, components, layout, q, Dq, tau, parameters, component_parameters)
 
 
-def rollout(chain, q0, Dq0, tau, dt, integrator="rk4", n_steps=None, trajectory=False, components=None, layout="sample"):
+def rollout(chain, q0, Dq0, tau, dt, integrator="rk4", n_steps=None, trajectory=False, components=None, layout="sample", parameters=None,
+            component_parameters=None):
     """Differentiable ``Chain.rollout``: returns (q_end, Dq_end), and with trajectory=True also (q_traj, Dq_traj) with one record per
     step (record k = the state after step k + 1).  tau: (T, N, n) / (T, n, N), one torque per step, or shaped like q0 with an explicit
     n_steps (held over the horizon: its gradient is the sum over the steps).  Gradients flow to q0, Dq0 and tau from the end state and
     from every trajectory record; the backward is one ``Chain.rolloutAdjoint`` call over the records the forward saved.
-    A sample whose rollout reports status -1 has NaN states from the failing step on and NaN gradients; nothing is raised."""
+    A sample whose rollout reports status -1 has NaN states from the failing step on and NaN gradients; nothing is raised.
+    parameters / component_parameters (the module docstring): the model to simulate, differentiable as well -- the backward is then one
+    ``Chain.rolloutParameterAdjoint`` call (chains with at most 10 input joints)."""
     if n_steps is None:
         if tau.dim() != 3:
             raise ValueError("torques shaped like q0 need an explicit n_steps")
         n_steps = tau.shape[0]
-    return RolloutFunction.apply(chain, components, layout, integrator, float(dt), int(n_steps), bool(trajectory), q0, Dq0, tau)
+    if parameters is None and component_parameters is None:
+        return RolloutFunction.apply(chain, components, layout, integrator, float(dt), int(n_steps), bool(trajectory), q0, Dq0, tau)
+    return RolloutParametersFunction.apply(chain, components, layout, integrator, float(dt), int(n_steps), bool(trajectory), q0, Dq0, tau,
+                                           parameters, component_parameters)

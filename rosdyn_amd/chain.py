@@ -518,6 +518,66 @@ class Chain(object):
                                               status.data_ptr(), chunk_samples, *ws))
         return (status,) + tuple(res[k] for k in names)
 
+    def getJointAccelerationParameterVjp(self, q, Dq, tau, DDq_bar, components=None, layout="sample", reduce=False, accumulate=None,
+                                         chunk_samples=0, workspace=None):
+        """Reverse-mode product of getJointAcceleration with respect to the model's PARAMETERS (include/rdyn.h:
+        rdyn_forward_dynamics_parameter_vjp; no reference counterpart): with w = M^-1 DDq_bar,
+        pi_bar = -getRegressor(q, Dq, DDq)' w (P = 10 getJointsNumber() entries, the order of getNominalParameters) and
+        comp_bar = -(component regressor)' w (components.columns entries), DDq = getJointAcceleration's.  Neither regressor is formed.
+        Returns (pi_bar, comp_bar, tau_bar, DDq, status).  reduce=False: the per-sample rows, (N, P) and (N, K) for layout="sample",
+        (P, N) and (K, N) for "element"; a status -1 sample is NaN in its rows.  reduce=True: the sums (P,) and (K,) over the samples
+        with status 1, reproducible bit for bit from run to run; accumulate = (pi_sum, comp_sum) adds to those tensors instead
+        (comp_sum may be None without components).  comp_bar is None without components.  tau_bar and DDq are those of
+        getJointAccelerationVjp.  chunk_samples, workspace: as in getJointAccelerationVjp (more than 10 input joints run in chunks; the
+        results do not depend on the chunk size)."""
+        torch = _torch()
+        b, N, lay = self._batch(layout, q, Dq, tau)
+        b.ddq = None
+        if (DDq_bar.shape != q.shape or DDq_bar.dtype != torch.float64 or not DDq_bar.is_cuda or not DDq_bar.is_contiguous()
+                or DDq_bar.device != q.device):
+            raise ValueError("Input data dimensions mismatch")
+        n, P = self.getActiveJointsNumber(), 10 * self.getJointsNumber()
+        comps, n_comps = self._component_list(components) if components is not None else (None, 0)
+        K = components.columns if components is not None else 0
+        tau_bar, DDq = self._out(q, N, lay, (n,)), self._out(q, N, lay, (n,))
+        status = torch.empty((N,), dtype=torch.int32, device=q.device)
+        rows = [None, None]
+        sums = [None, None]
+        acc = 0
+        if reduce:
+            if accumulate is not None:
+                sums, acc = list(accumulate), 1
+                for t, size in zip(sums, (P, K)):
+                    if t is not None and (tuple(t.shape) != (size,) or t.dtype != torch.float64 or not t.is_contiguous()
+                                          or t.device != q.device):
+                        raise ValueError("accumulate must hold contiguous float64 tensors of %d and %d entries" % (P, K))
+            else:
+                sums = [torch.empty((P,), dtype=torch.float64, device=q.device),
+                        torch.empty((K,), dtype=torch.float64, device=q.device) if K else None]
+        else:
+            rows = [self._out(q, N, lay, (P,)), self._out(q, N, lay, (K,)) if K else None]
+        nbytes = lib().rdyn_forward_dynamics_parameter_vjp_workspace_bytes(self._h, comps, n_comps, N, chunk_samples)
+        if workspace is None and nbytes > 0:
+            workspace = torch.empty((nbytes,), dtype=torch.uint8, device=q.device)
+        ws = (workspace.data_ptr() if workspace is not None else None, workspace.numel() if workspace is not None else 0)
+        ptr = [t.data_ptr() if t is not None else None for t in rows + sums]
+        check(lib().rdyn_forward_dynamics_parameter_vjp(self._h, C.byref(b), comps, n_comps, tau.data_ptr(), DDq_bar.data_ptr(), *ptr, acc,
+                                                        tau_bar.data_ptr(), DDq.data_ptr(), status.data_ptr(), chunk_samples, *ws))
+        res = sums if reduce else rows
+        return res[0], res[1], tau_bar, DDq, status
+
+    def withParameters(self, pi):
+        """The chain with the inertial parameters pi (include/rdyn.h: rdyn_chain_with_parameters; no reference counterpart): a new,
+        independent Chain equal to clone() in everything else, input-joint selection included.  pi: 10 getJointsNumber() values in the
+        order of getNominalParameters (host numpy array or CPU tensor); they are stored as given, so getNominalParameters of the
+        result returns them bit for bit.  Values that are not finite raise ValueError."""
+        pi = np.ascontiguousarray(np.asarray(pi, dtype=np.float64).reshape(-1))
+        if pi.size != 10 * self.getJointsNumber():
+            raise ValueError("pi must hold 10 values per chain joint (%d)" % (10 * self.getJointsNumber(),))
+        h = C.c_void_p()
+        check(lib().rdyn_chain_with_parameters(self._h, pi.ctypes.data_as(C.POINTER(C.c_double)), C.byref(h)))
+        return Chain(None, None, None, _handle=h)
+
     def rolloutAdjoint(self, q0, Dq0, tau, dt, q_traj, Dq_traj, gq_end=None, gDq_end=None, gq_traj=None, gDq_traj=None, integrator="rk4",
                        n_steps=None, layout="sample", components=None, sum_tau=False, out=None, chunk_samples=0, workspace=None):
         """Adjoint of rollout (include/rdyn.h: rdyn_rollout_adjoint; no reference counterpart): the exact transpose of the n_steps
@@ -530,6 +590,25 @@ class Chain(object):
         sum over the steps: the gradient of torques held over the whole horizon).  status (N,) int32: 1, or -1 when an evaluation of the
         sample failed or met a non-finite value -- a sample whose forward rollout reported -1 in particular: NaN in every gradient.
         out: None, or a dict with any of "gq0", "gDq0", "gtau" -> preallocated tensor; out["gq0"] / out["gDq0"] may be gq_end / gDq_end."""
+        return self._rollout_adjoint(q0, Dq0, tau, dt, q_traj, Dq_traj, gq_end, gDq_end, gq_traj, gDq_traj, integrator, n_steps, layout, components,
+                                     sum_tau, out, chunk_samples, workspace, None)
+
+    def rolloutParameterAdjoint(self, q0, Dq0, tau, dt, q_traj, Dq_traj, gq_end=None, gDq_end=None, gq_traj=None, gDq_traj=None,
+                                integrator="rk4", n_steps=None, layout="sample", components=None, sum_tau=False, out=None, chunk_samples=0,
+                                workspace=None, accumulate=False):
+        """rolloutAdjoint with the gradients with respect to the model's parameters (include/rdyn.h: rdyn_rollout_adjoint_parameters; no
+        reference counterpart).  The arguments are rolloutAdjoint's; returns (gq0, gDq0, gtau, gpi, gcomp, status): the first three and the
+        status are rolloutAdjoint's, bit for bit; gpi (10 getJointsNumber(),) = dL/d(inertial parameters, the order of
+        getNominalParameters) and gcomp (components.columns,) = dL/d(component parameters, column order; None without components), each
+        summed over the samples whose status is 1 -- a failed sample contributes nothing -- and reproducible bit for bit from run to run.
+        out may also hold "gpi" and "gcomp": preallocated tensors, which accumulate=True adds to instead of overwriting (a horizon split into
+        chained calls).  Chains with more than 10 input joints raise RdynError (RDYN_ERR_UNSUPPORTED)."""
+        return self._rollout_adjoint(q0, Dq0, tau, dt, q_traj, Dq_traj, gq_end, gDq_end, gq_traj, gDq_traj, integrator, n_steps, layout, components,
+                                     sum_tau, out, chunk_samples, workspace, bool(accumulate))
+
+    def _rollout_adjoint(self, q0, Dq0, tau, dt, q_traj, Dq_traj, gq_end, gDq_end, gq_traj, gDq_traj, integrator, n_steps, layout, components,
+                         sum_tau, out, chunk_samples, workspace, accumulate):
+        """the two calls above; accumulate None: without the parameter gradients"""
         torch = _torch()
         b, N, lay = self._batch(layout, q0, Dq0)
         if integrator not in _lib.INTEGRATORS:
@@ -579,13 +658,31 @@ class Chain(object):
         d.gq0, d.gdq0 = gq0.data_ptr(), gdq0.data_ptr()
         d.gtau, d.gtau_step_stride = ptr(gtau), 0 if sum_tau else q0.numel()
         d.status = status.data_ptr()
-        nbytes = lib().rdyn_rollout_adjoint_workspace_bytes(self._h, C.byref(d), N, chunk_samples)
+        comps, n_comps = self._component_list(components) if components is not None else (None, 0)
+        if accumulate is None:
+            nbytes = lib().rdyn_rollout_adjoint_workspace_bytes(self._h, C.byref(d), N, chunk_samples)
+        else:
+            nbytes = lib().rdyn_rollout_adjoint_parameters_workspace_bytes(self._h, C.byref(d), comps, n_comps, N, chunk_samples)
         if workspace is None and nbytes > 0:
             workspace = torch.empty((nbytes,), dtype=torch.uint8, device=q0.device)
         ws = (workspace.data_ptr() if workspace is not None else None, workspace.numel() if workspace is not None else 0)
-        comps, n_comps = self._component_list(components) if components is not None else (None, 0)
-        check(lib().rdyn_rollout_adjoint(self._h, C.byref(b), C.byref(d), comps, n_comps, chunk_samples, *ws))
-        return gq0, gdq0, gtau, status
+        if accumulate is None:
+            check(lib().rdyn_rollout_adjoint(self._h, C.byref(b), C.byref(d), comps, n_comps, chunk_samples, *ws))
+            return gq0, gdq0, gtau, status
+        sizes = {"gpi": 10 * self.getJointsNumber(), "gcomp": components.columns if components is not None else 0}
+        grads = {}
+        for key, size in sizes.items():
+            t = out.get(key)
+            if t is None:
+                if accumulate and size:
+                    raise ValueError("accumulate=True needs out['gpi'] (and out['gcomp'] with components)")
+                t = torch.empty((size,), dtype=torch.float64, device=q0.device)
+            elif tuple(t.shape) != (size,) or t.dtype != torch.float64 or not t.is_contiguous() or t.device != q0.device:
+                raise ValueError("out[%r] must be a contiguous float64 tensor of %d entries" % (key, size))
+            grads[key] = t
+        pg = _lib.ParameterGradient(grads["gpi"].data_ptr(), ptr(grads["gcomp"]), 1 if accumulate else 0)
+        check(lib().rdyn_rollout_adjoint_parameters(self._h, C.byref(b), C.byref(d), comps, n_comps, C.byref(pg), chunk_samples, *ws))
+        return gq0, gdq0, gtau, grads["gpi"], (grads["gcomp"] if components is not None else None), status
 
     def getRegressor(self, q, Dq, DDq, layout="sample", y_layout=None, out=None, tau_out=None, with_torque=False):
         """Regressor (and optionally the fused joint torque).

@@ -28,6 +28,20 @@ class ComponentSet(object):
             out += list(a.parameters[:3 if a.type == FRICTION2 else 2])
         return out
 
+    def withParameters(self, parameters):
+        """The same components (types, joints, velocity constants) with the flat parameter vector `parameters`: `columns` values in
+        column order, the order getNominalParameters returns them in.  A new ComponentSet; this one is not touched."""
+        p = [float(x) for x in parameters]
+        if len(p) != self.columns:
+            raise ValueError("parameters must hold %d values" % (self.columns,))
+        comps, k = [], 0
+        for a in self._arr:
+            cols = 3 if a.type == FRICTION2 else 2
+            comps.append({"type": a.type, "joint": a.joint, "min_velocity": a.min_velocity, "max_velocity": a.max_velocity,
+                          "parameters": p[k:k + cols]})
+            k += cols
+        return ComponentSet(comps, self.n_active)
+
     def getRegressor(self, q, Dq, layout="sample", out=None, tau_add=None):
         """Returns C: layout="sample" -> (N, K, n) (per-sample column-major n x K); "element" -> (K, n, N)."""
         import torch

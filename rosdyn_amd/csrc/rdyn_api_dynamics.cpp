@@ -1,5 +1,6 @@
 // rdyn_api_dynamics.cpp -- the forward-dynamics family of the C-ABI (include/rdyn.h): rdyn_forward_dynamics(_components),
-// rdyn_rollout(_components), rdyn_forward_dynamics_derivatives, rdyn_forward_dynamics_vjp, rdyn_rollout_adjoint and their workspace queries.
+// rdyn_rollout(_components), rdyn_forward_dynamics_derivatives, rdyn_forward_dynamics_vjp, rdyn_rollout_adjoint, their parameter-gradient
+// forms rdyn_forward_dynamics_parameter_vjp and rdyn_rollout_adjoint_parameters, and the workspace queries.
 // Every entry runs check_batch and its own pointer / descriptor checks, then dyn_prepare (the checks and the set-up all of them share),
 // then either one launch (chains the unrolled kernels sweep) or the chunked route through its workspace.  The workspace of every chunked
 // route is described ONCE, by a *Layout struct: the query returns its total, the call carves its pointers from its offsets.
@@ -658,6 +659,199 @@ int rdyn_forward_dynamics_vjp(const rdyn_chain* c, const rdyn_batch* b, const rd
                     k.stream);
 }
 
+// ---- reverse-mode product with respect to the parameters (rdyn_fwd_dyn_param_vjp.hip) ----------------------------
+// Chains the unrolled kernels sweep (long ones through their reduced companion, the rows and sums expanded by X_f'): one launch, and two
+// small ones behind it when a sum is asked for.  The workspace holds the waves' partial sums [ceil(N / 64)][10 n_swept + C] and their
+// total [10 n_swept + C].
+// More input joints: CORRECT, NOT FAST.  The chunked product of rdyn_forward_dynamics_vjp gives tau_bar, ddq and the status of the whole
+// batch (into the caller's arrays, or arrays of the workspace); then per chunk the element-major image [Y | C] at that ddq -- the writer
+// of the wide normal equations (ChunkImage) -- and k_param_rows_from_image; the sums are the fixed-order column sums of the ROWS (the
+// caller's, or element-major rows in the workspace), so neither rows nor sums depend on chunk_samples.  Workspace: the product's | tau_bar
+// | ddq (n N each) | status (N) | the image of one chunk | rows [P + C][N] | the totals [P + C].
+namespace
+{
+struct ParamVjpLayout
+{
+  int cols;
+  int64_t waves;
+  size_t S, total;  // the partials at offset 0
+  // the chunked route
+  VjpLayout v;
+  int64_t chunk;
+  size_t tb, ddq, st, image, rows;
+};
+static ParamVjpLayout param_vjp_layout(const rdyn_chain* c, const rdyn_component* comps, int n_comps, int64_t n_samples, int64_t chunk_samples)
+{
+  ParamVjpLayout L = {};
+  if (!c || c->n_active() < 1 || n_samples <= 0 || chunk_samples < 0) return L;
+  const int C = (comps && n_comps > 0 && n_comps <= RDYN_MAX_COMPONENTS) ? rdyn_components_columns(comps, n_comps) : 0;
+  if (fwd_dyn_by_chunks(c))
+  {
+    const size_t n = (size_t)c->n_active(), N = (size_t)n_samples;
+    L.cols = 10 * c->n_joints() + (C > 0 ? C : 0);
+    L.v = vjp_layout(c, chunk_samples);
+    L.chunk = wide_chunk(c, L.cols, chunk_samples);
+    if (L.chunk > n_samples) L.chunk = (n_samples + 63) & ~(int64_t)63;
+    L.tb = L.v.total;
+    L.ddq = L.tb + align256(n * N * sizeof(double));
+    L.st = L.ddq + align256(n * N * sizeof(double));
+    L.image = L.st + align256(N * sizeof(int32_t));
+    L.rows = L.image + align256((size_t)L.chunk * n * (L.cols + 1) * sizeof(double));
+    L.S = L.rows + align256((size_t)L.cols * N * sizeof(double));
+    L.total = L.S + align256((size_t)L.cols * sizeof(double));
+    return L;
+  }
+  const rdyn_chain* const sw = c->long_chain() ? c->reduced.get() : c;
+  L.cols = 10 * sw->n_joints() + (C > 0 ? C : 0);
+  L.waves = (n_samples + 63) / 64;
+  L.S = align256((size_t)L.waves * L.cols * sizeof(double));
+  L.total = L.S + align256((size_t)L.cols * sizeof(double));
+  return L;
+}
+}  // namespace
+
+size_t rdyn_forward_dynamics_parameter_vjp_workspace_bytes(const rdyn_chain* c, const rdyn_component* comps, int n_comps, int64_t n_samples,
+                                                           int64_t chunk_samples)
+{
+  return param_vjp_layout(c, comps, n_comps, n_samples, chunk_samples).total;
+}
+
+int rdyn_forward_dynamics_parameter_vjp(const rdyn_chain* c, const rdyn_batch* b, const rdyn_component* comps, int n_comps, const double* tau,
+                                        const double* ddq_bar, double* pi_bar, double* comp_bar, double* pi_bar_sum, double* comp_bar_sum,
+                                        int accumulate, double* tau_bar, double* ddq, int32_t* status, int64_t chunk_samples, void* workspace,
+                                        size_t workspace_bytes)
+{
+  const char* const who = "rdyn_forward_dynamics_parameter_vjp";
+  int st = check_batch(c, b, true, false, who, LONG_KERNELS);
+  if (st != RDYN_OK) return st;
+  if (b->n_samples > 0 && (!tau || !ddq_bar)) return refuse(who, "null torque or seed pointer");
+  if (b->n_samples > 0 && !pi_bar && !comp_bar && !pi_bar_sum && !comp_bar_sum && !tau_bar) return refuse(who, "every product is null");
+  if (accumulate != 0 && accumulate != 1) return refuse(who, "accumulate is 0 or 1");
+  const bool sums = pi_bar_sum || comp_bar_sum;
+  const ParamVjpLayout L = param_vjp_layout(c, comps, n_comps, b->n_samples, chunk_samples < 0 ? 0 : chunk_samples);
+  DynCall k;
+  st = dyn_prepare(c, b, comps, n_comps, chunk_samples, (sums || fwd_dyn_by_chunks(c)) ? L.total : 0, workspace, workspace_bytes, who, &k);
+  if (st != RDYN_OK || !k.run) return st;
+  const int C = n_comps > 0 ? rdyn_components_columns(comps, n_comps) : 0;
+  if (!k.sw)
+  {
+    const int64_t N = b->n_samples;
+    const int P = 10 * c->n_joints();
+    char* const w = (char*)workspace;
+    double* const tb = tau_bar ? tau_bar : (double*)(w + L.tb);
+    double* const acc = ddq ? ddq : (double*)(w + L.ddq);
+    int32_t* const stp = status ? status : (int32_t*)(w + L.st);
+    st = vjp_chunks(c, b->q, b->dq, tau, ddq_bar, nullptr, nullptr, tb, acc, stp, N, k.in_ss, k.in_sj, L.v, workspace, k.comps, k.stream);
+    if (st != RDYN_OK) return st;
+    const bool want_pi = pi_bar || pi_bar_sum, want_comp = C > 0 && (comp_bar || comp_bar_sum);
+    if (!want_pi && !want_comp) return RDYN_OK;
+    // the rows: the caller's, or element-major ones in the workspace for the sums
+    RdynParamProductArgs pa;
+    memset(&pa, 0, sizeof pa);
+    double* const ws_rows = (double*)(w + L.rows);
+    double* pi_rows = pi_bar;
+    double* comp_rows = comp_bar;
+    rec_strides(b, P, &pa.pi_ss, &pa.pi_sc);
+    rec_strides(b, C, &pa.comp_ss, &pa.comp_sc);
+    if (!pi_rows && want_pi)
+    {
+      pi_rows = ws_rows;
+      pa.pi_ss = 1;
+      pa.pi_sc = N;
+    }
+    if (!comp_rows && want_comp)
+    {
+      comp_rows = ws_rows + (int64_t)P * N;
+      pa.comp_ss = 1;
+      pa.comp_sc = N;
+    }
+    RdynComponentArgs ca;
+    memset(&ca, 0, sizeof ca);
+    if (n_comps > 0 && (st = fill_components(comps, n_comps, k.n, &ca)) != RDYN_OK) return st;
+    rdyn_batch bi = *b;
+    bi.ddq = acc;
+    double* const image = (double*)(w + L.image);
+    ChunkImage img(c, &bi, nullptr, image, P + C, &ca, n_comps, C);
+    st = img.bind(true);
+    if (st != RDYN_OK) return st;
+    const int64_t in_step = (b->layout == RDYN_LAYOUT_SAMPLE_MAJOR) ? k.n : 1;
+    for (int64_t s0 = 0; s0 < N; s0 += L.chunk)
+    {
+      const int64_t cnt = (N - s0 < L.chunk) ? N - s0 : L.chunk;
+      st = img.write(s0, cnt, 1, k.stream);
+      if (st != RDYN_OK) return st;
+      pa.image = image;
+      pa.cnt = cnt;
+      pa.lda = (int64_t)k.n * cnt;
+      pa.n = k.n;
+      pa.P = P;
+      pa.K = C;
+      pa.tau_bar = tb + s0 * in_step;
+      pa.in_ss = k.in_ss;
+      pa.in_sj = k.in_sj;
+      pa.status = stp + s0;
+      pa.pi_rows = pi_rows ? pi_rows + s0 * pa.pi_ss : nullptr;
+      pa.comp_rows = comp_rows ? comp_rows + s0 * pa.comp_ss : nullptr;
+      RDYN_HIP_TRY(rdyn_launch_parameter_rows_from_image(pa, k.stream));
+    }
+    if (!sums) return RDYN_OK;
+    double* const S = (double*)(w + L.S);
+    if (pi_bar_sum) RDYN_HIP_TRY(rdyn_launch_parameter_column_sums(pi_rows, N, pa.pi_ss, pa.pi_sc, stp, P, S, k.stream));
+    if (comp_bar_sum && C > 0) RDYN_HIP_TRY(rdyn_launch_parameter_column_sums(comp_rows, N, pa.comp_ss, pa.comp_sc, stp, C, S + P, k.stream));
+    RdynParamSumArgs fa;
+    memset(&fa, 0, sizeof fa);
+    fa.S = S;
+    fa.pi_sum = pi_bar_sum;
+    fa.comp_sum = C > 0 ? comp_bar_sum : nullptr;
+    fa.accumulate = accumulate;
+    fa.n_swept = fa.n_full = c->n_joints();
+    fa.n_comp_cols = C;
+    RDYN_HIP_TRY(rdyn_launch_parameter_sums_finish(fa, k.stream));
+    return RDYN_OK;
+  }
+  RdynFwdDynParamVjpArgs a;
+  memset(&a, 0, sizeof a);
+  a.v.chain = k.chain;
+  a.v.q = b->q;
+  a.v.dq = b->dq;
+  a.v.tau = tau;
+  a.v.ddq_bar = ddq_bar;
+  a.v.tau_bar = tau_bar;
+  a.v.ddq = ddq;
+  a.v.status = status;
+  a.v.n_samples = b->n_samples;
+  a.v.in_ss = k.in_ss;
+  a.v.in_sj = k.in_sj;
+  a.v.staged = stage_records(b, tau_bar, ddq) ? k.n : 0;
+  a.v.t = k.table;
+  a.pi_bar = pi_bar;
+  a.comp_bar = comp_bar;
+  rec_strides(b, (int64_t)10 * c->n_joints(), &a.pi_ss, &a.pi_sc);
+  rec_strides(b, C, &a.comp_ss, &a.comp_sc);
+  a.partials = sums ? (double*)workspace : nullptr;
+  a.n_comp_cols = C;
+  RdynParamSumArgs sa;
+  memset(&sa, 0, sizeof sa);
+  a.n_full = sa.n_full = c->n_joints();
+  if (k.sw != c)
+  {
+    st = device_expand(c, &a.expand);
+    if (st != RDYN_OK) return st;
+    sa.expand = a.expand;
+    for (int f = 0; f < c->n_joints(); ++f) a.red_of[f] = sa.red_of[f] = c->red_of[f];
+  }
+  RDYN_HIP_TRY(rdyn_launch_forward_dynamics_parameter_vjp(k.sw->n_joints(), a, k.stream));
+  if (!sums) return RDYN_OK;
+  sa.S = (const double*)((char*)workspace + L.S);
+  sa.pi_sum = pi_bar_sum;
+  sa.comp_sum = comp_bar_sum;
+  sa.accumulate = accumulate;
+  sa.n_swept = k.sw->n_joints();
+  sa.n_comp_cols = C;
+  RDYN_HIP_TRY(rdyn_launch_parameter_sums(a.partials, L.waves, L.cols, 1, nullptr, sa, k.stream));
+  return RDYN_OK;
+}
+
 // ---- adjoint of a rollout (rdyn_rollout_adjoint.hip) ------------------------------------------------------------
 // Chains the unrolled kernels sweep: one launch for the whole horizon.  More input joints: a host loop over steps and stages on the state
 // arrays of AdjointLayout, behind the workspace of the product.
@@ -666,13 +860,35 @@ size_t rdyn_rollout_adjoint_workspace_bytes(const rdyn_chain* c, const rdyn_roll
   return adjoint_layout(c, d, n_samples, chunk_samples).s.total;
 }
 
-int rdyn_rollout_adjoint(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_adjoint_desc* d, const rdyn_component* comps, int n_comps,
-                         int64_t chunk_samples, void* workspace, size_t workspace_bytes)
+// With the parameter gradients (pg set; rdyn_rollout_adjoint_params.hip): the same launch with the PARAMS kernels, the lanes' accumulators
+// [10 n_swept + C][N], the final statuses [N] and the column sums [10 n_swept + C] in the workspace, then the two launches of
+// rdyn_launch_parameter_sums.  Chains the unrolled kernels do not sweep are refused.
+namespace
 {
-  const char* const who = "rdyn_rollout_adjoint";
+struct AdjointParamLayout { int cols; size_t st, S, total; };  // the accumulators at offset 0
+static AdjointParamLayout adjoint_param_layout(const rdyn_chain* c, const rdyn_component* comps, int n_comps, int64_t n_samples)
+{
+  AdjointParamLayout L = {};
+  if (!c || c->n_active() < 1 || n_samples <= 0 || fwd_dyn_by_chunks(c)) return L;
+  const int C = (comps && n_comps > 0 && n_comps <= RDYN_MAX_COMPONENTS) ? rdyn_components_columns(comps, n_comps) : 0;
+  const rdyn_chain* const sw = c->long_chain() ? c->reduced.get() : c;
+  L.cols = 10 * sw->n_joints() + (C > 0 ? C : 0);
+  L.st = align256((size_t)n_samples * L.cols * sizeof(double));
+  L.S = L.st + align256((size_t)n_samples * sizeof(int32_t));
+  L.total = L.S + align256((size_t)L.cols * sizeof(double));
+  return L;
+}
+
+// who = the entry point (error texts); pg null: rdyn_rollout_adjoint
+static int rollout_adjoint(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_adjoint_desc* d, const rdyn_component* comps, int n_comps,
+                           const rdyn_parameter_gradient* pg, bool with_pg, int64_t chunk_samples, void* workspace, size_t workspace_bytes,
+                           const char* who)
+{
   int st = check_batch(c, b, true, false, who, LONG_KERNELS);
   if (st != RDYN_OK) return st;
   if (!d) return refuse(who, "null descriptor");
+  if (with_pg && (!pg || (!pg->gpi && !pg->gcomp))) return refuse(who, "null parameter-gradient selection, or neither gpi nor gcomp in it");
+  if (with_pg && pg->accumulate != 0 && pg->accumulate != 1) return refuse(who, "accumulate is 0 or 1");
   const int n = c->n_active();
   const int64_t N = b->n_samples;
   const int T = d->n_steps;
@@ -685,10 +901,17 @@ int rdyn_rollout_adjoint(const rdyn_chain* c, const rdyn_batch* b, const rdyn_ro
   if ((T >= 2 && d->traj_step_stride < nN) || (running && d->gtraj_step_stride < nN) ||
       (d->gtau && d->gtau_step_stride != 0 && d->gtau_step_stride < nN))
     return refuse(who, "traj_step_stride, gtraj_step_stride and a non-zero gtau_step_stride must be >= n * n_samples");
-  if (N > 0 && !d->gq0 && !d->gdq0 && !d->gtau) return refuse(who, "every output is null");
+  if (N > 0 && !with_pg && !d->gq0 && !d->gdq0 && !d->gtau) return refuse(who, "every output is null");
+  if (with_pg && fwd_dyn_by_chunks(c))
+  {
+    rdyn_set_error("%s: chains with more than %d input joints are not served yet (this chain has %d); rdyn_rollout_adjoint serves them", who,
+                   RDYN_MAX_SWEPT_JOINTS, n);
+    return RDYN_ERR_UNSUPPORTED;
+  }
   const AdjointLayout L = adjoint_layout(c, d, N, chunk_samples);
+  const AdjointParamLayout PL = adjoint_param_layout(c, comps, n_comps, with_pg ? N : 0);
   DynCall k;
-  st = dyn_prepare(c, b, comps, n_comps, chunk_samples, L.s.total, workspace, workspace_bytes, who, &k);
+  st = dyn_prepare(c, b, comps, n_comps, chunk_samples, with_pg ? PL.total : L.s.total, workspace, workspace_bytes, who, &k);
   if (st != RDYN_OK || !k.run) return st;
   if (k.sw)
   {
@@ -723,7 +946,34 @@ int rdyn_rollout_adjoint(const rdyn_chain* c, const rdyn_batch* b, const rdyn_ro
     if ((d->gq0 || d->gdq0) && stage_records(b, d->gq0, d->gdq0)) a.staged |= 1;
     if (d->gtau && stage_records(b, d->gtau) && (d->gtau_step_stride * (int64_t)sizeof(double)) % 128 == 0) a.staged |= 2;
     a.t = k.table;
-    RDYN_HIP_TRY(rdyn_launch_rollout_adjoint(k.sw->n_joints(), a, k.stream));
+    if (!with_pg)
+    {
+      RDYN_HIP_TRY(rdyn_launch_rollout_adjoint(k.sw->n_joints(), a, k.stream));
+      return RDYN_OK;
+    }
+    const int C = n_comps > 0 ? rdyn_components_columns(comps, n_comps) : 0;
+    double* const acc = (double*)workspace;
+    int32_t* const st_final = (int32_t*)((char*)workspace + PL.st);
+    RdynParamSumArgs sa;
+    memset(&sa, 0, sizeof sa);
+    sa.n_full = c->n_joints();
+    if (k.sw != c)
+    {
+      st = device_expand(c, &sa.expand);
+      if (st != RDYN_OK) return st;
+      for (int f = 0; f < c->n_joints(); ++f) sa.red_of[f] = c->red_of[f];
+    }
+    if (d->integrator == RDYN_INTEGRATOR_RK4)
+      RDYN_HIP_TRY(rdyn_launch_rollout_adjoint_params_rk4(k.sw->n_joints(), a, acc, N, st_final, C, k.stream));
+    else
+      RDYN_HIP_TRY(rdyn_launch_rollout_adjoint_params_euler(k.sw->n_joints(), a, acc, N, st_final, C, k.stream));
+    sa.S = (const double*)((char*)workspace + PL.S);
+    sa.pi_sum = pg->gpi;
+    sa.comp_sum = pg->gcomp;
+    sa.accumulate = pg->accumulate;
+    sa.n_swept = k.sw->n_joints();
+    sa.n_comp_cols = C;
+    RDYN_HIP_TRY(rdyn_launch_parameter_sums(acc, N, 1, N, st_final, sa, k.stream));
     return RDYN_OK;
   }
   if (T > 0 && (st = long_deriv_lds_refusal(c, who)) != RDYN_OK) return st;
@@ -828,4 +1078,24 @@ int rdyn_rollout_adjoint(const rdyn_chain* c, const rdyn_batch* b, const rdyn_ro
   u.status = d->status;
   RDYN_HIP_TRY(update(RDYN_ADJ_OP_OUT));
   return RDYN_OK;
+}
+}  // namespace
+
+int rdyn_rollout_adjoint(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_adjoint_desc* d, const rdyn_component* comps, int n_comps,
+                         int64_t chunk_samples, void* workspace, size_t workspace_bytes)
+{
+  return rollout_adjoint(c, b, d, comps, n_comps, nullptr, false, chunk_samples, workspace, workspace_bytes, "rdyn_rollout_adjoint");
+}
+
+size_t rdyn_rollout_adjoint_parameters_workspace_bytes(const rdyn_chain* c, const rdyn_rollout_adjoint_desc* d, const rdyn_component* comps,
+                                                       int n_comps, int64_t n_samples, int64_t chunk_samples)
+{
+  return (!d || chunk_samples < 0) ? 0 : adjoint_param_layout(c, comps, n_comps, n_samples).total;
+}
+
+int rdyn_rollout_adjoint_parameters(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_adjoint_desc* d, const rdyn_component* comps,
+                                    int n_comps, const rdyn_parameter_gradient* pg, int64_t chunk_samples, void* workspace,
+                                    size_t workspace_bytes)
+{
+  return rollout_adjoint(c, b, d, comps, n_comps, pg, true, chunk_samples, workspace, workspace_bytes, "rdyn_rollout_adjoint_parameters");
 }

@@ -192,6 +192,7 @@ void build_sorted_view(rdyn_chain* c)
   std::unique_ptr<rdyn_chain> s(new rdyn_chain());
   s->joints = c->joints;
   s->links = c->links;
+  s->pi_set = c->pi_set;
   s->moveable_names = c->moveable_names;
   memcpy(s->gravity, c->gravity, sizeof s->gravity);
   s->q_max = c->q_max;
@@ -359,6 +360,7 @@ void rdyn_chain_finalize(rdyn_chain* c)
     K.in_idx = -1;
     // child link nominal parameters (Link::fromUrdf 288-328, getNominalParameters 399-417)
     link_parameters(c->links[j + 1], K.pi, nullptr, nullptr);
+    if (!c->pi_set.empty()) memcpy(K.pi, c->pi_set.data() + (size_t)10 * j, sizeof K.pi);
 
     // limits (primitives_impl.h:85-143).  Where the reference leaves a member uninitialised
     // (m_Dq_max without <limit>), 1e10 is used.
@@ -482,9 +484,34 @@ int rdyn_chain_clone(const rdyn_chain* chain, rdyn_chain** out)
   rdyn_chain* c = new rdyn_chain();
   c->joints = chain->joints;
   c->links = chain->links;
+  c->pi_set = chain->pi_set;
   c->moveable_names = chain->moveable_names;
   c->active = chain->active;
   memcpy(c->gravity, chain->gravity, sizeof c->gravity);
+  rdyn_chain_finalize(c);
+  *out = c;
+  return RDYN_OK;
+}
+
+int rdyn_chain_with_parameters(const rdyn_chain* chain, const double* pi, rdyn_chain** out)
+{
+  if (!chain || !out || (!pi && chain->n_joints() > 0))
+  {
+    rdyn_set_error("rdyn_chain_with_parameters: null argument");
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  *out = nullptr;
+  const int np = 10 * chain->n_joints();
+  for (int i = 0; i < np; ++i)
+    if (!std::isfinite(pi[i]))
+    {
+      rdyn_set_error("rdyn_chain_with_parameters: parameter %d of link '%s' is not finite", i % 10, chain->links[i / 10 + 1].name);
+      return RDYN_ERR_INVALID_ARGUMENT;
+    }
+  rdyn_chain* c = nullptr;
+  const int st = rdyn_chain_clone(chain, &c);
+  if (st != RDYN_OK) return st;
+  c->pi_set.assign(pi, pi + np);
   rdyn_chain_finalize(c);
   *out = c;
   return RDYN_OK;
@@ -582,7 +609,17 @@ int rdyn_chain_link_parameters(const rdyn_chain* c, int i, double pi[10], double
     return RDYN_ERR_INVALID_ARGUMENT;
   }
   double tmp[10];
-  link_parameters(c->links[i], pi ? pi : tmp, mass, cog);
+  if (i == 0 || c->pi_set.empty())
+  {
+    link_parameters(c->links[i], pi ? pi : tmp, mass, cog);
+    return RDYN_OK;
+  }
+  // parameters set by rdyn_chain_with_parameters: the mass and the centre of gravity follow from them (a massless link: the origin)
+  const double* const p = c->pi_set.data() + (size_t)10 * (i - 1);
+  if (pi) memcpy(pi, p, sizeof(double) * 10);
+  if (mass) *mass = p[0];
+  if (cog)
+    for (int k = 0; k < 3; ++k) cog[k] = p[0] != 0.0 ? p[1 + k] / p[0] : 0.0;
   return RDYN_OK;
 }
 

@@ -18,6 +18,10 @@ struct rdyn_chain
   std::vector<std::string> moveable_names;  // m_moveable_joints_name
   std::vector<int> active;                  // m_active_joints: chain index per input
   double gravity[3];
+  // rdyn_chain_with_parameters: the parameters of the child links as given, [10 n_joints] in the order of rdyn_nominal_parameters; they
+  // stand in for what the link descriptions give (empty: none were set).  Stored as they are, so a massless link with a first moment
+  // or an inertia -- which no rdyn_link_desc expresses -- is kept, and rdyn_nominal_parameters returns the very bits handed in.
+  std::vector<double> pi_set;
   // per chain joint limits (Joint::fromUrdf, primitives_impl.h:85-143)
   std::vector<double> q_max, q_min, dq_max, ddq_max, tau_max;
 

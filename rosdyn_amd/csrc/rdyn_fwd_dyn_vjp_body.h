@@ -38,145 +38,68 @@ template <int NJ, class QF, class DQF, class EARLY>
 __device__ __forceinline__ bool fwd_dyn_vjp_eval(ChainPtr c, const RdynComponentTable& tb, QF q_of, DQF dq_of, double (&rhs)[NJ],
                                                  double (&ab)[NJ], double (&qb)[NJ], double (&vb)[NJ], bool want_q, bool want_v, EARLY early)
 {
-  bool fin = true;
-#pragma unroll
-  for (int f = 0; f < NJ; ++f)
-  {
-    const int idx = c->j[f].in_idx;
-    qb[f] = vb[f] = 0.0;
-    if (idx < 0) continue;
-    const double qv = q_of(f, idx), dqv = dq_of(f, idx);
-    fin = fin && vjp_finite(qv) && vjp_finite(dqv) && vjp_finite(rhs[f]) && vjp_finite(ab[f]);
-    rhs[f] -= joint_component_torque(tb, idx, qv, dqv);
-  }
+#define RDYN_VJP_PARAMS 0
+#include "rdyn_fwd_dyn_vjp_body.inc"
+#undef RDYN_VJP_PARAMS
+}
 
-#define RDYN_FWD_Q(f, idx) q_of(f, idx)
-#define RDYN_FWD_DQ(f, idx) dq_of(f, idx)
-#include "rdyn_fwd_dyn_body.inc"
-#undef RDYN_FWD_Q
-#undef RDYN_FWD_DQ
-  // (in scope from here on: sv0, sv1 = sin q / 1 - cos q by chain joint, M = the factor, rhs = ddq, ok)
+// The same product with a hook on every link of the primal sweep: what the gradients with respect to the model's parameters are made of
+// (rdyn_fwd_dyn_param_vjp.hip, rdyn_rollout_adjoint_params.hip; rdyn_fwd_dyn_vjp_body.inc says what the hook is given).
+template <int NJ, class QF, class DQF, class EARLY, class LINK>
+__device__ __forceinline__ bool fwd_dyn_vjp_params_eval(ChainPtr c, const RdynComponentTable& tb, QF q_of, DQF dq_of, double (&rhs)[NJ],
+                                                        double (&ab)[NJ], double (&qb)[NJ], double (&vb)[NJ], bool want_q, bool want_v, EARLY early,
+                                                        LINK link)
+{
+#define RDYN_VJP_PARAMS 1
+#include "rdyn_fwd_dyn_vjp_body.inc"
+#undef RDYN_VJP_PARAMS
+}
 
-  // ---- w = L^-T L^-1 ab (identity rows for locked joints: their entries stay 0)
-#pragma unroll
-  for (int i = 0; i < NJ; ++i)
-  {
-    double v = ab[i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) v = fma(-M[TRI(i, k)], ab[k], v);
-    ab[i] = v * M[TRI(i, i)];
-  }
-#pragma unroll
-  for (int i = NJ - 1; i >= 0; --i)
-  {
-    double v = ab[i];
-#pragma unroll
-    for (int k = i + 1; k < NJ; ++k) v = fma(-M[TRI(k, i)], ab[k], v);
-    ab[i] = v * M[TRI(i, i)];
-  }
-  const bool good = ok && fin;
-  early(good, rhs);
-  if (!want_q && !want_v) return good;  // wave-uniform
+// What a link hook makes of its arguments: g = -(Y' w) of the link, the ten entries in the order of rdyn_nominal_parameters.  w' tau is
+// the power of the link wrenches f = m d + alpha x h + omega x (omega x h), n = I alpha + omega x I omega + h x d (link_wrench) on the
+// twists (ov, vv), so with d = acc + omega x v and e = ov x omega
+//     d/dm = vv . d      d/dh = vv x alpha + omega x (omega x vv) + d x ov      d/dI = the six entries of sym(ov alpha' + e omega')
+__device__ __forceinline__ void link_parameter_row(V3 om, V3 vl, V3 al, V3 acc, V3 ov, V3 vv, double (&g)[10])
+{
+  const V3 d = acc + cross(om, vl);
+  const V3 e = cross(ov, om);
+  const V3 gh = cross(vv, al) + cross(om, cross(om, vv)) + cross(d, ov);
+  g[0] = -dot(vv, d);
+  g[1] = -gh.x;
+  g[2] = -gh.y;
+  g[3] = -gh.z;
+  g[4] = -fma(ov.x, al.x, e.x * om.x);
+  g[5] = -(fma(ov.x, al.y, ov.y * al.x) + fma(e.x, om.y, e.y * om.x));
+  g[6] = -(fma(ov.x, al.z, ov.z * al.x) + fma(e.x, om.z, e.z * om.x));
+  g[7] = -fma(ov.y, al.y, e.y * om.y);
+  g[8] = -(fma(ov.y, al.z, ov.z * al.y) + fma(e.y, om.z, e.z * om.y));
+  g[9] = -fma(ov.z, al.z, e.z * om.z);
+}
 
-  // ---- primal forward sweep at ddq: the state of every link, its net wrench
-  double dqs[NJ];
-  V3 W[NJ], VL[NJ], AL[NJ], AC[NJ], Fc[NJ], Nc[NJ];
+// ... and of the components: x[k * ld] += -row_k w_j for every column k of the list, in column order -- row the regressor row of the
+// component (rdyn_component_row.h) at q / dq of its joint j, w by chain joint.  q, dq by chain joint as well.
+template <int NJ>
+__device__ __forceinline__ void component_parameter_rows(ChainPtr c, const RdynComponentTable& tb, const double (&q)[NJ], const double (&dq)[NJ],
+                                                         const double (&w)[NJ], double* x, int64_t ld)
+{
+  int col = 0;
+#pragma unroll 1
+  for (int i = 0; i < tb.n_comps; ++i)
   {
-    V3 w = mk(0, 0, 0), vl = mk(0, 0, 0), al = mk(0, 0, 0);
-    V3 acc = mk(-c->g[0], -c->g[1], -c->g[2]);  // base "acceleration" -g
+    const RdynComponent& cp = tb.comps[i];
+    double wj = 0.0, qj = 0.0, dqj = 0.0;
 #pragma unroll
     for (int f = 0; f < NJ; ++f)
-    {
-      JointRef J = c->j[f];
-      const double dqf = J.in_idx >= 0 ? dq_of(f, J.in_idx) : 0.0;
-      dqs[f] = dqf;
-      double R[9];
-      V3 t;
-      joint_transform(J, sv0[f], sv1[f], R, t);
-      primal_step(J, R, t, dqf, rhs[f], w, vl, al, acc);
-      W[f] = w; VL[f] = vl; AL[f] = al; AC[f] = acc;
-      link_wrench(J, w, vl, al, acc, Fc[f], Nc[f]);
-    }
-  }
-  // ---- primal backward pass: Fc, Nc[f] = the wrench through joint f (everything downstream), about link f + 1's origin, own frame
-#pragma unroll
-  for (int f = NJ - 1; f >= 1; --f)
-  {
-    double R[9];
-    V3 t;
-    joint_transform(c->j[f], sv0[f], sv1[f], R, t);
-    const V3 Fp = rot(R, Fc[f]);
-    Nc[f - 1] = Nc[f - 1] + rot(R, Nc[f]) + cross(t, Fp);
-    Fc[f - 1] = Fc[f - 1] + Fp;
-  }
-
-  // ---- one column per input joint, reduced against w row by row: KIND 0 d / d q_k, KIND 1 d / d Dq_k
-  auto columns = [&](auto kind_tag, double (&out)[NJ]) {
-    constexpr int KIND = decltype(kind_tag)::value;
-#pragma unroll
-    for (int k = 0; k < NJ; ++k)
-    {
-      JointRef Jk = c->j[k];
-      const int col = Jk.in_idx;
-      if (col < 0) continue;
-      V3 dFo[NJ], dNo[NJ];  // (entries k .. NJ - 1 are used)
+      if (c->j[f].in_idx == cp.joint)
       {
-        Tangent d = tangent_seed(KIND, Jk.type, ld3(Jk.u), W[k], VL[k], AL[k], AC[k]);
-        tangent_wrench(Jk, W[k], VL[k], d, dFo[k], dNo[k]);
-#pragma unroll
-        for (int f = k + 1; f < NJ; ++f)
-        {
-          JointRef J = c->j[f];
-          double R[9];
-          V3 t;
-          joint_transform(J, sv0[f], sv1[f], R, t);
-          tangent_step(J, R, t, dqs[f], d);
-          tangent_wrench(J, W[f], VL[f], d, dFo[f], dNo[f]);
-        }
+        wj = w[f];
+        qj = q[f];
+        dqj = dq[f];
       }
-      double r = 0.0;  // column k of dtau . w, the rows from the tip down
-      V3 dF = mk(0, 0, 0), dN = mk(0, 0, 0);
-#pragma unroll
-      for (int f = NJ - 1; f >= 0; --f)
-      {
-        JointRef J = c->j[f];
-        const int type = J.type;
-        const V3 u = ld3(J.u);
-        if (f >= k)
-        {
-          dF = dF + dFo[f];
-          dN = dN + dNo[f];
-        }
-        if (J.in_idx >= 0)
-        {
-          if (type == RDYN_REVOLUTE) r = fma(dot(u, dN), ab[f], r);
-          else if (type == RDYN_PRISMATIC) r = fma(dot(u, dF), ab[f], r);
-        }
-        if (f == 0) break;
-        if (KIND == 0 && f == k)
-        {
-          // the derivative of joint k's own transform applied to the primal wrench it transmits
-          if (type == RDYN_REVOLUTE)
-          {
-            dF = dF + cross(u, Fc[k]);
-            dN = dN + cross(u, Nc[k]);
-          }
-          else if (type == RDYN_PRISMATIC)
-            dN = dN + cross(u, Fc[k]);
-        }
-        double R[9];
-        V3 t;
-        joint_transform(J, sv0[f], sv1[f], R, t);
-        const V3 Fp = rot(R, dF);
-        dN = rot(R, dN) + cross(t, Fp);
-        dF = Fp;
-      }
-      out[k] = -fma(joint_component_slope(tb, col, KIND, q_of(k, col), dqs[k]), ab[k], r);
-    }
-  };
-  if (want_q) columns(std::integral_constant<int, 0>(), qb);
-  if (want_v) columns(std::integral_constant<int, 1>(), vb);
-  return good;
+    double row[3];
+    const int nc = component_row(cp, cp.type == RDYN_COMP_SPRING ? qj : dqj, row);
+    for (int k = 0; k < nc; ++k, ++col) x[col * ld] += -(row[k] * wj);
+  }
 }
 }  // namespace
 #endif

@@ -588,6 +588,55 @@ struct RdynFwdDynVjpArgs
   RdynComponentTable t;
 };
 hipError_t rdyn_launch_forward_dynamics_vjp(int n_joints, const RdynFwdDynVjpArgs& a, hipStream_t st);
+// ... with respect to the parameters (rdyn_fwd_dyn_param_vjp.hip): pi_bar = -Y(q, dq, ddq)' w, comp_bar = -C(q, dq)' w with
+// w = tau_bar = M^-1 ddq_bar.  v = the arguments of the product above (q_bar, dq_bar are not used); the swept chain has n_joints links.
+// Rows: column k of sample s at pi_bar[s * pi_ss + k * pi_sc] (10 n_full columns) and comp_bar[s * comp_ss + k * comp_sc]
+// (n_comp_cols columns); partials: [waves][10 n_joints + n_comp_cols], the sums of each wave's samples, the swept chain's columns.
+// expand: null, or the blocks X_f of the chain of n_full joints the swept chain is the companion of, red_of its link -> body map.
+struct RdynFwdDynParamVjpArgs
+{
+  RdynFwdDynVjpArgs v;
+  double *pi_bar, *comp_bar;  // may be null
+  int64_t pi_ss, pi_sc, comp_ss, comp_sc;
+  double* partials;           // may be null
+  int n_comp_cols;
+  const double* expand;
+  int n_full;
+  int red_of[RDYN_MAX_JOINTS];  // (ints: RdynSweepArgs::expand_red_of says why)
+};
+hipError_t rdyn_launch_forward_dynamics_parameter_vjp(int n_joints, const RdynFwdDynParamVjpArgs& a, hipStream_t st);
+// S[col] = the sum over r < n_rows of x[r * row_stride + col * col_stride], col < 10 n_swept + n_comp_cols, the rows whose status word is
+// not 1 left out (status null: none) -> pi_sum[10 n_full], comp_sum[n_comp_cols] (each may be null; accumulate: += instead of =),
+// through expand / red_of as above (null: n_full = n_swept).  S is workspace.  Two launches, fixed order of additions.
+struct RdynParamSumArgs
+{
+  const double* S;
+  double *pi_sum, *comp_sum;
+  int accumulate, n_swept, n_full, n_comp_cols;
+  const double* expand;
+  int red_of[RDYN_MAX_JOINTS];  // (ints: RdynSweepArgs::expand_red_of says why)
+};
+hipError_t rdyn_launch_parameter_sums(const double* x, int64_t n_rows, int64_t row_stride, int64_t col_stride, const int32_t* status,
+                                      const RdynParamSumArgs& a, hipStream_t st);
+// ... its two halves: S[col] of `cols` columns alone, and S -> the caller's vectors
+hipError_t rdyn_launch_parameter_column_sums(const double* x, int64_t n_rows, int64_t row_stride, int64_t col_stride, const int32_t* status,
+                                             int cols, double* S, hipStream_t st);
+hipError_t rdyn_launch_parameter_sums_finish(const RdynParamSumArgs& a, hipStream_t st);
+// ... of a chain with more input joints than the unrolled kernels sweep: the rows of one chunk from its element-major image [Y (P) | C (K)]
+// (row j * cnt + s, column stride lda) and tau_bar / status of the chunk's samples (pointers at the chunk's first sample, tau_bar
+// addressed like q): row[col] = -sum_j image(j, s, col) tau_bar_j, quiet NaN where status is not 1.  pi_rows / comp_rows may be null.
+struct RdynParamProductArgs
+{
+  const double* image;
+  int64_t cnt, lda;
+  int n, P, K;
+  const double* tau_bar;
+  int64_t in_ss, in_sj;
+  const int32_t* status;
+  double *pi_rows, *comp_rows;
+  int64_t pi_ss, pi_sc, comp_ss, comp_sc;
+};
+hipError_t rdyn_launch_parameter_rows_from_image(const RdynParamProductArgs& a, hipStream_t st);
 // ... of a chain with more input joints than the unrolled kernels sweep: the three transposed products from the matrices
 // rdyn_forward_dynamics_derivatives left element-major in the workspace (element e = i + n k of sample s of the chunk at X[e * ld + s]);
 // status = what that call wrote for the chunk (not null)
@@ -631,6 +680,13 @@ struct RdynRolloutAdjointArgs
   RdynComponentTable t;
 };
 hipError_t rdyn_launch_rollout_adjoint(int n_joints, const RdynRolloutAdjointArgs& a, hipStream_t st);
+// ... with the gradients with respect to the parameters (rdyn_rollout_adjoint_params.hip, one object per integrator): the same sweep, and
+// every product adds its rows to acc[col * ld + s] (10 n_joints + n_comp_cols columns, zeroed by the kernel), status[s] = the sample's
+// final verdict; rdyn_launch_parameter_sums(acc, n_samples, 1, ld, status, ...) makes the sums of them
+hipError_t rdyn_launch_rollout_adjoint_params_euler(int n_joints, const RdynRolloutAdjointArgs& a, double* acc, int64_t ld, int32_t* status,
+                                                    int n_comp_cols, hipStream_t st);
+hipError_t rdyn_launch_rollout_adjoint_params_rk4(int n_joints, const RdynRolloutAdjointArgs& a, double* acc, int64_t ld, int32_t* status,
+                                                  int n_comp_cols, hipStream_t st);
 // ... of a chain with more input joints than the unrolled kernels sweep: the element-wise updates between the passes of the host loop
 // (rdyn_api_dynamics.cpp).  Every array holds count = n * n_samples doubles in the batch's layout; op selects the update (the formulas are at the
 // head of rdyn_rollout_adjoint.hip).

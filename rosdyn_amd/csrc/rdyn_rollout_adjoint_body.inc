@@ -1,0 +1,227 @@
+// rdyn_rollout_adjoint_body.inc -- one lane's backward sweep over the horizon of a rollout (the head of rdyn_rollout_adjoint.hip has the
+// scheme), included as text by k_rollout_adjoint and k_rollout_adjoint_params so that the first compiles to exactly what it compiled to
+// before the second existed.  Expects: template parameters NJ, INTEGRATOR; the kernel argument a (RdynRolloutAdjointArgs).
+// RDYN_ADJ_PARAMS 1 (k_rollout_adjoint_params; also expects p, RdynAdjointParamAcc): every product adds its parameter rows -- the ten
+// entries per link of link_parameter_row, then the component columns -- to the lane's own accumulators p.acc[col * p.ld + s], zeroed
+// here first, and the sample's final verdict goes to p.status[s]: the host sums the columns over the samples that ended alive.
+  const ChainPtr c = as_const(a.chain);
+  const int lane = threadIdx.x;
+  const int64_t s_wave = (int64_t)blockIdx.x * 64;
+  const int64_t s = s_wave + lane;
+  if (s >= a.n_samples) return;
+  const bool full = a.n_samples - s_wave >= 64;  // wave-uniform
+  const bool stg_x = (a.staged & 1) && full, stg_tau = (a.staged & 2) && full;
+  const double dt = a.dt;
+  const int T = a.n_steps;
+  const int64_t so = s * a.in_ss;
+  SmallRecords sm;
+  if (stg_x || stg_tau)
+  {
+    extern __shared__ __attribute__((aligned(16))) char adjoint_stage_lds[];
+    sm.init(adjoint_stage_lds, c->n_active, lane);
+  }
+  const double qnan = __builtin_nan("");
+#if RDYN_ADJ_PARAMS
+  // the lane's accumulators, zeroed; the link hook of a product
+  double* const pacc = p.acc + s;
+#pragma unroll 1
+  for (int k = 0; k < 10 * NJ + p.n_comp_cols; ++k) pacc[k * p.ld] = 0.0;
+  auto link = [&](int f, JointRef, V3 om, V3 vl, V3 al, V3 acc, V3 ov, V3 vv) {
+    double g[10];
+    link_parameter_row(om, vl, al, acc, ov, vv, g);
+    double* const x = pacc + (int64_t)(10 * f) * p.ld;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) x[k * p.ld] += g[k];
+  };
+#endif
+
+  // lambda_T (the end seeds may alias gq0 / gdq0: read whole before the first store)
+  double lq[NJ], lv[NJ], gsum[NJ];
+  load_record<NJ>(c, a.gq_end ? a.gq_end + so : nullptr, a.in_sj, lq);
+  load_record<NJ>(c, a.gdq_end ? a.gdq_end + so : nullptr, a.in_sj, lv);
+#pragma unroll
+  for (int f = 0; f < NJ; ++f) gsum[f] = 0.0;
+  if (T > 0)
+  {
+    double g[NJ];
+    if (a.gq_traj)
+    {
+      load_record<NJ>(c, a.gq_traj + (int64_t)(T - 1) * a.gtraj_step + so, a.in_sj, g);
+#pragma unroll
+      for (int f = 0; f < NJ; ++f) lq[f] += g[f];
+    }
+    if (a.gdq_traj)
+    {
+      load_record<NJ>(c, a.gdq_traj + (int64_t)(T - 1) * a.gtraj_step + so, a.in_sj, g);
+#pragma unroll
+      for (int f = 0; f < NJ; ++f) lv[f] += g[f];
+    }
+  }
+  bool alive = true;
+
+#pragma unroll 1
+  for (int t = T - 1; t >= 0; --t)
+  {
+    double q[NJ], dq[NJ], tau[NJ], gt[NJ];
+    {
+      const int64_t ro = (int64_t)(t - 1) * a.traj_step + so;
+      load_record<NJ>(c, t == 0 ? a.q + so : a.q_traj + ro, a.in_sj, q);
+      load_record<NJ>(c, t == 0 ? a.dq + so : a.dq_traj + ro, a.in_sj, dq);
+      load_record<NJ>(c, a.tau + (int64_t)t * a.tau_step + so, a.in_sj, tau);
+    }
+    bool ok = true;
+    if (INTEGRATOR == RDYN_INTEGRATOR_SEMI_IMPLICIT_EULER)
+    {
+      double qb[NJ], vb[NJ];
+#pragma unroll
+      for (int f = 0; f < NJ; ++f)
+      {
+        lv[f] = fma(dt, lq[f], lv[f]);
+        gt[f] = dt * lv[f];  // mu; the product leaves tau_bar here
+      }
+#if RDYN_ADJ_PARAMS
+      ok = fwd_dyn_vjp_params_eval<NJ>(per_evaluation(c), a.t, [&](int f, int) { return q[f]; }, [&](int f, int) { return dq[f]; }, tau, gt, qb,
+                                       vb, true, true, [](bool, double (&)[NJ]) {}, link);
+      component_parameter_rows<NJ>(c, a.t, q, dq, gt, pacc + (int64_t)(10 * NJ) * p.ld, p.ld);
+#else
+      ok = fwd_dyn_vjp_eval<NJ>(per_evaluation(c), a.t, [&](int f, int) { return q[f]; }, [&](int f, int) { return dq[f]; }, tau, gt, qb, vb, true,
+                                true, [](bool, double (&)[NJ]) {});
+#endif
+#pragma unroll
+      for (int f = 0; f < NJ; ++f)
+      {
+        lq[f] += qb[f];
+        lv[f] += vb[f];
+      }
+    }
+    else
+    {
+      // ---- the stage states X2 .. X4 (X1 = x_t), rdyn_rollout_body.inc's arithmetic
+      double x2q[NJ], x2v[NJ], x3q[NJ], x3v[NJ], x4q[NJ], x4v[NJ];
+      {
+        double sq[NJ], kq[NJ];
+#pragma unroll
+        for (int f = 0; f < NJ; ++f)
+        {
+          sq[f] = q[f];
+          kq[f] = dq[f];
+          x2q[f] = x2v[f] = x3q[f] = x3v[f] = x4q[f] = x4v[f] = 0.0;
+        }
+#pragma unroll 1
+        for (int stage = 0; stage < 3; ++stage)
+        {
+          double rhs[NJ];
+#pragma unroll
+          for (int f = 0; f < NJ; ++f)
+          {
+            const int idx = c->j[f].in_idx;
+            rhs[f] = tau[f];
+            if (idx >= 0) rhs[f] -= joint_component_torque(a.t, idx, sq[f], kq[f]);
+          }
+          fwd_dyn_eval<NJ>(per_evaluation(c), sq, kq, rhs);  // (its pivot test runs again inside the stage's product)
+          const double cdt = stage == 2 ? dt : 0.5 * dt;  // of the NEXT stage
+#pragma unroll
+          for (int f = 0; f < NJ; ++f)
+          {
+            sq[f] = fma(cdt, kq[f], q[f]);
+            kq[f] = fma(cdt, rhs[f], dq[f]);
+            x2q[f] = stage == 0 ? sq[f] : x2q[f];
+            x2v[f] = stage == 0 ? kq[f] : x2v[f];
+            x3q[f] = stage == 1 ? sq[f] : x3q[f];
+            x3v[f] = stage == 1 ? kq[f] : x3v[f];
+            x4q[f] = stage == 2 ? sq[f] : x4q[f];
+            x4v[f] = stage == 2 ? kq[f] : x4v[f];
+          }
+        }
+      }
+      // ---- the four products, last stage first
+      double xq[NJ], xv[NJ], cq[NJ], cv[NJ];  // x_bar; the carry c_{i + 1} X_bar_{i + 1} into stage i's seed
+#pragma unroll
+      for (int f = 0; f < NJ; ++f)
+      {
+        xq[f] = lq[f];
+        xv[f] = lv[f];
+        cq[f] = cv[f] = gt[f] = 0.0;
+      }
+#pragma unroll 1
+      for (int i = 3; i >= 0; --i)
+      {
+        const double dtb = dt * ((i == 0 || i == 3) ? 1.0 / 6.0 : 1.0 / 3.0);
+        const double ci = i == 3 ? dt : 0.5 * dt;
+        double sq[NJ], sv[NJ], rhs[NJ], mu[NJ], qb[NJ], vb[NJ];
+#pragma unroll
+        for (int f = 0; f < NJ; ++f)
+        {
+          sq[f] = i == 0 ? q[f] : (i == 1 ? x2q[f] : (i == 2 ? x3q[f] : x4q[f]));
+          sv[f] = i == 0 ? dq[f] : (i == 1 ? x2v[f] : (i == 2 ? x3v[f] : x4v[f]));
+          rhs[f] = tau[f];
+          cq[f] = fma(dtb, lq[f], cq[f]);  // kq_i
+          mu[f] = fma(dtb, lv[f], cv[f]);  // kv_i
+        }
+#if RDYN_ADJ_PARAMS
+        ok = fwd_dyn_vjp_params_eval<NJ>(per_evaluation(c), a.t, [&](int f, int) { return sq[f]; }, [&](int f, int) { return sv[f]; }, rhs, mu,
+                                         qb, vb, true, true, [](bool, double (&)[NJ]) {}, link) &&
+             ok;
+        component_parameter_rows<NJ>(c, a.t, sq, sv, mu, pacc + (int64_t)(10 * NJ) * p.ld, p.ld);
+#else
+        ok = fwd_dyn_vjp_eval<NJ>(per_evaluation(c), a.t, [&](int f, int) { return sq[f]; }, [&](int f, int) { return sv[f]; }, rhs, mu, qb, vb,
+                                true, true, [](bool, double (&)[NJ]) {}) &&
+             ok;
+#endif
+#pragma unroll
+        for (int f = 0; f < NJ; ++f)
+        {
+          const double bv = cq[f] + vb[f];  // X_bar_i = (qb, bv)
+          gt[f] += mu[f];
+          xq[f] += qb[f];
+          xv[f] += bv;
+          cq[f] = ci * qb[f];
+          cv[f] = ci * bv;
+        }
+      }
+#pragma unroll
+      for (int f = 0; f < NJ; ++f)
+      {
+        lq[f] = xq[f];
+        lv[f] = xv[f];
+      }
+    }
+    alive = alive && ok;
+#pragma unroll
+    for (int f = 0; f < NJ; ++f)
+    {
+      lq[f] = alive ? lq[f] : qnan;
+      lv[f] = alive ? lv[f] : qnan;
+      gt[f] = alive ? gt[f] : qnan;
+      gsum[f] += gt[f];
+    }
+    if (a.gtau && a.gtau_step)
+    {
+      const int64_t go = (int64_t)t * a.gtau_step;
+      put_record<NJ>(c, sm, stg_tau, gt, a.gtau + go + s_wave * a.in_ss, a.gtau + go + so, a.in_sj, lane);
+    }
+    if (t >= 1)
+    {
+      double g[NJ];
+      if (a.gq_traj)
+      {
+        load_record<NJ>(c, a.gq_traj + (int64_t)(t - 1) * a.gtraj_step + so, a.in_sj, g);
+#pragma unroll
+        for (int f = 0; f < NJ; ++f) lq[f] += g[f];
+      }
+      if (a.gdq_traj)
+      {
+        load_record<NJ>(c, a.gdq_traj + (int64_t)(t - 1) * a.gtraj_step + so, a.in_sj, g);
+#pragma unroll
+        for (int f = 0; f < NJ; ++f) lv[f] += g[f];
+      }
+    }
+  }
+
+  if (a.status) a.status[s] = alive ? 1 : -1;
+#if RDYN_ADJ_PARAMS
+  p.status[s] = alive ? 1 : -1;
+#endif
+  if (a.gtau && !a.gtau_step) put_record<NJ>(c, sm, stg_tau, gsum, a.gtau + s_wave * a.in_ss, a.gtau + so, a.in_sj, lane);
+  if (a.gq0) put_record<NJ>(c, sm, stg_x, lq, a.gq0 + s_wave * a.in_ss, a.gq0 + so, a.in_sj, lane);
+  if (a.gdq0) put_record<NJ>(c, sm, stg_x, lv, a.gdq0 + s_wave * a.in_ss, a.gdq0 + so, a.in_sj, lane);

@@ -926,6 +926,47 @@ public:
     chk(rdyn_forward_dynamics_vjp(m_h, &b, comps.empty() ? nullptr : comps.data(), (int)comps.size(), tau, DDq_bar, q_bar, Dq_bar, tau_bar, ddq, status,
                                   chunk_samples, workspace, workspace_bytes));
   }
+  // ---- gradients with respect to the model's parameters (no reference counterpart)
+  // the chain with the inertial parameters pi (10 per chain joint, the order of getNominalParameters; stored as given): an independent
+  // chain equal to clone() in everything else: rdyn_chain_with_parameters
+  ChainPtr withParameters(const std::vector<double>& pi) const
+  {
+    if ((int)pi.size() != 10 * rdyn_chain_joints_number(m_h)) throw std::invalid_argument("withParameters: 10 values per chain joint");
+    rdyn_chain* h = nullptr;
+    if (rdyn_chain_with_parameters(m_h, pi.data(), &h) != RDYN_OK) throw std::invalid_argument(rdyn_last_error());
+    return ChainPtr(new Chain(h, AdoptHandle()));
+  }
+  // reverse-mode product of the forward dynamics of a batch with respect to the parameters: pi_bar = -Y' w, comp_bar = -C' w, w = M^-1 DDq_bar.
+  // pi_bar / comp_bar: the per-sample rows (10 joints / rdyn_components_columns doubles per sample, the layout of b.q); pi_bar_sum /
+  // comp_bar_sum: their sums over the samples with status 1 (accumulate: add to what is there); every output may be null (not all of the
+  // first five); the workspace is needed for the sums only: rdyn_forward_dynamics_parameter_vjp
+  size_t getJointAccelerationParameterVjpWorkspaceBytes(const std::vector<rdyn_component>& comps, int64_t n_samples, int64_t chunk_samples = 0) const
+  {
+    return rdyn_forward_dynamics_parameter_vjp_workspace_bytes(m_h, comps.empty() ? nullptr : comps.data(), (int)comps.size(), n_samples, chunk_samples);
+  }
+  void getJointAccelerationParameterVjpBatch(const std::vector<rdyn_component>& comps, const rdyn_batch& b, const double* tau, const double* DDq_bar,
+                                             double* pi_bar, double* comp_bar, double* pi_bar_sum, double* comp_bar_sum, bool accumulate,
+                                             double* tau_bar, double* ddq, int32_t* status, int64_t chunk_samples, void* workspace,
+                                             size_t workspace_bytes) const
+  {
+    chk(rdyn_forward_dynamics_parameter_vjp(m_h, &b, comps.empty() ? nullptr : comps.data(), (int)comps.size(), tau, DDq_bar, pi_bar, comp_bar,
+                                            pi_bar_sum, comp_bar_sum, accumulate ? 1 : 0, tau_bar, ddq, status, chunk_samples, workspace,
+                                            workspace_bytes));
+  }
+  // rolloutAdjointBatch with the gradients with respect to the parameters summed over the samples (pg.gpi: 10 per chain joint, pg.gcomp:
+  // rdyn_components_columns; desc.gq0, gdq0, gtau may all be null): rdyn_rollout_adjoint_parameters
+  size_t rolloutParameterAdjointWorkspaceBytes(const std::vector<rdyn_component>& comps, const rdyn_rollout_adjoint_desc& desc, int64_t n_samples,
+                                               int64_t chunk_samples = 0) const
+  {
+    return rdyn_rollout_adjoint_parameters_workspace_bytes(m_h, &desc, comps.empty() ? nullptr : comps.data(), (int)comps.size(), n_samples,
+                                                           chunk_samples);
+  }
+  void rolloutParameterAdjointBatch(const std::vector<rdyn_component>& comps, const rdyn_batch& b, const rdyn_rollout_adjoint_desc& desc,
+                                    const rdyn_parameter_gradient& pg, int64_t chunk_samples, void* workspace, size_t workspace_bytes) const
+  {
+    chk(rdyn_rollout_adjoint_parameters(m_h, &b, &desc, comps.empty() ? nullptr : comps.data(), (int)comps.size(), &pg, chunk_samples, workspace,
+                                        workspace_bytes));
+  }
   // derivatives of the joint torque of a batch (b.q, b.dq, b.ddq; every output n x n per sample, any may be null): rdyn_joint_torque_derivatives
   void getJointTorqueDerivativesBatch(const rdyn_batch& b, double* dtau_dq, double* dtau_dDq, double* M = nullptr) const
   {
@@ -949,6 +990,9 @@ public:
   void getTwistBatch(const rdyn_batch& b, double* twists, double* dtwists) const { chk(rdyn_twist(m_h, &b, twists, dtwists)); }
 
 private:
+  // takes over a handle the C-ABI made (withParameters)
+  struct AdoptHandle {};
+  Chain(rdyn_chain* h, AdoptHandle) : m_h(h) { refresh(); }
   rdyn_chain* m_h = nullptr;
   unsigned int m_links_number = 0, m_joints_number = 0, m_active_joints_number = 0;
   bool m_is_chain_ok = true;
