@@ -263,9 +263,10 @@ int rdyn_joint_inertia(const rdyn_chain* chain, const rdyn_batch* batch, double*
  * with M exactly what rdyn_joint_inertia returns for this chain AS CONFIGURED (input-joint selection and order included: joints that
  * are not input joints stay locked at 0) and h what rdyn_joint_torque_nonlinear returns (Coriolis, centrifugal and gravity terms).
  * batch->q, batch->dq required, batch->ddq ignored.  tau: n per sample, layout of batch->q; ddq: same shape and layout, may alias tau.
- * External wrenches and component (friction / spring) torques are additive in tau and are NOT parameters of this call; a caller folds
- * them in first:  tau - tau_add  with tau_add from rdyn_components_regressor(..., tau_add), and
- * tau - (rdyn_joint_torque_ext(q, 0, 0, ext) - rdyn_joint_torque(q, 0, 0))  for external wrenches.
+ * External wrenches and component (friction / spring) torques are additive in tau and are NOT parameters of this call:
+ * rdyn_forward_dynamics_components takes the components and rdyn_forward_dynamics_ext both (below, behind the component types); they
+ * subtract  tau_add of rdyn_components_regressor(..., tau_add)  and
+ * rdyn_joint_torque_ext(q, 0, 0, ext) - rdyn_joint_torque(q, 0, 0)  inside the one launch.
  * status (device int32 per sample, may be NULL): 1 solved; -1 = M not positive definite by the rule of rdyn_local_ik (a Cholesky pivot
  * <= 1e-10 trace(M)): what a fixed joint listed as an input joint, or a tail of links without <inertial>, produces.  A -1 sample gets
  * quiet NaN in all its ddq entries; no sample's failure affects another sample.
@@ -298,8 +299,9 @@ int rdyn_forward_dynamics(const rdyn_chain* chain, const rdyn_batch* batch, cons
  * rdyn_forward_dynamics.  From the failing step on every state of that sample -- the end state and all later trajectory records -- is
  * quiet NaN; the failure is sticky and no sample affects another.
  * Friction and spring components depend on the state, so unlike in rdyn_forward_dynamics a caller cannot fold them into tau across
- * steps: rdyn_rollout_components (below, behind the component types) takes them.  External wrenches are NOT parameters of either call
- * (left for a follow-up).  No joint limits, no adaptive steps.
+ * steps: rdyn_rollout_components (below, behind the component types) takes them.  External link wrenches give a joint torque that
+ * depends on q and cannot be folded in either: rdyn_rollout_ext (below, behind rdyn_rollout_components) takes them and evaluates them
+ * at every integrator stage.  No joint limits, no adaptive steps.
  * Chains swept in registers (at most RDYN_MAX_SWEPT_JOINTS input joints; longer chains through their rigid-body reduction): ONE kernel
  * launch for the whole horizon, the state in registers between the steps; a step reads n torques per sample and writes only the
  * trajectory record that is due; the workspace query returns 0 and workspace may be NULL.  More input joints (up to RDYN_MAX_JOINTS, any
@@ -464,6 +466,58 @@ int rdyn_forward_dynamics_components(const rdyn_chain* chain, const rdyn_batch* 
                                      size_t workspace_bytes);
 int rdyn_rollout_components(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_rollout_desc* desc, const rdyn_component* comps,
                             int n_comps, int64_t chunk_samples, void* workspace, size_t workspace_bytes);
+
+/* Forward dynamics and rollouts with external link wrenches: the forward side of rdyn_joint_torque_ext / getJointTorque(q, Dq, DDq,
+ * ext_wrenches_in_link_frame).  Let tau_E(q, ext) be the joint torque of the wrenches alone,
+ *     tau_E = rdyn_joint_torque_ext(q, 0, 0, ext) - rdyn_joint_torque(q, 0, 0)
+ * (equivalently rdyn_joint_torque_ext(q, 0, 0, ext) of the same chain with zero gravity): a wrench [force; torque] applied TO a chain
+ * link, given in that link's own frame, with the reference's twist-form transform (primitives_impl.h:1255) reproduced as it is.  tau_E is
+ * linear in ext, depends on q and not on Dq, and the base link's record does not enter.  Then
+ *     FD_E(q, Dq, tau, ext) = FD_c(q, Dq, tau - tau_E(q, ext))
+ * with FD_c the function of rdyn_forward_dynamics_components for the chain AS CONFIGURED (input-joint selection and order, locked joints,
+ * gravity, the component list; n_comps = 0 is the plain call).
+ *   rdyn_forward_dynamics_ext   ddq = FD_E(q, Dq, tau, ext); every other argument, the status and the aliasing rule (ddq may alias tau)
+ *                               are those of rdyn_forward_dynamics.  ext->step_stride is not read.
+ *   rdyn_rollout_ext            integrates x' = (Dq, FD_E(q, Dq, tau_t, ext_t)); the wrench of step t is held over the step like tau_t
+ *                               and evaluated at EVERY integrator stage at that stage's own q.  Everything else is rdyn_rollout's: the
+ *                               descriptor, sticky status, aliasing, trajectory records, the bitwise split of the horizon (with a
+ *                               per-step wrench sequence too: the later call starts at w + t0 * step_stride), independence from the
+ *                               chunk size.
+ * ext: see rdyn_ext_wrenches.  link = -1: w holds links_number x 6 doubles per sample, exactly the argument of rdyn_joint_torque_ext
+ * (sample-major: record after record; element-major: element e of sample s at w[e * n_samples + s]); link >= 0: 6 doubles per sample,
+ * the wrench of that one chain link (0 = the base link, which changes nothing; joints_number = the tool), the others zero.  The wrench
+ * arrays must not overlap an output.
+ * ext == NULL or ext->w == NULL IS rdyn_forward_dynamics_components / rdyn_rollout_components: the same kernels, the same bits, and the
+ * workspace queries equal the base queries.
+ * Status: the pivot rule of rdyn_forward_dynamics looks at M, which the wrenches do not enter.  A non-finite wrench entry therefore makes
+ * the sample's ddq NaN by propagation with status 1 in rdyn_forward_dynamics_ext; in a rollout the NaN state fails the pivot rule at the
+ * next evaluation, so the sample's status is -1 (and its state quiet NaN from then on) unless the entry was first read in the last
+ * evaluation of the horizon, where the end state is NaN with status 1.
+ * Chains of at most RDYN_MAX_SWEPT_JOINTS chain joints: still ONE launch, for one evaluation and for a whole horizon; the wrench enters
+ * the link's net wrench inside the forward sweep, no workspace.  More than RDYN_MAX_SWEPT_JOINTS input joints: the chunked route, whose
+ * wrench recursion takes the wrenches as it writes h (CORRECT, NOT FAST); the workspace is the base call's.  Long chains served through a
+ * reduced companion (more than RDYN_MAX_SWEPT_JOINTS chain joints, at most that many input joints): the wrenches belong to the original
+ * links, which the companion no longer has, so WITH wrenches these chains take the chunked route on the original chain (workspace: ask
+ * the queries below with the ext you will pass); without wrenches nothing changes for them.
+ * Errors, all RDYN_ERR_INVALID_ARGUMENT before any device work: every argument error of the base calls, and with wrenches a link outside
+ * [-1, joints_number], in rollouts a negative step_stride or a non-zero one smaller than one step's record (6 * links_number * n_samples,
+ * or 6 * n_samples for one link).  n_samples = 0 is RDYN_OK.  No allocation and no synchronisation: capturable into a graph once the
+ * chain has been used on the device. */
+typedef struct rdyn_ext_wrenches
+{
+  const double* w;      /* link = -1: links_number x 6 per sample, exactly the argument of rdyn_joint_torque_ext (record layout =
+                           batch->layout); link >= 0: 6 doubles per sample, [force; torque] applied to that chain link in its frame */
+  int32_t link;         /* -1 = every link; else a chain link index 0 .. joints_number (the tool is joints_number) */
+  int64_t step_stride;  /* rollouts only, in doubles: step t at w + t * step_stride; 0 = the same wrenches at every step */
+} rdyn_ext_wrenches;
+size_t rdyn_forward_dynamics_ext_workspace_bytes(const rdyn_chain* chain, const rdyn_ext_wrenches* ext, int64_t chunk_samples);
+int rdyn_forward_dynamics_ext(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_component* comps, int n_comps,
+                              const rdyn_ext_wrenches* ext, const double* tau, double* ddq, int32_t* status, int64_t chunk_samples,
+                              void* workspace, size_t workspace_bytes);
+size_t rdyn_rollout_ext_workspace_bytes(const rdyn_chain* chain, const rdyn_rollout_desc* desc, const rdyn_ext_wrenches* ext,
+                                        int64_t n_samples, int64_t chunk_samples);
+int rdyn_rollout_ext(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_rollout_desc* desc, const rdyn_component* comps,
+                     int n_comps, const rdyn_ext_wrenches* ext, int64_t chunk_samples, void* workspace, size_t workspace_bytes);
 
 /* Derivatives of the forward dynamics (no reference counterpart): the linearisation of DDq = FD_c(q, Dq, tau).  Per sample, with FD_c the
  * function of rdyn_forward_dynamics_components for the chain AS CONFIGURED (input-joint selection and order, locked joints, the reduced

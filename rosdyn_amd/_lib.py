@@ -47,6 +47,10 @@ class ParameterGradient(C.Structure):
 INTEGRATORS = {"semi_implicit_euler": 0, "euler": 0, "rk4": 1}
 
 
+class ExtWrenches(C.Structure):
+    _fields_ = [("w", C.c_void_p), ("link", C.c_int32), ("step_stride", C.c_int64)]
+
+
 class Component(C.Structure):
     _fields_ = [("type", C.c_int32), ("joint", C.c_int32), ("min_velocity", C.c_double), ("max_velocity", C.c_double),
                 ("parameters", C.c_double * 3)]
@@ -117,6 +121,10 @@ SYMBOLS = {
     "rdyn_rollout": (_I, [_VP, _BP, C.POINTER(RolloutDesc), C.c_int64, _VP, C.c_size_t]),
     "rdyn_forward_dynamics_components": (_I, [_VP, _BP, _VP, _I, _VP, _VP, _VP, C.c_int64, _VP, C.c_size_t]),
     "rdyn_rollout_components": (_I, [_VP, _BP, C.POINTER(RolloutDesc), _VP, _I, C.c_int64, _VP, C.c_size_t]),
+    "rdyn_forward_dynamics_ext_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(ExtWrenches), C.c_int64]),
+    "rdyn_forward_dynamics_ext": (_I, [_VP, _BP, _VP, _I, C.POINTER(ExtWrenches), _VP, _VP, _VP, C.c_int64, _VP, C.c_size_t]),
+    "rdyn_rollout_ext_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(RolloutDesc), C.POINTER(ExtWrenches), C.c_int64, C.c_int64]),
+    "rdyn_rollout_ext": (_I, [_VP, _BP, C.POINTER(RolloutDesc), _VP, _I, C.POINTER(ExtWrenches), C.c_int64, _VP, C.c_size_t]),
     "rdyn_joint_torque_derivatives": (_I, [_VP, _BP, _VP, _VP, _VP]),
     "rdyn_forward_dynamics_derivatives_workspace_bytes": (C.c_size_t, [_VP, C.c_int64]),
     "rdyn_forward_dynamics_derivatives": (_I, [_VP, _BP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP, C.c_size_t]),

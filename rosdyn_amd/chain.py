@@ -361,22 +361,56 @@ class Chain(object):
         assert components.n_active == self.getActiveJointsNumber(), "the ComponentSet was made for another number of active joints"
         return C.cast(components._arr, C.c_void_p), components.n_comps
 
-    def getJointAcceleration(self, q, Dq, tau, layout="sample", out=None, chunk_samples=0, workspace=None, components=None):
+    def _ext_wrenches(self, q, N, lay, ext_wrenches, ext_link, steps=None):
+        """The rdyn_ext_wrenches of a call: one record is (N, links, 6) / (links * 6, N) for every link (ext_link None), (N, 6) / (6, N)
+        for the link named ext_link.  steps None: one record; otherwise a leading dimension of at least `steps` records makes the
+        sequence per step, without it the wrenches are constant over the horizon."""
+        torch = _torch()
+        w = ext_wrenches
+        if w.dtype != torch.float64 or not w.is_cuda or not w.is_contiguous() or w.device != q.device:
+            raise ValueError("inputs must be contiguous float64 CUDA tensors")
+        L = self.getLinksNumber()
+        if ext_link is None:
+            rec, link = ((N, L, 6) if lay == LAYOUT_SAMPLE_MAJOR else (L * 6, N)), -1
+        else:
+            rec, link = ((N, 6) if lay == LAYOUT_SAMPLE_MAJOR else (6, N)), self._link_index(ext_link)
+        x = _lib.ExtWrenches()
+        x.w, x.link, x.step_stride = w.data_ptr(), link, 0
+        if tuple(w.shape) == rec:
+            return x
+        if steps is not None and w.dim() == len(rec) + 1 and tuple(w.shape[1:]) == rec and w.shape[0] >= steps:
+            x.step_stride = w[0].numel()
+            return x
+        raise ValueError("Input data dimensions mismatch")
+
+    def getJointAcceleration(self, q, Dq, tau, layout="sample", out=None, chunk_samples=0, workspace=None, components=None,
+                             ext_wrenches=None, ext_link=None):
         """Forward dynamics (include/rdyn.h: rdyn_forward_dynamics; no reference counterpart): DDq solves
         getJointInertia(q) DDq = tau - getJointTorqueNonLinearPart(q, Dq) per sample.  Returns (DDq, status): status (N,) int32, 1 solved,
         -1 the inertia matrix is not positive definite (that sample's DDq is NaN).  out may be tau itself.
         components: None, or a ComponentSet (friction, springs) whose torque at (q, Dq) is subtracted from tau first
-        (rdyn_forward_dynamics_components)."""
+        (rdyn_forward_dynamics_components).
+        ext_wrenches: None, or external wrenches [force; torque] applied TO the links, in each link's own frame, as getJointTorqueExt
+        takes them: (N, links, 6) for layout="sample", (links * 6, N) for "element"; with ext_link (a link name as in getJacobianLink)
+        the wrench of that one link, (N, 6) / (6, N).  Their joint torque is subtracted inside the evaluation (rdyn_forward_dynamics_ext)."""
         torch = _torch()
         b, N, lay = self._batch(layout, q, Dq, tau)
         b.ddq = None
         DDq = self._out(q, N, lay, (self.getActiveJointsNumber(),), out)
         status = torch.empty((N,), dtype=torch.int32, device=q.device)
-        nbytes = lib().rdyn_forward_dynamics_workspace_bytes(self._h, chunk_samples)
+        ext = self._ext_wrenches(q, N, lay, ext_wrenches, ext_link) if ext_wrenches is not None else None
+        if ext is not None:
+            nbytes = lib().rdyn_forward_dynamics_ext_workspace_bytes(self._h, C.byref(ext), chunk_samples)
+        else:
+            nbytes = lib().rdyn_forward_dynamics_workspace_bytes(self._h, chunk_samples)
         if workspace is None and nbytes > 0:
             workspace = torch.empty((nbytes,), dtype=torch.uint8, device=q.device)
         ws = (workspace.data_ptr() if workspace is not None else None, workspace.numel() if workspace is not None else 0)
-        if components is None:
+        if ext is not None:
+            comps, n_comps = self._component_list(components) if components is not None else (None, 0)
+            check(lib().rdyn_forward_dynamics_ext(self._h, C.byref(b), comps, n_comps, C.byref(ext), tau.data_ptr(), DDq.data_ptr(),
+                                                  status.data_ptr(), chunk_samples, *ws))
+        elif components is None:
             check(lib().rdyn_forward_dynamics(self._h, C.byref(b), tau.data_ptr(), DDq.data_ptr(), status.data_ptr(), chunk_samples, *ws))
         else:
             comps, n_comps = self._component_list(components)
@@ -385,7 +419,7 @@ class Chain(object):
         return DDq, status
 
     def rollout(self, q0, Dq0, tau, dt, integrator="rk4", n_steps=None, layout="sample", trajectory_every=0, out=None, chunk_samples=0,
-                workspace=None, components=None):
+                workspace=None, components=None, ext_wrenches=None, ext_link=None):
         """Rollout (include/rdyn.h: rdyn_rollout; no reference counterpart): n_steps integrator steps of size dt of the forward dynamics
         from (q0, Dq0), the torques held over each step.  integrator: "rk4" or "semi_implicit_euler" ("euler").
         tau: (T, N, n) for layout="sample", (T, n, N) for "element" -- n_steps defaults to T and may be smaller; or (N, n) / (n, N) with an
@@ -394,7 +428,10 @@ class Chain(object):
         state after step (r + 1) k, shaped (records,) + q0.shape.  status (N,) int32: 1, or -1 from the step on at which the inertia
         matrix was not positive definite (NaN state from then on).  out: None or (q_end, Dq_end) tensors; they may be q0 and Dq0.
         components: None, or a ComponentSet (friction, springs) whose torque is subtracted from tau at every integrator stage, at the
-        stage's own state (rdyn_rollout_components)."""
+        stage's own state (rdyn_rollout_components).
+        ext_wrenches, ext_link: None, or external link wrenches as in getJointAcceleration, evaluated at every integrator stage at the
+        stage's own q (rdyn_rollout_ext): one record -- (N, links, 6) / (links * 6, N), or (N, 6) / (6, N) with ext_link -- is constant
+        over the horizon; a leading dimension T makes the sequence per step, held over each step like the torques."""
         torch = _torch()
         b, N, lay = self._batch(layout, q0, Dq0)
         if integrator not in _lib.INTEGRATORS:
@@ -426,11 +463,18 @@ class Chain(object):
             dq_traj = torch.empty_like(q_traj)
             d.q_traj, d.dq_traj = q_traj.data_ptr(), dq_traj.data_ptr()
             d.traj_step_stride, d.traj_every = q0.numel(), int(trajectory_every)
-        nbytes = lib().rdyn_rollout_workspace_bytes(self._h, C.byref(d), N, chunk_samples)
+        ext = self._ext_wrenches(q0, N, lay, ext_wrenches, ext_link, steps=int(n_steps)) if ext_wrenches is not None else None
+        if ext is not None:
+            nbytes = lib().rdyn_rollout_ext_workspace_bytes(self._h, C.byref(d), C.byref(ext), N, chunk_samples)
+        else:
+            nbytes = lib().rdyn_rollout_workspace_bytes(self._h, C.byref(d), N, chunk_samples)
         if workspace is None and nbytes > 0:
             workspace = torch.empty((nbytes,), dtype=torch.uint8, device=q0.device)
         ws = (workspace.data_ptr() if workspace is not None else None, workspace.numel() if workspace is not None else 0)
-        if components is None:
+        if ext is not None:
+            comps, n_comps = self._component_list(components) if components is not None else (None, 0)
+            check(lib().rdyn_rollout_ext(self._h, C.byref(b), C.byref(d), comps, n_comps, C.byref(ext), chunk_samples, *ws))
+        elif components is None:
             check(lib().rdyn_rollout(self._h, C.byref(b), C.byref(d), chunk_samples, *ws))
         else:
             comps, n_comps = self._component_list(components)

@@ -1,5 +1,6 @@
 // rdyn_api_dynamics.cpp -- the forward-dynamics family of the C-ABI (include/rdyn.h): rdyn_forward_dynamics(_components),
-// rdyn_rollout(_components), rdyn_forward_dynamics_derivatives, rdyn_forward_dynamics_vjp, rdyn_rollout_adjoint, their parameter-gradient
+// rdyn_rollout(_components), their forms with external link wrenches rdyn_forward_dynamics_ext and rdyn_rollout_ext,
+// rdyn_forward_dynamics_derivatives, rdyn_forward_dynamics_vjp, rdyn_rollout_adjoint, their parameter-gradient
 // forms rdyn_forward_dynamics_parameter_vjp and rdyn_rollout_adjoint_parameters, and the workspace queries.
 // Every entry runs check_batch and its own pointer / descriptor checks, then dyn_prepare (the checks and the set-up all of them share),
 // then either one launch (chains the unrolled kernels sweep) or the chunked route through its workspace.  The workspace of every chunked
@@ -11,7 +12,9 @@
 // no workspace.  More than RDYN_MAX_SWEPT_JOINTS input joints: element-major chunk images [M | h] ((n n + n) doubles per sample)
 // written by k_long_inertia and the wrench recursion, factorised and solved in place by k_fwd_solve; the default chunk is the rule of
 // rdyn_regressor_gram_wide (an image within 128 MiB, at least 16 384 samples).
-static bool fwd_dyn_by_chunks(const rdyn_chain* c) { return c->long_chain() && !c->reduced; }
+// With external wrenches (ext) every long chain takes the chunked route on the ORIGINAL chain: the wrenches belong to its links, which
+// the reduced companion no longer has.
+static bool fwd_dyn_by_chunks(const rdyn_chain* c, bool ext = false) { return c->long_chain() && (ext || !c->reduced); }
 static int64_t fwd_dyn_chunk(const rdyn_chain* c, int64_t chunk_samples)
 {
   const int64_t n = c->n_active();
@@ -45,10 +48,10 @@ struct RolloutLayout { FwdLayout f; StateLayout s; };
 // adjoint: lq | lv | mu | qb | vb | tb and for RK4 xq | xv | kq | kv | gt | x2q | x2v | x3q | x3v | x4q | x4v | acc
 struct AdjointLayout { VjpLayout v; StateLayout s; };
 
-static FwdLayout fwd_layout(const rdyn_chain* c, int64_t chunk_samples)
+static FwdLayout fwd_layout(const rdyn_chain* c, int64_t chunk_samples, bool ext = false)
 {
   FwdLayout L = {};
-  if (!c || c->n_active() < 1 || chunk_samples < 0 || !fwd_dyn_by_chunks(c)) return L;
+  if (!c || c->n_active() < 1 || chunk_samples < 0 || !fwd_dyn_by_chunks(c, ext)) return L;
   const size_t n = (size_t)c->n_active();
   L.chunk = fwd_dyn_chunk(c, chunk_samples);
   L.total = align256((size_t)L.chunk * (n * n + n) * sizeof(double));
@@ -94,11 +97,11 @@ static StateLayout state_layout(size_t first, size_t count, const rdyn_chain* c,
   return s;
 }
 
-static RolloutLayout rollout_layout(const rdyn_chain* c, const rdyn_rollout_desc* d, int64_t n_samples, int64_t chunk_samples)
+static RolloutLayout rollout_layout(const rdyn_chain* c, const rdyn_rollout_desc* d, int64_t n_samples, int64_t chunk_samples, bool ext = false)
 {
   RolloutLayout L = {};
   if (!d || n_samples < 0) return L;
-  L.f = fwd_layout(c, chunk_samples);
+  L.f = fwd_layout(c, chunk_samples, ext);
   L.s = state_layout(L.f.total, d->integrator == RDYN_INTEGRATOR_RK4 ? 7 : 3, c, n_samples);
   return L;
 }
@@ -135,9 +138,9 @@ struct DynCall
 
 // The checks every entry makes after check_batch and its own pointer / descriptor checks, in this order, and the set-up behind them:
 // the sign of chunk_samples, the workspace against `need` (the total of the entry's layout), the component list; then no samples = done;
-// the device, the strides, the swept chain or the chunked route.  who = the entry point (error texts).
+// the device, the strides, the swept chain or the chunked route (ext: the call has external wrenches).  who = the entry point (error texts).
 static int dyn_prepare(const rdyn_chain* c, const rdyn_batch* b, const rdyn_component* comps, int n_comps, int64_t chunk_samples, size_t need,
-                       const void* workspace, size_t workspace_bytes, const char* who, DynCall* k)
+                       const void* workspace, size_t workspace_bytes, const char* who, DynCall* k, bool ext = false)
 {
   k->run = false;
   if (chunk_samples < 0) return refuse(who, "negative chunk_samples");
@@ -165,7 +168,7 @@ static int dyn_prepare(const rdyn_chain* c, const rdyn_batch* b, const rdyn_comp
   if (st != RDYN_OK) return st;
   k->stream = (hipStream_t)b->stream;
   rec_strides(b, k->n, &k->in_ss, &k->in_sj);
-  k->sw = fwd_dyn_by_chunks(c) ? nullptr : (c->long_chain() ? c->reduced.get() : c);
+  k->sw = fwd_dyn_by_chunks(c, ext) ? nullptr : (c->long_chain() ? c->reduced.get() : c);
   k->run = true;
   return k->sw ? device_const(k->sw, &k->chain) : RDYN_OK;
 }
@@ -187,6 +190,31 @@ static int check_integration(int n_steps, double dt, int integrator, const doubl
   return RDYN_OK;
 }
 
+// The external wrenches of a call: x.w null = none (ext null or ext->w null: the call IS the components call).  The link index, and for
+// rollouts the step stride against one step's record; the strides of a record in the batch's layout.
+static int check_ext(const rdyn_chain* c, const rdyn_batch* b, const rdyn_ext_wrenches* ext, bool steps, const char* who, RdynExtArgs* x)
+{
+  memset(x, 0, sizeof *x);
+  if (!ext || !ext->w) return RDYN_OK;
+  if (ext->link < -1 || ext->link > c->n_joints())
+  {
+    rdyn_set_error("%s: wrench link %d outside -1 .. %d (-1 = every link, %d = the tool)", who, (int)ext->link, c->n_joints(), c->n_joints());
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  const int64_t rec = ext->link < 0 ? 6 * (int64_t)(c->n_joints() + 1) : 6;
+  if (steps && (ext->step_stride < 0 || (ext->step_stride != 0 && ext->step_stride < rec * b->n_samples)))
+  {
+    rdyn_set_error("%s: wrench step_stride %lld is negative, or not zero and smaller than one step's record (%lld doubles)", who,
+                   (long long)ext->step_stride, (long long)(rec * b->n_samples));
+    return RDYN_ERR_INVALID_ARGUMENT;
+  }
+  x->w = ext->w;
+  rec_strides(b, rec, &x->ss, &x->se);
+  x->step = steps ? ext->step_stride : 0;
+  x->one = ext->link < 0 ? 0 : 1 + ext->link;
+  return RDYN_OK;
+}
+
 }  // namespace
 
 int long_deriv_lds_refusal(const rdyn_chain* c, const char* who)
@@ -199,10 +227,12 @@ int long_deriv_lds_refusal(const rdyn_chain* c, const char* who)
 
 // ---- forward dynamics: ddq = M^-1 (tau - h) (rdyn_fwd_dyn.hip) -------------------------------------------------
 // one pass of the chunked route over n_samples samples: per chunk the image [M | h] (k_long_inertia, the wrench recursion), then k_fwd_solve
-// (comps: null = the plain solve kernel; otherwise its variant, which subtracts tau_c at the sample's (q, dq) from tau)
+// (comps: null = the plain solve kernel; otherwise its variant, which subtracts tau_c at the sample's (q, dq) from tau; ext: null, or the
+// wrenches of the pass (ext->w at the first sample): the wrench recursion takes them and writes h + tau_E where it writes h, tau_E being
+// linear in ext and independent of dq -- no second launch, no buffer)
 static int fwd_dyn_chunks(const rdyn_chain* c, const double* q, const double* dq, const double* tau, double* ddq, int32_t* status,
                           int64_t n_samples, int64_t in_ss, int64_t in_sj, int64_t chunk, double* image, hipStream_t stream,
-                          const RdynComponentTable* comps)
+                          const RdynComponentTable* comps, const RdynExtArgs* ext = nullptr)
 {
   const int n = c->n_active();
   RdynLongLocalArgs ia;
@@ -232,6 +262,13 @@ static int fwd_dyn_chunks(const rdyn_chain* c, const double* q, const double* dq
     ha.tau = image + (int64_t)n * n * cnt;
     ha.tau_ss = 1;
     ha.tau_sj = cnt;
+    if (ext)
+    {
+      ha.ext = ext->w + s0 * ext->ss;
+      ha.ext_ss = ext->ss;
+      ha.ext_se = ext->se;
+      ha.ext_one = ext->one;
+    }
     RDYN_HIP_TRY(rdyn_launch_long_ext(c->n_joints(), ha, stream));
     RdynFwdSolveArgs sa;
     memset(&sa, 0, sizeof sa);
@@ -259,19 +296,25 @@ static int fwd_dyn_chunks(const rdyn_chain* c, const double* q, const double* dq
   return RDYN_OK;
 }
 
-// who = the entry point (error texts); comps with n_comps = 0 is the plain call: the same kernels
-static int forward_dynamics(const rdyn_chain* c, const rdyn_batch* b, const rdyn_component* comps, int n_comps, const double* tau, double* ddq,
-                            int32_t* status, int64_t chunk_samples, void* workspace, size_t workspace_bytes, const char* who)
+// who = the entry point (error texts); comps with n_comps = 0 is the plain call: the same kernels; ext null, or without w: no wrenches,
+// the same kernels again
+static int forward_dynamics(const rdyn_chain* c, const rdyn_batch* b, const rdyn_component* comps, int n_comps, const rdyn_ext_wrenches* ext,
+                            const double* tau, double* ddq, int32_t* status, int64_t chunk_samples, void* workspace, size_t workspace_bytes,
+                            const char* who)
 {
   int st = check_batch(c, b, true, false, who, LONG_KERNELS);
   if (st != RDYN_OK) return st;
   if (b->n_samples > 0 && (!tau || !ddq)) return refuse(who, "null torque or acceleration pointer");
-  const FwdLayout L = fwd_layout(c, chunk_samples);
+  RdynExtArgs x;
+  st = check_ext(c, b, ext, false, who, &x);
+  if (st != RDYN_OK) return st;
+  const FwdLayout L = fwd_layout(c, chunk_samples, x.w != nullptr);
   DynCall k;
-  st = dyn_prepare(c, b, comps, n_comps, chunk_samples, L.total, workspace, workspace_bytes, who, &k);
+  st = dyn_prepare(c, b, comps, n_comps, chunk_samples, L.total, workspace, workspace_bytes, who, &k, x.w != nullptr);
   if (st != RDYN_OK || !k.run) return st;
   if (!k.sw)
-    return fwd_dyn_chunks(c, b->q, b->dq, tau, ddq, status, b->n_samples, k.in_ss, k.in_sj, L.chunk, (double*)workspace, k.stream, k.comps);
+    return fwd_dyn_chunks(c, b->q, b->dq, tau, ddq, status, b->n_samples, k.in_ss, k.in_sj, L.chunk, (double*)workspace, k.stream, k.comps,
+                          x.w ? &x : nullptr);
   RdynFwdDynArgs a;
   memset(&a, 0, sizeof a);
   a.chain = k.chain;
@@ -284,6 +327,15 @@ static int forward_dynamics(const rdyn_chain* c, const rdyn_batch* b, const rdyn
   a.in_ss = k.in_ss;
   a.in_sj = k.in_sj;
   a.staged = stage_records(b, ddq) ? k.n : 0;
+  if (x.w)
+  {
+    RdynFwdDynExtArgs ae;
+    ae.c.f = a;
+    ae.c.t = k.table;
+    ae.x = x;
+    RDYN_HIP_TRY(rdyn_launch_forward_dynamics_ext(k.sw->n_joints(), ae, k.stream));
+    return RDYN_OK;
+  }
   if (n_comps == 0)
   {
     RDYN_HIP_TRY(rdyn_launch_forward_dynamics(k.sw->n_joints(), a, k.stream));
@@ -299,9 +351,9 @@ static int forward_dynamics(const rdyn_chain* c, const rdyn_batch* b, const rdyn
 // ---- rollouts: T integrator steps of the forward dynamics (rdyn_rollout.hip) ------------------------------------
 // Chains the unrolled kernels sweep: one launch for the whole horizon.  More input joints: per stage the chunked forward dynamics above,
 // then k_rollout_stage on the state arrays of RolloutLayout.
-// who = the entry point (error texts); comps with n_comps = 0 is the plain call: the same kernels
+// who = the entry point (error texts); comps with n_comps = 0 is the plain call: the same kernels; ext null, or without w: no wrenches
 static int rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_desc* d, const rdyn_component* comps, int n_comps,
-                   int64_t chunk_samples, void* workspace, size_t workspace_bytes, const char* who)
+                   const rdyn_ext_wrenches* ext, int64_t chunk_samples, void* workspace, size_t workspace_bytes, const char* who)
 {
   int st = check_batch(c, b, true, false, who, LONG_KERNELS);
   if (st != RDYN_OK) return st;
@@ -314,9 +366,12 @@ static int rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_
   if (N > 0 && !d->q_end && !d->dq_end && !traj) return refuse(who, "every output is null");
   if (traj && (d->traj_every < 1 || d->traj_step_stride < (int64_t)n * N))
     return refuse(who, "a trajectory needs traj_every >= 1 and traj_step_stride >= n * n_samples");
-  const RolloutLayout L = rollout_layout(c, d, N, chunk_samples);
+  RdynExtArgs x;
+  st = check_ext(c, b, ext, true, who, &x);
+  if (st != RDYN_OK) return st;
+  const RolloutLayout L = rollout_layout(c, d, N, chunk_samples, x.w != nullptr);
   DynCall k;
-  st = dyn_prepare(c, b, comps, n_comps, chunk_samples, L.s.total, workspace, workspace_bytes, who, &k);
+  st = dyn_prepare(c, b, comps, n_comps, chunk_samples, L.s.total, workspace, workspace_bytes, who, &k, x.w != nullptr);
   if (st != RDYN_OK || !k.run) return st;
   const int every = traj ? d->traj_every : 0;
   if (k.sw)
@@ -345,6 +400,15 @@ static int rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_
     // whole lines: every record of the kind starts on a line (the trajectory's step stride keeps the alignment of its first record)
     if ((d->q_end || d->dq_end) && stage_records(b, d->q_end, d->dq_end)) a.staged |= 1;
     if (traj && stage_records(b, d->q_traj, d->dq_traj) && (d->traj_step_stride * (int64_t)sizeof(double)) % 128 == 0) a.staged |= 2;
+    if (x.w)
+    {
+      RdynRolloutExtArgs ae;
+      ae.c.r = a;
+      ae.c.t = k.table;
+      ae.x = x;
+      RDYN_HIP_TRY(rdyn_launch_rollout_ext(k.sw->n_joints(), ae, k.stream));
+      return RDYN_OK;
+    }
     if (n_comps == 0)
     {
       RDYN_HIP_TRY(rdyn_launch_rollout(k.sw->n_joints(), a, k.stream));
@@ -392,12 +456,14 @@ static int rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_
   for (int t = 0; t < d->n_steps; ++t)
   {
     const double* const tau_t = d->tau + (int64_t)t * d->tau_step_stride;
+    RdynExtArgs xt = x;  // the step's wrenches, held over its stages
+    if (x.w) xt.w = x.w + (int64_t)t * x.step;
     const bool due = every > 0 && (t + 1) % every == 0;
     const int64_t rec = due ? ((t + 1) / every - 1) * d->traj_step_stride : 0;
     for (int stage = 0; stage < stages; ++stage)
     {
       st = fwd_dyn_chunks(c, stage ? sq : q, stage ? sv : dq, tau_t, ddq, st_stage, N, k.in_ss, k.in_sj, L.f.chunk, (double*)workspace, k.stream,
-                          k.comps);  // components see the stage state
+                          k.comps, x.w ? &xt : nullptr);  // components and wrenches see the stage state
       if (st != RDYN_OK) return st;
       const bool last = stage == stages - 1;
       sa.stage = stage;
@@ -543,13 +609,25 @@ size_t rdyn_forward_dynamics_workspace_bytes(const rdyn_chain* c, int64_t chunk_
 int rdyn_forward_dynamics(const rdyn_chain* c, const rdyn_batch* b, const double* tau, double* ddq, int32_t* status, int64_t chunk_samples,
                           void* workspace, size_t workspace_bytes)
 {
-  return forward_dynamics(c, b, nullptr, 0, tau, ddq, status, chunk_samples, workspace, workspace_bytes, "rdyn_forward_dynamics");
+  return forward_dynamics(c, b, nullptr, 0, nullptr, tau, ddq, status, chunk_samples, workspace, workspace_bytes, "rdyn_forward_dynamics");
 }
 
 int rdyn_forward_dynamics_components(const rdyn_chain* c, const rdyn_batch* b, const rdyn_component* comps, int n_comps, const double* tau,
                                      double* ddq, int32_t* status, int64_t chunk_samples, void* workspace, size_t workspace_bytes)
 {
-  return forward_dynamics(c, b, comps, n_comps, tau, ddq, status, chunk_samples, workspace, workspace_bytes, "rdyn_forward_dynamics_components");
+  return forward_dynamics(c, b, comps, n_comps, nullptr, tau, ddq, status, chunk_samples, workspace, workspace_bytes,
+                          "rdyn_forward_dynamics_components");
+}
+
+size_t rdyn_forward_dynamics_ext_workspace_bytes(const rdyn_chain* c, const rdyn_ext_wrenches* ext, int64_t chunk_samples)
+{
+  return fwd_layout(c, chunk_samples, ext && ext->w).total;
+}
+
+int rdyn_forward_dynamics_ext(const rdyn_chain* c, const rdyn_batch* b, const rdyn_component* comps, int n_comps, const rdyn_ext_wrenches* ext,
+                              const double* tau, double* ddq, int32_t* status, int64_t chunk_samples, void* workspace, size_t workspace_bytes)
+{
+  return forward_dynamics(c, b, comps, n_comps, ext, tau, ddq, status, chunk_samples, workspace, workspace_bytes, "rdyn_forward_dynamics_ext");
 }
 
 size_t rdyn_rollout_workspace_bytes(const rdyn_chain* c, const rdyn_rollout_desc* d, int64_t n_samples, int64_t chunk_samples)
@@ -560,13 +638,25 @@ size_t rdyn_rollout_workspace_bytes(const rdyn_chain* c, const rdyn_rollout_desc
 int rdyn_rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_desc* d, int64_t chunk_samples, void* workspace,
                  size_t workspace_bytes)
 {
-  return rollout(c, b, d, nullptr, 0, chunk_samples, workspace, workspace_bytes, "rdyn_rollout");
+  return rollout(c, b, d, nullptr, 0, nullptr, chunk_samples, workspace, workspace_bytes, "rdyn_rollout");
 }
 
 int rdyn_rollout_components(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_desc* d, const rdyn_component* comps, int n_comps,
                             int64_t chunk_samples, void* workspace, size_t workspace_bytes)
 {
-  return rollout(c, b, d, comps, n_comps, chunk_samples, workspace, workspace_bytes, "rdyn_rollout_components");
+  return rollout(c, b, d, comps, n_comps, nullptr, chunk_samples, workspace, workspace_bytes, "rdyn_rollout_components");
+}
+
+size_t rdyn_rollout_ext_workspace_bytes(const rdyn_chain* c, const rdyn_rollout_desc* d, const rdyn_ext_wrenches* ext, int64_t n_samples,
+                                        int64_t chunk_samples)
+{
+  return rollout_layout(c, d, n_samples, chunk_samples, ext && ext->w).s.total;
+}
+
+int rdyn_rollout_ext(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_desc* d, const rdyn_component* comps, int n_comps,
+                     const rdyn_ext_wrenches* ext, int64_t chunk_samples, void* workspace, size_t workspace_bytes)
+{
+  return rollout(c, b, d, comps, n_comps, ext, chunk_samples, workspace, workspace_bytes, "rdyn_rollout_ext");
 }
 
 size_t rdyn_forward_dynamics_derivatives_workspace_bytes(const rdyn_chain* c, int64_t chunk_samples)

@@ -38,7 +38,9 @@ template <int NJ>
 __global__ __launch_bounds__(64) void k_fwd_dyn(const RdynFwdDynArgs a)
 {
 #define RDYN_FWD_KERNEL_RHS(rhs)
+#define RDYN_FWD_LINK_WRENCH(f, R, t, fo, no)
 #include "rdyn_fwd_dyn_kernel.inc"
+#undef RDYN_FWD_LINK_WRENCH
 #undef RDYN_FWD_KERNEL_RHS
 }
 

@@ -27,7 +27,9 @@ __device__ __forceinline__ bool fwd_dyn_eval(ChainPtr c, const double (&q)[NJ], 
 {
 #define RDYN_FWD_Q(f, idx) q[f]
 #define RDYN_FWD_DQ(f, idx) dq[f]
+#define RDYN_FWD_LINK_WRENCH(f, R, t, fo, no)
 #include "rdyn_fwd_dyn_body.inc"
+#undef RDYN_FWD_LINK_WRENCH
 #undef RDYN_FWD_Q
 #undef RDYN_FWD_DQ
   return ok;

@@ -1,7 +1,9 @@
 // rdyn_fwd_dyn_body.inc -- the body of one forward-dynamics evaluation (rdyn_fwd_dyn_body.h), included as text where it runs so that
 // k_fwd_dyn compiles to exactly what it was before k_rollout shared it.  Expects: template parameter NJ; ChainPtr c; double rhs[NJ] (in: the
 // torque by chain joint, 0 where the joint is not an input joint; out: ddq); RDYN_FWD_Q(f, idx) / RDYN_FWD_DQ(f, idx) = q, dq of chain joint
-// f with input index idx >= 0.  Leaves bool ok (false: a pivot failed, rhs is not to be used).
+// f with input index idx >= 0; RDYN_FWD_LINK_WRENCH(f, R, t, fo, no): statements run once the net wrench (fo, no) of link f + 1 is formed,
+// R, t the transform of joint f -- nothing in every kernel but those with external wrenches (rdyn_ext_wrench.h), which subtract the link's
+// wrench here.  Leaves bool ok (false: a pivot failed, rhs is not to be used).
   // ---- forward: velocities, bias accelerations and the net wrench of every link in its own frame (DDq = 0)
   V3 w = mk(0, 0, 0), vl = mk(0, 0, 0), al = mk(0, 0, 0);
   V3 acc = mk(-c->g[0], -c->g[1], -c->g[2]);  // base "acceleration" -g
@@ -59,6 +61,7 @@
     const V3 d = acc + cross(w, vl);
     Fo[f] = axpy(cross(al, h) + cross(w, cross(w, h)), d, m);
     No[f] = symv(pi + 4, al) + cross(w, symv(pi + 4, w)) + cross(h, d);
+    RDYN_FWD_LINK_WRENCH(f, R, t, Fo[f], No[f])
   }
 
   // ---- backward: composite bodies, bias torques, the columns of M

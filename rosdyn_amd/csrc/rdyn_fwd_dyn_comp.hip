@@ -27,7 +27,9 @@ __global__ __launch_bounds__(64) void k_fwd_dyn_comp(const RdynFwdDynCompArgs ac
     const int idx = c->j[f].in_idx;                                                                      \
     if (idx >= 0) rhs[f] -= joint_component_torque(ac.t, idx, qp[idx * a.in_sj], dqp[idx * a.in_sj]);    \
   }
+#define RDYN_FWD_LINK_WRENCH(f, R, t, fo, no)
 #include "rdyn_fwd_dyn_kernel.inc"
+#undef RDYN_FWD_LINK_WRENCH
 #undef RDYN_FWD_KERNEL_RHS
 }
 

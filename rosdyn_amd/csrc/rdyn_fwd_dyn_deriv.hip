@@ -97,7 +97,9 @@ __global__ __launch_bounds__(64) void k_fwd_dyn_deriv(const RdynFwdDynDerivArgs 
 
 #define RDYN_FWD_Q(f, idx) qp[idx * a.in_sj]
 #define RDYN_FWD_DQ(f, idx) dqp[idx * a.in_sj]
+#define RDYN_FWD_LINK_WRENCH(f, R, t, fo, no)
 #include "rdyn_fwd_dyn_body.inc"
+#undef RDYN_FWD_LINK_WRENCH
 #undef RDYN_FWD_Q
 #undef RDYN_FWD_DQ
   // (in scope from here on: sv0, sv1 = sin q / 1 - cos q by chain joint, M = the factor, rhs = ddq, ok)

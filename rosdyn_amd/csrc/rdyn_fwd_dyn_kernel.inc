@@ -1,7 +1,7 @@
 // rdyn_fwd_dyn_kernel.inc -- the body of k_fwd_dyn (rdyn_fwd_dyn.hip), included as text by the kernel and by its variant with components
 // (rdyn_fwd_dyn_comp.hip), so that the plain kernel compiles to exactly what it was.  Expects: template parameter NJ; RdynFwdDynArgs a;
 // RDYN_FWD_KERNEL_RHS(rhs): statements run once the torques are in rhs[NJ] (by chain joint), with c, qp, dqp and a in scope -- nothing in
-// the plain kernel, rhs -= tau_c with components.
+// the plain kernel, rhs -= tau_c with components; RDYN_FWD_LINK_WRENCH: the hook of rdyn_fwd_dyn_body.inc, empty but with external wrenches.
   ChainPtr c = as_const(a.chain);
   const int lane = threadIdx.x;
   const int64_t s_wave = (int64_t)blockIdx.x * 64;

@@ -18,7 +18,9 @@
 
 #define RDYN_FWD_Q(f, idx) q_of(f, idx)
 #define RDYN_FWD_DQ(f, idx) dq_of(f, idx)
+#define RDYN_FWD_LINK_WRENCH(f, R, t, fo, no)
 #include "rdyn_fwd_dyn_body.inc"
+#undef RDYN_FWD_LINK_WRENCH
 #undef RDYN_FWD_Q
 #undef RDYN_FWD_DQ
   // (in scope from here on: sv0, sv1 = sin q / 1 - cos q by chain joint, M = the factor, rhs = ddq, ok)

@@ -72,6 +72,7 @@ struct RdynKinExtArgs
   int64_t tau_ss, tau_sj;
   int staged;  // sample-major records through wave-private LDS, whole lines (rdyn_record_stage.h); decided by the host: natural strides, line-aligned outputs
   int ext_staged;  // ... and the external wrenches read as whole lines into the same tile (16-byte aligned, natural stride)
+  int ext_one;     // rdyn_long_kin.hip only: 0 = ext holds links x 6 per sample; 1 + l = 6 per sample, applied to chain link l alone
 };
 hipError_t rdyn_launch_base_ext(int n_joints, const RdynKinExtArgs& a, hipStream_t st);
 hipError_t rdyn_launch_long_ext(int n_joints, const RdynKinExtArgs& a, hipStream_t st);  // a.chain_long; any chain length
@@ -573,6 +574,29 @@ struct RdynRolloutCompArgs
   RdynComponentTable t;
 };
 hipError_t rdyn_launch_rollout_components(int n_joints, const RdynRolloutCompArgs& a, hipStream_t st);
+
+// forward dynamics and rollouts with external link wrenches (rdyn_fwd_dyn_ext.hip, rdyn_rollout_ext.hip): the evaluation's torque is
+// tau - tau_c(q, dq) - tau_E(q, ext), tau_E the joint torque of the wrenches alone (rdyn_joint_torque_ext's convention).  The wrenches
+// enter the net wrench of their link inside the evaluation; the arguments travel behind those of the kernel with components.
+struct RdynExtArgs
+{
+  const double* w;  // element e of sample s of step t at w[t * step + s * ss + e * se]
+  int64_t ss, se;
+  int64_t step;     // rollouts: doubles between the wrenches of consecutive steps (0: the same at every step)
+  int one;          // 0: links x 6 per sample, every chain link; 1 + l: 6 per sample, applied to chain link l alone
+};
+struct RdynFwdDynExtArgs
+{
+  RdynFwdDynCompArgs c;
+  RdynExtArgs x;
+};
+hipError_t rdyn_launch_forward_dynamics_ext(int n_joints, const RdynFwdDynExtArgs& a, hipStream_t st);
+struct RdynRolloutExtArgs
+{
+  RdynRolloutCompArgs c;
+  RdynExtArgs x;
+};
+hipError_t rdyn_launch_rollout_ext(int n_joints, const RdynRolloutExtArgs& a, hipStream_t st);
 
 // reverse-mode product of the forward dynamics (rdyn_fwd_dyn_vjp.hip): with ddq = FD_c(q, dq, tau) and the seed ddq_bar per sample,
 // tau_bar = M^-1 ddq_bar, q_bar = dddq_dq' ddq_bar, dq_bar = dddq_dv' ddq_bar (the matrices of RdynFwdDynDerivArgs).  Every vector is

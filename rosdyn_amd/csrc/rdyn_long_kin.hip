@@ -322,9 +322,9 @@ __global__ __launch_bounds__(STAGED ? 64 : 256) void k_long_ext(const RdynKinExt
   const V3 grav = mk(c->g[0], c->g[1], c->g[2]);
   auto ext_of = [&](int link) -> S6 {  // -ext_wrenches_in_link_frame.at(link), :1255
     S6 e = zero;
-    if (a.ext)
+    if (a.ext && (a.ext_one == 0 || a.ext_one == link + 1))  // ext_one: the records hold the wrench of one link only (rdyn_forward_dynamics_ext)
     {
-      const double* __restrict__ ep = a.ext + s * a.ext_ss + (int64_t)(6 * link) * a.ext_se;
+      const double* __restrict__ ep = a.ext + s * a.ext_ss + (int64_t)(a.ext_one ? 0 : 6 * link) * a.ext_se;
       e.l = mk(-ep[0], -ep[a.ext_se], -ep[2 * a.ext_se]);
       e.a = mk(-ep[3 * a.ext_se], -ep[4 * a.ext_se], -ep[5 * a.ext_se]);
     }

@@ -34,7 +34,13 @@ template <int NJ, int INTEGRATOR>
 __global__ __launch_bounds__(64) void k_rollout(const RdynRolloutArgs a)
 {
 #define RDYN_ROLLOUT_RHS(q, dq, rhs)
+#define RDYN_ROLLOUT_TAKE
+#define RDYN_ROLLOUT_PREFETCH
+#define RDYN_ROLLOUT_EVAL(c, q, dq, rhs) fwd_dyn_eval<NJ>(c, q, dq, rhs)
 #include "rdyn_rollout_body.inc"
+#undef RDYN_ROLLOUT_EVAL
+#undef RDYN_ROLLOUT_PREFETCH
+#undef RDYN_ROLLOUT_TAKE
 #undef RDYN_ROLLOUT_RHS
 }
 

@@ -1,7 +1,10 @@
 // rdyn_rollout_body.inc -- the body of k_rollout (rdyn_rollout.hip), included as text by the kernel and by its variant with components
 // (rdyn_rollout_comp.hip), so that the plain kernel compiles to exactly what it was.  Expects: template parameters NJ, INTEGRATOR;
 // RdynRolloutArgs a; RDYN_ROLLOUT_RHS(q, dq, rhs): statements run immediately before each evaluation, the stage state in q[NJ], dq[NJ] and
-// the step's torques in rhs[NJ] (all by chain joint), with c in scope -- nothing in the plain kernel, rhs -= tau_c(q, dq) with components.
+// the step's torques in rhs[NJ] (all by chain joint), with c in scope -- nothing in the plain kernel, rhs -= tau_c(q, dq) with components;
+// RDYN_ROLLOUT_EVAL(c, q, dq, rhs): the evaluation, fwd_dyn_eval<NJ> but with external wrenches (rdyn_rollout_ext.hip), whose kernel also
+// fills RDYN_ROLLOUT_TAKE (statements run where rhs takes its copy of the step's torques, the step t in scope: the step's wrench is taken
+// the same way) and RDYN_ROLLOUT_PREFETCH (statements run where the torques of step t + 1 are requested); both empty everywhere else.
   const ChainPtr c = as_const(a.chain);
   const int lane = threadIdx.x;
   const int64_t s_wave = (int64_t)blockIdx.x * 64;
@@ -57,6 +60,7 @@
       double rhs[NJ];
 #pragma unroll
       for (int f = 0; f < NJ; ++f) rhs[f] = tau[f];
+      RDYN_ROLLOUT_TAKE
       if (more)
       {
 #pragma unroll
@@ -65,9 +69,10 @@
           const int idx = c->j[f].in_idx;
           if (idx >= 0) tau[f] = tp[idx * a.in_sj];
         }
+        RDYN_ROLLOUT_PREFETCH
       }
       RDYN_ROLLOUT_RHS(q, dq, rhs)
-      ok = fwd_dyn_eval<NJ>(per_evaluation(c), q, dq, rhs);
+      ok = RDYN_ROLLOUT_EVAL(per_evaluation(c), q, dq, rhs);
 #pragma unroll
       for (int f = 0; f < NJ; ++f)
       {
@@ -93,6 +98,7 @@
           kq[f] = fma(cdt, kv[f], dq[f]);  // the stage velocity = this stage's slope of q
           rhs[f] = tau[f];
         }
+        RDYN_ROLLOUT_TAKE
         if (stage == 3 && more)
         {
 #pragma unroll
@@ -101,9 +107,10 @@
             const int idx = c->j[f].in_idx;
             if (idx >= 0) tau[f] = tp[idx * a.in_sj];
           }
+          RDYN_ROLLOUT_PREFETCH
         }
         RDYN_ROLLOUT_RHS(sq, kq, rhs)
-        ok = fwd_dyn_eval<NJ>(per_evaluation(c), sq, kq, rhs) && ok;
+        ok = RDYN_ROLLOUT_EVAL(per_evaluation(c), sq, kq, rhs) && ok;
 #pragma unroll
         for (int f = 0; f < NJ; ++f)
         {

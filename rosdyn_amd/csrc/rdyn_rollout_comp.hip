@@ -30,7 +30,13 @@ __global__ __launch_bounds__(64) void k_rollout_comp(const RdynRolloutCompArgs a
     const int idx = c->j[f].in_idx;                                                    \
     if (idx >= 0) rhs[f] -= joint_component_torque(ac.t, idx, q[f], dq[f]);            \
   }
+#define RDYN_ROLLOUT_TAKE
+#define RDYN_ROLLOUT_PREFETCH
+#define RDYN_ROLLOUT_EVAL(c, q, dq, rhs) fwd_dyn_eval<NJ>(c, q, dq, rhs)
 #include "rdyn_rollout_body.inc"
+#undef RDYN_ROLLOUT_EVAL
+#undef RDYN_ROLLOUT_PREFETCH
+#undef RDYN_ROLLOUT_TAKE
 #undef RDYN_ROLLOUT_RHS
 }
 

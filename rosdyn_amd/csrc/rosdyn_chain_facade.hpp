@@ -601,21 +601,41 @@ public:
   {
     return jointAcceleration(q, Dq, tau, &comps);
   }
+  // ... with external wrenches applied TO the links, in link frames, as getJointTorque(q, Dq, DDq, ext_wrenches_in_link_frame) takes
+  // them (include/rdyn.h: rdyn_forward_dynamics_ext): their joint torque is subtracted from tau inside the evaluation
+  VectorXd getJointAcceleration(const VectorXd& q, const VectorXd& Dq, const VectorXd& tau, const VectorOfVector6d& ext_wrenches_in_link_frame)
+  {
+    if (ext_wrenches_in_link_frame.size() != m_links_number) throw std::invalid_argument("Input data dimensions mismatch");
+    return jointAcceleration(q, Dq, tau, nullptr, &ext_wrenches_in_link_frame);
+  }
 
 private:
-  // comps == nullptr: rdyn_forward_dynamics, as before the components were added; otherwise rdyn_forward_dynamics_components
-  VectorXd jointAcceleration(const VectorXd& q, const VectorXd& Dq, const VectorXd& tau, const std::vector<rdyn_component>* comps)
+  // comps == nullptr: rdyn_forward_dynamics, as before the components were added; otherwise rdyn_forward_dynamics_components;
+  // ext != nullptr: rdyn_forward_dynamics_ext
+  VectorXd jointAcceleration(const VectorXd& q, const VectorXd& Dq, const VectorXd& tau, const std::vector<rdyn_component>* comps,
+                             const VectorOfVector6d* ext = nullptr)
   {
     const size_t n = m_active_joints_number;
     stage(&q, &Dq, &tau);  // tau rides in the DDq slot of the staging buffer
-    // device record after the inputs: DDq (n) | status (int32 in one double) | the one-sample chunk image of the chunked route
-    const size_t ws_bytes = rdyn_forward_dynamics_workspace_bytes(m_h, 1);
-    if (n + 1 + (ws_bytes + 7) / 8 > m_host.size()) throw std::runtime_error("getJointAcceleration: staging buffer too small");
+    // device record after the inputs: DDq (n) | status (int32 in one double) | the wrenches (6 links, with ext) | the one-sample chunk
+    // image of the chunked route
+    const size_t n_ext = ext ? 6 * (size_t)m_links_number : 0;
+    rdyn_ext_wrenches x = {ext ? out(n + 1) : nullptr, -1, 0};
+    const size_t ws_bytes = ext ? rdyn_forward_dynamics_ext_workspace_bytes(m_h, &x, 1) : rdyn_forward_dynamics_workspace_bytes(m_h, 1);
+    if (n + 1 + n_ext + (ws_bytes + 7) / 8 > m_host.size()) throw std::runtime_error("getJointAcceleration: staging buffer too small");
     int32_t* const flag = reinterpret_cast<int32_t*>(out(n));
     const double* const d_tau = m_b.ddq;
     m_b.ddq = nullptr;
-    void* const ws = ws_bytes ? out(n + 1) : nullptr;
-    if (!comps) chk(rdyn_forward_dynamics(m_h, &m_b, d_tau, out(0), flag, 1, ws, ws_bytes));
+    void* const ws = ws_bytes ? out(n + 1 + n_ext) : nullptr;
+    if (ext)
+    {
+      double* const e = hout(n + 1);
+      for (unsigned l = 0; l < m_links_number; ++l)
+        for (int i = 0; i < 6; ++i) e[6 * l + i] = (*ext)[l](i);
+      chk(rdyn_forward_dynamics_ext(m_h, &m_b, comps ? comps->data() : nullptr, comps ? (int)comps->size() : 0, &x, d_tau, out(0), flag, 1, ws,
+                                    ws_bytes));
+    }
+    else if (!comps) chk(rdyn_forward_dynamics(m_h, &m_b, d_tau, out(0), flag, 1, ws, ws_bytes));
     else chk(rdyn_forward_dynamics_components(m_h, &m_b, comps->data(), (int)comps->size(), d_tau, out(0), flag, 1, ws, ws_bytes));
     wait_done();
     int32_t st;
@@ -888,6 +908,18 @@ public:
   {
     chk(rdyn_forward_dynamics_components(m_h, &b, comps.data(), (int)comps.size(), tau, ddq, status, chunk_samples, workspace, workspace_bytes));
   }
+  // ... with external link wrenches (rdyn_forward_dynamics_ext; ext.w a device pointer; comps may be empty; the workspace query takes ext:
+  // long chains with a reduced companion need a workspace only with wrenches)
+  size_t getJointAccelerationWorkspaceBytes(const rdyn_ext_wrenches& ext, int64_t chunk_samples = 0) const
+  {
+    return rdyn_forward_dynamics_ext_workspace_bytes(m_h, &ext, chunk_samples);
+  }
+  void getJointAccelerationBatch(const std::vector<rdyn_component>& comps, const rdyn_ext_wrenches& ext, const rdyn_batch& b, const double* tau,
+                                 double* ddq, int32_t* status, int64_t chunk_samples, void* workspace, size_t workspace_bytes) const
+  {
+    chk(rdyn_forward_dynamics_ext(m_h, &b, comps.empty() ? nullptr : comps.data(), (int)comps.size(), &ext, tau, ddq, status, chunk_samples,
+                                  workspace, workspace_bytes));
+  }
   // rollout of a batch (b.q, b.dq = the initial state; every pointer of desc a device pointer in the layout of b.q): rdyn_rollout
   size_t rolloutWorkspaceBytes(const rdyn_rollout_desc& desc, int64_t n_samples, int64_t chunk_samples = 0) const
   {
@@ -902,6 +934,18 @@ public:
                     void* workspace, size_t workspace_bytes) const
   {
     chk(rdyn_rollout_components(m_h, &b, &desc, comps.data(), (int)comps.size(), chunk_samples, workspace, workspace_bytes));
+  }
+  // ... with external link wrenches, evaluated at every integrator stage at the stage's own q (rdyn_rollout_ext; ext.w a device pointer,
+  // ext.step_stride = 0 holds the same wrenches over the horizon; comps may be empty)
+  size_t rolloutWorkspaceBytes(const rdyn_rollout_desc& desc, const rdyn_ext_wrenches& ext, int64_t n_samples, int64_t chunk_samples = 0) const
+  {
+    return rdyn_rollout_ext_workspace_bytes(m_h, &desc, &ext, n_samples, chunk_samples);
+  }
+  void rolloutBatch(const std::vector<rdyn_component>& comps, const rdyn_ext_wrenches& ext, const rdyn_batch& b, const rdyn_rollout_desc& desc,
+                    int64_t chunk_samples, void* workspace, size_t workspace_bytes) const
+  {
+    chk(rdyn_rollout_ext(m_h, &b, &desc, comps.empty() ? nullptr : comps.data(), (int)comps.size(), &ext, chunk_samples, workspace,
+                         workspace_bytes));
   }
   // adjoint of a rollout of a batch (b.q, b.dq = the forward call's initial state; every pointer of desc a device pointer in the layout of
   // b.q; comps may be empty): the gradients with respect to the initial state and the torques from the seeds on the end state and on the
