@@ -704,6 +704,56 @@ int rdyn_rollout_adjoint_parameters(const rdyn_chain* chain, const rdyn_batch* b
                                     const rdyn_component* comps, int n_comps, const rdyn_parameter_gradient* pg, int64_t chunk_samples,
                                     void* workspace, size_t workspace_bytes);
 
+/* Reverse mode through external link wrenches (no reference counterpart): the product of rdyn_forward_dynamics_ext and the adjoint of
+ * rdyn_rollout_ext.  Notation as at rdyn_forward_dynamics_ext: FD_E(q, Dq, tau, ext) = FD_c(q, Dq, tau - tau_E(q, ext)), tau_E linear in
+ * ext, a function of q and not of Dq; the base link's record never enters.
+ *   rdyn_forward_dynamics_vjp_ext   per sample, with w = M^-1 ddq_bar:
+ *       ddq     = FD_E(q, Dq, tau, ext), the bits of rdyn_forward_dynamics_ext          tau_bar = w
+ *       dq_bar  as in rdyn_forward_dynamics_vjp, at this ddq
+ *       q_bar   = -(dtau_dq + diag d tau_c / d q + d tau_E / d q)' w at this ddq
+ *       ext_bar = -(d tau_E / d ext)' w
+ *     ext_bar has exactly the shape and layout of ext->w: links_number x 6 per sample for link = -1, 6 per sample for link >= 0, in the
+ *     record layout of the batch; the base link's record is +0.0.  It must not overlap an input or another output.  ext->step_stride
+ *     is not read.  Every product is optional (all four NULL with samples: RDYN_ERR_INVALID_ARGUMENT); tau_bar may alias ddq_bar.
+ *     Status: the rule of rdyn_forward_dynamics_vjp, extended to the wrench entries the sample reads (a non-finite one gives -1; the base
+ *     link's record is not read).  A -1 sample gets quiet NaN in every requested output, ext_bar included.
+ *   rdyn_rollout_adjoint_ext        the exact transpose of the scheme rdyn_rollout_ext integrates: the step transposes written at
+ *     rdyn_rollout_adjoint with vjp replaced by the product above, evaluated with the wrench of step t (w + t * ext->step_stride), held
+ *     over the step and taken at each stage's own q; the RK4 stage states are rebuilt with FD_E.  gext (optional, and so is its gw): the
+ *     wrench gradient of step t goes to gw + t * step_stride in the shape of one step's wrench record -- with RK4 the sum of the four
+ *     stage products of the step.  step_stride = 0: one record, the sum over the steps (what a wrench held over the horizon needs; in a
+ *     single call only, like gtau_step_stride = 0).  With a stride >= one record the bitwise split-horizon property of
+ *     rdyn_rollout_adjoint holds, gw included.  A -1 sample's gw is NaN from the failing backward step on (step_stride = 0: the whole
+ *     record); nothing is added to another sample.  Every lane adds into its own record in a fixed order, no floating-point atomics:
+ *     gw is reproducible bit for bit.  gq0, gdq0, gtau and gw all NULL with samples is RDYN_ERR_INVALID_ARGUMENT.
+ * Routing, decided before any device work:
+ *   ext == NULL or ext->w == NULL   IS rdyn_forward_dynamics_vjp / rdyn_rollout_adjoint: the same kernels, the same bits, every chain
+ *                                   those serve; the queries equal the base queries.  A non-NULL ext_bar / gw is then
+ *                                   RDYN_ERR_INVALID_ARGUMENT.
+ *   with wrenches, at most RDYN_MAX_SWEPT_JOINTS chain joints: ONE launch for one product or one horizon; the queries return 0.
+ *   with wrenches, every chain for which rdyn_forward_dynamics_ext takes the chunked route (more than RDYN_MAX_SWEPT_JOINTS input joints,
+ *                                   and long chains that otherwise run on a reduced companion): RDYN_ERR_UNSUPPORTED.  Their reverse
+ *                                   mode with wrenches is the follow-up; without wrenches these calls serve them as the base calls do.
+ * Errors, all RDYN_ERR_INVALID_ARGUMENT before any device work: those of rdyn_forward_dynamics_vjp / rdyn_rollout_adjoint, those of
+ * rdyn_forward_dynamics_ext / rdyn_rollout_ext (the link range; in the adjoint the wrench step_stride rule), and a non-zero
+ * gext->step_stride that is negative or smaller than one step's record.  n_samples = 0 is RDYN_OK.  No allocation, no synchronisation:
+ * capturable into a graph once the chain has been used on the device. */
+size_t rdyn_forward_dynamics_vjp_ext_workspace_bytes(const rdyn_chain* chain, const rdyn_ext_wrenches* ext, int64_t chunk_samples);
+int rdyn_forward_dynamics_vjp_ext(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_component* comps, int n_comps,
+                                  const rdyn_ext_wrenches* ext, const double* tau, const double* ddq_bar, double* q_bar, double* dq_bar,
+                                  double* tau_bar, double* ext_bar, double* ddq, int32_t* status, int64_t chunk_samples, void* workspace,
+                                  size_t workspace_bytes);
+typedef struct rdyn_ext_wrench_gradient
+{
+  double* gw;           /* may be NULL; step t at gw + t * step_stride, one step's wrench record each */
+  int64_t step_stride;  /* in doubles; 0 = one record, the sum over the steps */
+} rdyn_ext_wrench_gradient;
+size_t rdyn_rollout_adjoint_ext_workspace_bytes(const rdyn_chain* chain, const rdyn_rollout_adjoint_desc* desc, const rdyn_ext_wrenches* ext,
+                                                int64_t n_samples, int64_t chunk_samples);
+int rdyn_rollout_adjoint_ext(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_rollout_adjoint_desc* desc,
+                             const rdyn_component* comps, int n_comps, const rdyn_ext_wrenches* ext, const rdyn_ext_wrench_gradient* gext,
+                             int64_t chunk_samples, void* workspace, size_t workspace_bytes);
+
 /* ---- mixed-chain batch (BASELINE.json configs[4]: 256 distinct 6-7-DOF chains x 4 096 samples) --------------
  * One launch per group of chains with equal joint count (and output-layout kind) evaluates rdyn_regressor for MANY
  * (chain, batch) items: grid = (ceil(max samples / workgroup), items); every workgroup reads its item's descriptor and its

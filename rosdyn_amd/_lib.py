@@ -51,6 +51,10 @@ class ExtWrenches(C.Structure):
     _fields_ = [("w", C.c_void_p), ("link", C.c_int32), ("step_stride", C.c_int64)]
 
 
+class ExtWrenchGradient(C.Structure):
+    _fields_ = [("gw", C.c_void_p), ("step_stride", C.c_int64)]
+
+
 class Component(C.Structure):
     _fields_ = [("type", C.c_int32), ("joint", C.c_int32), ("min_velocity", C.c_double), ("max_velocity", C.c_double),
                 ("parameters", C.c_double * 3)]
@@ -138,6 +142,13 @@ SYMBOLS = {
     "rdyn_rollout_adjoint_parameters_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(RolloutAdjointDesc), _VP, _I, C.c_int64, C.c_int64]),
     "rdyn_rollout_adjoint_parameters": (_I, [_VP, _BP, C.POINTER(RolloutAdjointDesc), _VP, _I, C.POINTER(ParameterGradient), C.c_int64, _VP,
                                              C.c_size_t]),
+    "rdyn_forward_dynamics_vjp_ext_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(ExtWrenches), C.c_int64]),
+    "rdyn_forward_dynamics_vjp_ext": (_I, [_VP, _BP, _VP, _I, C.POINTER(ExtWrenches), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP,
+                                           C.c_size_t]),
+    "rdyn_rollout_adjoint_ext_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(RolloutAdjointDesc), C.POINTER(ExtWrenches), C.c_int64,
+                                                              C.c_int64]),
+    "rdyn_rollout_adjoint_ext": (_I, [_VP, _BP, C.POINTER(RolloutAdjointDesc), _VP, _I, C.POINTER(ExtWrenches),
+                                      C.POINTER(ExtWrenchGradient), C.c_int64, _VP, C.c_size_t]),
     "rdyn_local_ik": (_I, [_VP, _BP, _VP, _DP, C.c_double, _I, _VP, _VP, _VP]),
     "rdyn_local_ik_damped": (_I, [_VP, _BP, _VP, _DP, C.c_double, C.c_double, _I, _VP, _VP, _VP]),
     "rdyn_frame_distance": (_I, [C.c_int64, _VP, _VP, _I, _I, _VP, _VP, _I, _VP]),

@@ -23,11 +23,18 @@ device-to-host copy and a new chain per call; a chain is a host object) -- small
 returns dL/dparameters and dL/dcomponent_parameters on those tensors' devices, from ``Chain.getJointAccelerationParameterVjp`` (the sums)
 and ``Chain.rolloutParameterAdjoint``: sums over the samples whose status is 1 -- a failed sample is NaN in its own state gradients and
 adds NOTHING to the parameter gradients.  Without these arguments the two classes above are used, unchanged.
+
+External link wrenches: both helpers take ``ext_wrenches`` (a tensor shaped as ``Chain.getJointAcceleration`` / ``Chain.rollout`` take
+it, differentiable) and ``ext_link``.  They run through ``JointAccelerationExtFunction`` / ``RolloutExtFunction``, whose backward is
+``Chain.getJointAccelerationVjp(ext_wrenches=)`` / ONE ``Chain.rolloutAdjoint(ext_wrenches=)`` call.  In ``rollout`` a wrench shaped like
+one step's record is held over the horizon and its gradient is the sum over the steps; a leading ``T`` axis means one record per step.
+Wrenches together with ``parameters`` / ``component_parameters`` raise ValueError: the parameter gradients with wrenches are the
+follow-up (include/rdyn.h).
 """
 import torch
 
 __all__ = ["joint_acceleration", "rollout", "JointAccelerationFunction", "RolloutFunction", "JointAccelerationParametersFunction",
-           "RolloutParametersFunction"]
+           "RolloutParametersFunction", "JointAccelerationExtFunction", "RolloutExtFunction"]
 
 
 class JointAccelerationFunction(torch.autograd.Function):
@@ -159,28 +166,102 @@ class RolloutParametersFunction(torch.autograd.Function):
                 + _parameter_grads(ctx, gpi, gcomp, 10))
 
 
-def joint_acceleration(chain, q, Dq, tau, components=None, layout="sample", parameters=None, component_parameters=None):
+class JointAccelerationExtFunction(torch.autograd.Function):
+    """JointAccelerationFunction with external link wrenches among the inputs"""
+
+    @staticmethod
+    def forward(ctx, chain, components, layout, ext_link, q, Dq, tau, ext_wrenches):
+        q, Dq, tau, w = (t.detach().contiguous() for t in (q, Dq, tau, ext_wrenches))
+        ddq, _ = chain.getJointAcceleration(q, Dq, tau, layout=layout, components=components, ext_wrenches=w, ext_link=ext_link)
+        ctx.chain, ctx.components, ctx.layout, ctx.ext_link = chain, components, layout, ext_link
+        ctx.save_for_backward(q, Dq, tau, w)
+        return ddq
+
+    @staticmethod
+    def backward(ctx, g):
+        q, Dq, tau, w = ctx.saved_tensors
+        names = tuple(k for k, need in zip(("q", "dq", "tau", "ext"), ctx.needs_input_grad[4:8]) if need)
+        if not names:
+            return (None,) * 8
+        res = ctx.chain.getJointAccelerationVjp(q, Dq, tau, g.contiguous(), layout=ctx.layout, want=names, components=ctx.components,
+                                                ext_wrenches=w, ext_link=ctx.ext_link)
+        grads = dict(zip(names, res[1:]))
+        return None, None, None, None, grads.get("q"), grads.get("dq"), grads.get("tau"), grads.get("ext")
+
+
+class RolloutExtFunction(torch.autograd.Function):
+    """RolloutFunction with external link wrenches among the inputs; the backward is ONE Chain.rolloutAdjoint(ext_wrenches=) call"""
+
+    @staticmethod
+    def forward(ctx, chain, components, layout, integrator, dt, n_steps, trajectory, ext_link, q0, Dq0, tau, ext_wrenches):
+        q0, Dq0, tau, w = (t.detach().contiguous() for t in (q0, Dq0, tau, ext_wrenches))
+        q_end, dq_end, _, q_traj, dq_traj = chain.rollout(q0, Dq0, tau, dt, integrator=integrator, n_steps=n_steps, layout=layout,
+                                                          trajectory_every=1, components=components, ext_wrenches=w, ext_link=ext_link)
+        ctx.chain, ctx.components, ctx.layout, ctx.integrator, ctx.dt, ctx.ext_link = chain, components, layout, integrator, dt, ext_link
+        ctx.n_steps, ctx.trajectory, ctx.sum_tau = q_traj.shape[0], trajectory, tau.dim() == 2
+        ctx.sum_ext = w.dim() == (2 if ext_link is not None else (3 if layout == "sample" else 2))  # one record: held over the horizon
+        ctx.save_for_backward(q0, Dq0, tau, q_traj, dq_traj, w)
+        if trajectory:
+            return q_end, dq_end, q_traj.clone(), dq_traj.clone()  # (the saved records must not be written to by the caller)
+        return q_end, dq_end
+
+    @staticmethod
+    def backward(ctx, gq_end, gdq_end, gq_traj=None, gdq_traj=None):
+        q0, Dq0, tau, q_traj, dq_traj, w = ctx.saved_tensors
+        c = lambda t: t.contiguous() if t is not None else None
+        res = ctx.chain.rolloutAdjoint(q0, Dq0, tau, ctx.dt, q_traj, dq_traj, gq_end=c(gq_end), gDq_end=c(gdq_end), gq_traj=c(gq_traj),
+                                       gDq_traj=c(gdq_traj), integrator=ctx.integrator, n_steps=ctx.n_steps, layout=ctx.layout,
+                                       components=ctx.components, sum_tau=ctx.sum_tau, ext_wrenches=w, ext_link=ctx.ext_link,
+                                       want_ext=bool(ctx.needs_input_grad[11]), sum_ext=ctx.sum_ext)
+        gq0, gdq0, gtau = res[:3]
+        gext = None
+        if ctx.needs_input_grad[11]:
+            gext = res[4]
+            if not ctx.sum_ext and gext.shape[0] < w.shape[0]:  # a sequence longer than the horizon: the unused records get 0
+                gext = torch.cat([gext, gext.new_zeros((w.shape[0] - gext.shape[0],) + tuple(gext.shape[1:]))])
+        need = ctx.needs_input_grad[8:11]
+        return (None,) * 8 + (gq0 if need[0] else None, gdq0 if need[1] else None, gtau if need[2] else None, gext)
+
+
+def _no_parameters_with_wrenches(parameters, component_parameters):
+    if parameters is not None or component_parameters is not None:
+        raise ValueError("ext_wrenches together with parameters / component_parameters is not served yet: the parameter gradients with "
+                         "external wrenches are the follow-up")
+
+
+def joint_acceleration(chain, q, Dq, tau, components=None, layout="sample", parameters=None, component_parameters=None, ext_wrenches=None,
+                       ext_link=None):
     """Differentiable ``Chain.getJointAcceleration``: DDq = FD_c(q, Dq, tau), shaped like q.  Gradients flow to q, Dq and tau through
     ``Chain.getJointAccelerationVjp``.  A sample with status -1 is NaN in DDq and in its gradients; nothing is raised.
-    parameters / component_parameters (the module docstring): the model to evaluate, differentiable as well."""
+    parameters / component_parameters (the module docstring): the model to evaluate, differentiable as well.
+    ext_wrenches, ext_link (the module docstring): external link wrenches as ``Chain.getJointAcceleration`` takes them, differentiable."""
+    if ext_wrenches is not None:
+        _no_parameters_with_wrenches(parameters, component_parameters)
+        return JointAccelerationExtFunction.apply(chain, components, layout, ext_link, q, Dq, tau, ext_wrenches)
     if parameters is None and component_parameters is None:
         return JointAccelerationFunction.apply(chain, components, layout, q, Dq, tau)
     return JointAccelerationParametersFunction.apply(chain, components, layout, q, Dq, tau, parameters, component_parameters)
 
 
 def rollout(chain, q0, Dq0, tau, dt, integrator="rk4", n_steps=None, trajectory=False, components=None, layout="sample", parameters=None,
-            component_parameters=None):
+            component_parameters=None, ext_wrenches=None, ext_link=None):
     """Differentiable ``Chain.rollout``: returns (q_end, Dq_end), and with trajectory=True also (q_traj, Dq_traj) with one record per
     step (record k = the state after step k + 1).  tau: (T, N, n) / (T, n, N), one torque per step, or shaped like q0 with an explicit
     n_steps (held over the horizon: its gradient is the sum over the steps).  Gradients flow to q0, Dq0 and tau from the end state and
     from every trajectory record; the backward is one ``Chain.rolloutAdjoint`` call over the records the forward saved.
     A sample whose rollout reports status -1 has NaN states from the failing step on and NaN gradients; nothing is raised.
     parameters / component_parameters (the module docstring): the model to simulate, differentiable as well -- the backward is then one
-    ``Chain.rolloutParameterAdjoint`` call (chains with at most 10 input joints)."""
+    ``Chain.rolloutParameterAdjoint`` call (chains with at most 10 input joints).
+    ext_wrenches, ext_link (the module docstring): external link wrenches as ``Chain.rollout`` takes them, differentiable: one step's
+    record is held over the horizon (its gradient is the sum over the steps), a leading T axis is one record per step."""
     if n_steps is None:
         if tau.dim() != 3:
             raise ValueError("torques shaped like q0 need an explicit n_steps")
         n_steps = tau.shape[0]
+    if ext_wrenches is not None:
+        _no_parameters_with_wrenches(parameters, component_parameters)
+        return RolloutExtFunction.apply(chain, components, layout, integrator, float(dt), int(n_steps), bool(trajectory), ext_link, q0, Dq0,
+                                        tau, ext_wrenches)
     if parameters is None and component_parameters is None:
         return RolloutFunction.apply(chain, components, layout, integrator, float(dt), int(n_steps), bool(trajectory), q0, Dq0, tau)
     return RolloutParametersFunction.apply(chain, components, layout, integrator, float(dt), int(n_steps), bool(trajectory), q0, Dq0, tau,

@@ -383,6 +383,17 @@ class Chain(object):
             return x
         raise ValueError("Input data dimensions mismatch")
 
+    def _like_wrenches(self, shape_of, out, key):
+        """an output shaped like the wrench tensor shape_of (or its shape): out when given and matching, otherwise new"""
+        torch = _torch()
+        shape = tuple(shape_of) if isinstance(shape_of, (tuple, list)) else tuple(shape_of.shape)
+        if out is None:
+            dev = shape_of.device if hasattr(shape_of, "device") else None
+            return torch.empty(shape, dtype=torch.float64, device=dev)
+        if tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous():
+            raise ValueError("out[%r] must be a contiguous float64 CUDA tensor of shape %s" % (key, shape))
+        return out
+
     def getJointAcceleration(self, q, Dq, tau, layout="sample", out=None, chunk_samples=0, workspace=None, components=None,
                              ext_wrenches=None, ext_link=None):
         """Forward dynamics (include/rdyn.h: rdyn_forward_dynamics; no reference counterpart): DDq solves
@@ -530,19 +541,25 @@ class Chain(object):
         return (DDq, status) + tuple(res[k] for k in names)
 
     def getJointAccelerationVjp(self, q, Dq, tau, DDq_bar, layout="sample", want=("q", "dq", "tau"), components=None, out=None,
-                                chunk_samples=0, workspace=None):
+                                chunk_samples=0, workspace=None, ext_wrenches=None, ext_link=None):
         """Reverse-mode product of getJointAcceleration (include/rdyn.h: rdyn_forward_dynamics_vjp; no reference counterpart): for the seed
         DDq_bar on DDq, "q" -> (d DDq / d q)' DDq_bar, "dq" -> (d DDq / d Dq)' DDq_bar, "tau" -> M^-1 DDq_bar, the matrices those of
         getJointAccelerationDerivatives (components and their slopes included) -- never formed.  want: a selection with at least one of the
         three; "ddq" may be added and names DDq itself (getJointAcceleration's bits).  Returns (status, *wanted) in the order of `want` (a
         single name may be given as a string); every vector is shaped like q.  status (N,) int32: 1, or -1 (the inertia matrix is not
         positive definite, or q, Dq, tau or DDq_bar of the sample is not finite): that sample is NaN in every output.
-        out: None, or a dict name -> preallocated tensor; out["tau"] may be DDq_bar itself."""
+        out: None, or a dict name -> preallocated tensor; out["tau"] may be DDq_bar itself.
+        ext_wrenches, ext_link: None, or external link wrenches as in getJointAcceleration (rdyn_forward_dynamics_vjp_ext): the product
+        is that of getJointAcceleration(ext_wrenches=), "q" gains the dependence of the wrench torque on q, and want may name "ext":
+        the gradient with respect to the wrenches, shaped like ext_wrenches (the base link's record 0); a non-finite wrench entry the
+        sample reads gives status -1."""
         single = isinstance(want, str)
         names = (want,) if single else tuple(want)
-        if (not names or len(set(names)) != len(names) or any(k not in ("q", "dq", "tau", "ddq") for k in names)
+        allowed = ("q", "dq", "tau", "ddq") + (("ext",) if ext_wrenches is not None else ())
+        if (not names or len(set(names)) != len(names) or any(k not in allowed for k in names)
                 or not any(k != "ddq" for k in names)):
-            raise ValueError('want must be a selection of "q", "dq", "tau" (at least one) and "ddq"')
+            raise ValueError('want must be a selection of "q", "dq", "tau" (at least one) and "ddq"'
+                             if ext_wrenches is None else 'want must be a selection of "q", "dq", "tau", "ext" (at least one) and "ddq"')
         torch = _torch()
         b, N, lay = self._batch(layout, q, Dq, tau)
         b.ddq = None
@@ -550,9 +567,18 @@ class Chain(object):
                 or DDq_bar.device != q.device):
             raise ValueError("Input data dimensions mismatch")
         n = self.getActiveJointsNumber()
-        res = {k: self._out(q, N, lay, (n,), (out or {}).get(k)) for k in names}
+        res = {k: self._out(q, N, lay, (n,), (out or {}).get(k)) for k in names if k != "ext"}
         ptr = [res[k].data_ptr() if k in res else None for k in ("q", "dq", "tau", "ddq")]
         status = torch.empty((N,), dtype=torch.int32, device=q.device)
+        if ext_wrenches is not None:
+            ext = self._ext_wrenches(q, N, lay, ext_wrenches, ext_link)
+            if "ext" in names:
+                res["ext"] = self._like_wrenches(ext_wrenches, (out or {}).get("ext"), "ext")
+            comps, n_comps = self._component_list(components) if components is not None else (None, 0)
+            check(lib().rdyn_forward_dynamics_vjp_ext(self._h, C.byref(b), comps, n_comps, C.byref(ext), tau.data_ptr(), DDq_bar.data_ptr(),
+                                                      ptr[0], ptr[1], ptr[2], res["ext"].data_ptr() if "ext" in res else None, ptr[3],
+                                                      status.data_ptr(), chunk_samples, None, 0))
+            return (status,) + tuple(res[k] for k in names)
         nbytes = lib().rdyn_forward_dynamics_vjp_workspace_bytes(self._h, chunk_samples)
         if workspace is None and nbytes > 0:
             workspace = torch.empty((nbytes,), dtype=torch.uint8, device=q.device)
@@ -623,7 +649,8 @@ class Chain(object):
         return Chain(None, None, None, _handle=h)
 
     def rolloutAdjoint(self, q0, Dq0, tau, dt, q_traj, Dq_traj, gq_end=None, gDq_end=None, gq_traj=None, gDq_traj=None, integrator="rk4",
-                       n_steps=None, layout="sample", components=None, sum_tau=False, out=None, chunk_samples=0, workspace=None):
+                       n_steps=None, layout="sample", components=None, sum_tau=False, out=None, chunk_samples=0, workspace=None,
+                       ext_wrenches=None, ext_link=None, want_ext=False, sum_ext=False):
         """Adjoint of rollout (include/rdyn.h: rdyn_rollout_adjoint; no reference counterpart): the exact transpose of the n_steps
         integrator steps rollout takes, from the seeds on the end state (gq_end, gDq_end, shaped like q0; None = 0) and, optionally, on
         every trajectory record (gq_traj, gDq_traj: (>= n_steps,) + q0.shape, record k seeds the state after step k + 1) back to the
@@ -633,9 +660,18 @@ class Chain(object):
         Returns (gq0, gDq0, gtau, status).  gtau: (n_steps,) + q0.shape, one gradient per step, or shaped like q0 with sum_tau=True (the
         sum over the steps: the gradient of torques held over the whole horizon).  status (N,) int32: 1, or -1 when an evaluation of the
         sample failed or met a non-finite value -- a sample whose forward rollout reported -1 in particular: NaN in every gradient.
-        out: None, or a dict with any of "gq0", "gDq0", "gtau" -> preallocated tensor; out["gq0"] / out["gDq0"] may be gq_end / gDq_end."""
+        out: None, or a dict with any of "gq0", "gDq0", "gtau" -> preallocated tensor; out["gq0"] / out["gDq0"] may be gq_end / gDq_end.
+        ext_wrenches, ext_link: the forward call's external link wrenches, with rollout's shape rules (rdyn_rollout_adjoint_ext): the
+        transpose is that of rollout(ext_wrenches=).  want_ext=True appends gext to the returned tuple, the gradient with respect to the
+        wrenches: (n_steps,) + one record's shape, one gradient per step, or one record with sum_ext=True (the sum over the steps: the
+        gradient of a wrench held over the horizon); out may hold "gext"."""
+        if ext_wrenches is None:
+            if want_ext or sum_ext or ext_link is not None:
+                raise ValueError("want_ext, sum_ext and ext_link need ext_wrenches")
+            return self._rollout_adjoint(q0, Dq0, tau, dt, q_traj, Dq_traj, gq_end, gDq_end, gq_traj, gDq_traj, integrator, n_steps, layout,
+                                         components, sum_tau, out, chunk_samples, workspace, None)
         return self._rollout_adjoint(q0, Dq0, tau, dt, q_traj, Dq_traj, gq_end, gDq_end, gq_traj, gDq_traj, integrator, n_steps, layout, components,
-                                     sum_tau, out, chunk_samples, workspace, None)
+                                     sum_tau, out, chunk_samples, workspace, None, (ext_wrenches, ext_link, bool(want_ext), bool(sum_ext)))
 
     def rolloutParameterAdjoint(self, q0, Dq0, tau, dt, q_traj, Dq_traj, gq_end=None, gDq_end=None, gq_traj=None, gDq_traj=None,
                                 integrator="rk4", n_steps=None, layout="sample", components=None, sum_tau=False, out=None, chunk_samples=0,
@@ -651,8 +687,9 @@ class Chain(object):
                                      sum_tau, out, chunk_samples, workspace, bool(accumulate))
 
     def _rollout_adjoint(self, q0, Dq0, tau, dt, q_traj, Dq_traj, gq_end, gDq_end, gq_traj, gDq_traj, integrator, n_steps, layout, components,
-                         sum_tau, out, chunk_samples, workspace, accumulate):
-        """the two calls above; accumulate None: without the parameter gradients"""
+                         sum_tau, out, chunk_samples, workspace, accumulate, wrenches=None):
+        """the two calls above; accumulate None: without the parameter gradients; wrenches: None, or rolloutAdjoint's (ext_wrenches,
+        ext_link, want_ext, sum_ext)"""
         torch = _torch()
         b, N, lay = self._batch(layout, q0, Dq0)
         if integrator not in _lib.INTEGRATORS:
@@ -703,6 +740,20 @@ class Chain(object):
         d.gtau, d.gtau_step_stride = ptr(gtau), 0 if sum_tau else q0.numel()
         d.status = status.data_ptr()
         comps, n_comps = self._component_list(components) if components is not None else (None, 0)
+        if wrenches is not None:
+            ext_wrenches, ext_link, want_ext, sum_ext = wrenches
+            ext = self._ext_wrenches(q0, N, lay, ext_wrenches, ext_link, steps=T)
+            g = _lib.ExtWrenchGradient()
+            gext = None
+            if want_ext:
+                rec = tuple(ext_wrenches.shape[1:]) if ext.step_stride else tuple(ext_wrenches.shape)
+                shape = rec if sum_ext else (max(T, 0),) + rec
+                gext = self._like_wrenches(shape, out.get("gext"), "gext") if out.get("gext") is not None else torch.empty(
+                    shape, dtype=torch.float64, device=q0.device)
+                g.gw, g.step_stride = ptr(gext), 0 if sum_ext else int(torch.Size(rec).numel())
+            check(lib().rdyn_rollout_adjoint_ext(self._h, C.byref(b), C.byref(d), comps, n_comps, C.byref(ext), C.byref(g), chunk_samples,
+                                                 None, 0))
+            return (gq0, gdq0, gtau, status) + ((gext,) if want_ext else ())
         if accumulate is None:
             nbytes = lib().rdyn_rollout_adjoint_workspace_bytes(self._h, C.byref(d), N, chunk_samples)
         else:

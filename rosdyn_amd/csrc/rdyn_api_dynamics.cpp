@@ -1,7 +1,8 @@
 // rdyn_api_dynamics.cpp -- the forward-dynamics family of the C-ABI (include/rdyn.h): rdyn_forward_dynamics(_components),
 // rdyn_rollout(_components), their forms with external link wrenches rdyn_forward_dynamics_ext and rdyn_rollout_ext,
 // rdyn_forward_dynamics_derivatives, rdyn_forward_dynamics_vjp, rdyn_rollout_adjoint, their parameter-gradient
-// forms rdyn_forward_dynamics_parameter_vjp and rdyn_rollout_adjoint_parameters, and the workspace queries.
+// forms rdyn_forward_dynamics_parameter_vjp and rdyn_rollout_adjoint_parameters, their forms with external link wrenches
+// rdyn_forward_dynamics_vjp_ext and rdyn_rollout_adjoint_ext, and the workspace queries.
 // Every entry runs check_batch and its own pointer / descriptor checks, then dyn_prepare (the checks and the set-up all of them share),
 // then either one launch (chains the unrolled kernels sweep) or the chunked route through its workspace.  The workspace of every chunked
 // route is described ONCE, by a *Layout struct: the query returns its total, the call carves its pointers from its offsets.
@@ -213,6 +214,18 @@ static int check_ext(const rdyn_chain* c, const rdyn_batch* b, const rdyn_ext_wr
   x->step = steps ? ext->step_stride : 0;
   x->one = ext->link < 0 ? 0 : 1 + ext->link;
   return RDYN_OK;
+}
+
+// reverse mode with wrenches serves the chains swept in registers on their own links; every chain whose rdyn_forward_dynamics_ext takes
+// the chunked route is refused
+static int ext_reverse_refusal(const rdyn_chain* c, const char* who)
+{
+  if (!fwd_dyn_by_chunks(c, true)) return RDYN_OK;
+  rdyn_set_error("%s: with external wrenches, chains that rdyn_forward_dynamics_ext serves by its chunked route (more than %d input joints, "
+                 "or more than %d chain joints on a reduced companion; this chain has %d input joints, %d chain joints) are not served yet; "
+                 "without wrenches the call serves them",
+                 who, RDYN_MAX_SWEPT_JOINTS, RDYN_MAX_SWEPT_JOINTS, c->n_active(), c->n_joints());
+  return RDYN_ERR_UNSUPPORTED;
 }
 
 }  // namespace
@@ -749,6 +762,59 @@ int rdyn_forward_dynamics_vjp(const rdyn_chain* c, const rdyn_batch* b, const rd
                     k.stream);
 }
 
+// ---- reverse-mode product with external link wrenches (rdyn_fwd_dyn_vjp_ext.hip) -------------------------------------
+// Without wrenches the call IS rdyn_forward_dynamics_vjp.  With them: chains swept in registers, one launch, no workspace.
+size_t rdyn_forward_dynamics_vjp_ext_workspace_bytes(const rdyn_chain* c, const rdyn_ext_wrenches* ext, int64_t chunk_samples)
+{
+  return (ext && ext->w) ? 0 : vjp_layout(c, chunk_samples).total;
+}
+
+int rdyn_forward_dynamics_vjp_ext(const rdyn_chain* c, const rdyn_batch* b, const rdyn_component* comps, int n_comps, const rdyn_ext_wrenches* ext,
+                                  const double* tau, const double* ddq_bar, double* q_bar, double* dq_bar, double* tau_bar, double* ext_bar,
+                                  double* ddq, int32_t* status, int64_t chunk_samples, void* workspace, size_t workspace_bytes)
+{
+  const char* const who = "rdyn_forward_dynamics_vjp_ext";
+  if (!ext || !ext->w)
+  {
+    if (ext_bar) return refuse(who, "ext_bar without external wrenches");
+    return rdyn_forward_dynamics_vjp(c, b, comps, n_comps, tau, ddq_bar, q_bar, dq_bar, tau_bar, ddq, status, chunk_samples, workspace,
+                                     workspace_bytes);
+  }
+  int st = check_batch(c, b, true, false, who, LONG_KERNELS);
+  if (st != RDYN_OK) return st;
+  if (b->n_samples > 0 && (!tau || !ddq_bar)) return refuse(who, "null torque or seed pointer");
+  if (b->n_samples > 0 && !q_bar && !dq_bar && !tau_bar && !ext_bar) return refuse(who, "every product is null");
+  RdynExtArgs x;
+  st = check_ext(c, b, ext, false, who, &x);
+  if (st != RDYN_OK) return st;
+  if ((st = ext_reverse_refusal(c, who)) != RDYN_OK) return st;
+  DynCall k;
+  st = dyn_prepare(c, b, comps, n_comps, chunk_samples, 0, workspace, workspace_bytes, who, &k);
+  if (st != RDYN_OK || !k.run) return st;
+  RdynFwdDynVjpExtArgs ax;
+  memset(&ax, 0, sizeof ax);
+  RdynFwdDynVjpArgs& a = ax.v;
+  a.chain = k.chain;
+  a.q = b->q;
+  a.dq = b->dq;
+  a.tau = tau;
+  a.ddq_bar = ddq_bar;
+  a.q_bar = q_bar;
+  a.dq_bar = dq_bar;
+  a.tau_bar = tau_bar;
+  a.ddq = ddq;
+  a.status = status;
+  a.n_samples = b->n_samples;
+  a.in_ss = k.in_ss;
+  a.in_sj = k.in_sj;
+  a.staged = stage_records(b, q_bar, dq_bar, tau_bar, ddq) ? k.n : 0;
+  a.t = k.table;
+  ax.x = x;
+  ax.ext_bar = ext_bar;
+  RDYN_HIP_TRY(rdyn_launch_forward_dynamics_vjp_ext(k.sw->n_joints(), ax, k.stream));
+  return RDYN_OK;
+}
+
 // ---- reverse-mode product with respect to the parameters (rdyn_fwd_dyn_param_vjp.hip) ----------------------------
 // Chains the unrolled kernels sweep (long ones through their reduced companion, the rows and sums expanded by X_f'): one launch, and two
 // small ones behind it when a sum is asked for.  The workspace holds the waves' partial sums [ceil(N / 64)][10 n_swept + C] and their
@@ -969,10 +1035,11 @@ static AdjointParamLayout adjoint_param_layout(const rdyn_chain* c, const rdyn_c
   return L;
 }
 
-// who = the entry point (error texts); pg null: rdyn_rollout_adjoint
+// who = the entry point (error texts); pg null: rdyn_rollout_adjoint; ext with w (never with pg): rdyn_rollout_adjoint_ext with wrenches,
+// gext its gradient selection (may be null)
 static int rollout_adjoint(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_adjoint_desc* d, const rdyn_component* comps, int n_comps,
                            const rdyn_parameter_gradient* pg, bool with_pg, int64_t chunk_samples, void* workspace, size_t workspace_bytes,
-                           const char* who)
+                           const char* who, const rdyn_ext_wrenches* ext = nullptr, const rdyn_ext_wrench_gradient* gext = nullptr)
 {
   int st = check_batch(c, b, true, false, who, LONG_KERNELS);
   if (st != RDYN_OK) return st;
@@ -991,7 +1058,22 @@ static int rollout_adjoint(const rdyn_chain* c, const rdyn_batch* b, const rdyn_
   if ((T >= 2 && d->traj_step_stride < nN) || (running && d->gtraj_step_stride < nN) ||
       (d->gtau && d->gtau_step_stride != 0 && d->gtau_step_stride < nN))
     return refuse(who, "traj_step_stride, gtraj_step_stride and a non-zero gtau_step_stride must be >= n * n_samples");
-  if (N > 0 && !with_pg && !d->gq0 && !d->gdq0 && !d->gtau) return refuse(who, "every output is null");
+  RdynExtArgs x;
+  st = check_ext(c, b, ext, true, who, &x);
+  if (st != RDYN_OK) return st;
+  double* const gw = (x.w && gext) ? gext->gw : nullptr;
+  if (gw)
+  {
+    const int64_t rec = (x.one ? 6 : 6 * (int64_t)(c->n_joints() + 1)) * N;
+    if (gext->step_stride < 0 || (gext->step_stride != 0 && gext->step_stride < rec))
+    {
+      rdyn_set_error("%s: wrench-gradient step_stride %lld is negative, or not zero and smaller than one step's record (%lld doubles)", who,
+                     (long long)gext->step_stride, (long long)rec);
+      return RDYN_ERR_INVALID_ARGUMENT;
+    }
+  }
+  if (N > 0 && !with_pg && !d->gq0 && !d->gdq0 && !d->gtau && !gw) return refuse(who, "every output is null");
+  if (x.w && (st = ext_reverse_refusal(c, who)) != RDYN_OK) return st;
   if (with_pg && fwd_dyn_by_chunks(c))
   {
     rdyn_set_error("%s: chains with more than %d input joints are not served yet (this chain has %d); rdyn_rollout_adjoint serves them", who,
@@ -1001,7 +1083,7 @@ static int rollout_adjoint(const rdyn_chain* c, const rdyn_batch* b, const rdyn_
   const AdjointLayout L = adjoint_layout(c, d, N, chunk_samples);
   const AdjointParamLayout PL = adjoint_param_layout(c, comps, n_comps, with_pg ? N : 0);
   DynCall k;
-  st = dyn_prepare(c, b, comps, n_comps, chunk_samples, with_pg ? PL.total : L.s.total, workspace, workspace_bytes, who, &k);
+  st = dyn_prepare(c, b, comps, n_comps, chunk_samples, with_pg ? PL.total : (x.w ? 0 : L.s.total), workspace, workspace_bytes, who, &k);
   if (st != RDYN_OK || !k.run) return st;
   if (k.sw)
   {
@@ -1036,6 +1118,20 @@ static int rollout_adjoint(const rdyn_chain* c, const rdyn_batch* b, const rdyn_
     if ((d->gq0 || d->gdq0) && stage_records(b, d->gq0, d->gdq0)) a.staged |= 1;
     if (d->gtau && stage_records(b, d->gtau) && (d->gtau_step_stride * (int64_t)sizeof(double)) % 128 == 0) a.staged |= 2;
     a.t = k.table;
+    if (x.w)
+    {
+      RdynRolloutAdjointExtArgs ax;
+      memset(&ax, 0, sizeof ax);
+      ax.a = a;
+      ax.x = x;
+      ax.gw = gw;
+      ax.gw_step = gw ? gext->step_stride : 0;
+      if (d->integrator == RDYN_INTEGRATOR_RK4)
+        RDYN_HIP_TRY(rdyn_launch_rollout_adjoint_ext_rk4(k.sw->n_joints(), ax, k.stream));
+      else
+        RDYN_HIP_TRY(rdyn_launch_rollout_adjoint_ext_euler(k.sw->n_joints(), ax, k.stream));
+      return RDYN_OK;
+    }
     if (!with_pg)
     {
       RDYN_HIP_TRY(rdyn_launch_rollout_adjoint(k.sw->n_joints(), a, k.stream));
@@ -1188,4 +1284,23 @@ int rdyn_rollout_adjoint_parameters(const rdyn_chain* c, const rdyn_batch* b, co
                                     size_t workspace_bytes)
 {
   return rollout_adjoint(c, b, d, comps, n_comps, pg, true, chunk_samples, workspace, workspace_bytes, "rdyn_rollout_adjoint_parameters");
+}
+
+size_t rdyn_rollout_adjoint_ext_workspace_bytes(const rdyn_chain* c, const rdyn_rollout_adjoint_desc* d, const rdyn_ext_wrenches* ext,
+                                                int64_t n_samples, int64_t chunk_samples)
+{
+  return (ext && ext->w) ? 0 : adjoint_layout(c, d, n_samples, chunk_samples).s.total;
+}
+
+int rdyn_rollout_adjoint_ext(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_adjoint_desc* d, const rdyn_component* comps, int n_comps,
+                             const rdyn_ext_wrenches* ext, const rdyn_ext_wrench_gradient* gext, int64_t chunk_samples, void* workspace,
+                             size_t workspace_bytes)
+{
+  const char* const who = "rdyn_rollout_adjoint_ext";
+  if (!ext || !ext->w)
+  {
+    if (gext && gext->gw) return refuse(who, "a wrench gradient without external wrenches");
+    return rollout_adjoint(c, b, d, comps, n_comps, nullptr, false, chunk_samples, workspace, workspace_bytes, "rdyn_rollout_adjoint");
+  }
+  return rollout_adjoint(c, b, d, comps, n_comps, nullptr, false, chunk_samples, workspace, workspace_bytes, who, ext, gext);
 }

@@ -22,6 +22,7 @@
 #include "rdyn_component_row.h"
 #include "rdyn_joint_step.h"
 #include "rdyn_tangent_step.h"
+#include "rdyn_ext_wrench.h"
 
 namespace
 {
@@ -39,7 +40,9 @@ __device__ __forceinline__ bool fwd_dyn_vjp_eval(ChainPtr c, const RdynComponent
                                                  double (&ab)[NJ], double (&qb)[NJ], double (&vb)[NJ], bool want_q, bool want_v, EARLY early)
 {
 #define RDYN_VJP_PARAMS 0
+#define RDYN_VJP_EXT 0
 #include "rdyn_fwd_dyn_vjp_body.inc"
+#undef RDYN_VJP_EXT
 #undef RDYN_VJP_PARAMS
 }
 
@@ -51,7 +54,42 @@ __device__ __forceinline__ bool fwd_dyn_vjp_params_eval(ChainPtr c, const RdynCo
                                                         LINK link)
 {
 #define RDYN_VJP_PARAMS 1
+#define RDYN_VJP_EXT 0
 #include "rdyn_fwd_dyn_vjp_body.inc"
+#undef RDYN_VJP_EXT
+#undef RDYN_VJP_PARAMS
+}
+
+// ---- with external link wrenches (rdyn_ext_wrench.h)
+// the tangent of a link's wrench contribution [-(e.lin + e.ang x pl); -e.ang] along dpl, the tangent of pl: the force part alone has one
+__device__ __forceinline__ void ext_tangent_wrench(const ExtEval& x, int link, V3 dpl, V3& dfo)
+{
+  V3 ea;
+  if (x.one == 0)
+  {
+    const double* const p = x.rec + (int64_t)(6 * link + 3) * x.se;
+    ea = mk(p[0], p[x.se], p[2 * x.se]);
+  }
+  else if (x.one == link + 1)
+    ea = x.a;
+  else
+    return;
+  dfo = dfo - cross(ea, dpl);
+}
+
+// The product of ddq = FD_E(q, dq, tau, ext) = FD_c(q, dq, tau - tau_E(q, ext)), x the wrenches of the evaluation
+// (rdyn_fwd_dyn_vjp_ext.hip, rdyn_rollout_adjoint_ext.hip; rdyn_fwd_dyn_vjp_body.inc says what changes): q_bar gains -(d tau_E / d q)' w,
+// and with want_e (wave-uniform) ext_out(link, lin, ang) is handed -(d tau_E / d ext)' w of every chain link 1 .. NJ, base to tip, behind
+// early(): [lin; ang] in the layout of the link's wrench record.  tau_E is linear in ext: the record does not depend on the wrenches.
+template <int NJ, class QF, class DQF, class EARLY, class EXTOUT>
+__device__ __forceinline__ bool fwd_dyn_vjp_ext_eval(ChainPtr c, const RdynComponentTable& tb, QF q_of, DQF dq_of, double (&rhs)[NJ],
+                                                     double (&ab)[NJ], double (&qb)[NJ], double (&vb)[NJ], bool want_q, bool want_v, EARLY early,
+                                                     ExtEval x, bool want_e, EXTOUT ext_out)
+{
+#define RDYN_VJP_PARAMS 0
+#define RDYN_VJP_EXT 1
+#include "rdyn_fwd_dyn_vjp_body.inc"
+#undef RDYN_VJP_EXT
 #undef RDYN_VJP_PARAMS
 }
 

@@ -750,6 +750,26 @@ struct RdynAdjointUpdateArgs
 };
 hipError_t rdyn_launch_adjoint_update(const RdynAdjointUpdateArgs& a, hipStream_t st);
 
+// the product and the adjoint with external link wrenches (rdyn_fwd_dyn_vjp_ext.hip, rdyn_rollout_adjoint_ext.hip): of
+// ddq = FD_c(q, dq, tau - tau_E(q, ext)) and of the rollout RdynRolloutExtArgs describes.  x = the wrenches (w not null); ext_bar / gw: null,
+// or -(d tau_E / d ext)' w in the layout of x.w (strides x.ss, x.se), step t of the adjoint at gw + t * gw_step (0: the sum over the steps).
+struct RdynFwdDynVjpExtArgs
+{
+  RdynFwdDynVjpArgs v;
+  RdynExtArgs x;
+  double* ext_bar;
+};
+hipError_t rdyn_launch_forward_dynamics_vjp_ext(int n_joints, const RdynFwdDynVjpExtArgs& a, hipStream_t st);
+struct RdynRolloutAdjointExtArgs
+{
+  RdynRolloutAdjointArgs a;
+  RdynExtArgs x;
+  double* gw;
+  int64_t gw_step;
+};
+hipError_t rdyn_launch_rollout_adjoint_ext_euler(int n_joints, const RdynRolloutAdjointExtArgs& a, hipStream_t st);
+hipError_t rdyn_launch_rollout_adjoint_ext_rk4(int n_joints, const RdynRolloutAdjointExtArgs& a, hipStream_t st);
+
 // pieces of rdyn_identification_tsqr for the multi-device form (rdyn_api_tsqr.cpp): widths of the swept / the chain's factor, the factor of
 // the swept chain alone, the expansion (+ accumulation) of a swept factor
 int rdyn_internal_tsqr_widths(const rdyn_chain* c, const rdyn_component* comps, int n_comps, int* n1s, int* n1, int* expands);

@@ -45,7 +45,9 @@ template <int NJ, int INTEGRATOR>
 __global__ __launch_bounds__(64) void k_rollout_adjoint(const RdynRolloutAdjointArgs a)
 {
 #define RDYN_ADJ_PARAMS 0
+#define RDYN_ADJ_EXT 0
 #include "rdyn_rollout_adjoint_body.inc"
+#undef RDYN_ADJ_EXT
 #undef RDYN_ADJ_PARAMS
 }
 

@@ -4,6 +4,11 @@
 // RDYN_ADJ_PARAMS 1 (k_rollout_adjoint_params; also expects p, RdynAdjointParamAcc): every product adds its parameter rows -- the ten
 // entries per link of link_parameter_row, then the component columns -- to the lane's own accumulators p.acc[col * p.ld + s], zeroed
 // here first, and the sample's final verdict goes to p.status[s]: the host sums the columns over the samples that ended alive.
+// RDYN_ADJ_EXT 1 (k_rollout_adjoint_ext; RDYN_ADJ_PARAMS 0; the kernel argument is ax, RdynRolloutAdjointExtArgs, a = ax.a): the rollout
+// is rdyn_rollout_ext's -- the wrench of step t, held over the step, enters the rebuilt RK4 stages (fwd_dyn_eval_ext) and every product
+// (fwd_dyn_vjp_ext_eval) at that stage's own q.  With gw every product ADDS its -(d tau_E / d ext)' w to the lane's own record of the
+// step in memory (6 (NJ + 1) doubles per lane do not belong in registers), zeroed when the step begins -- or once, here, when the
+// record is the sum over the steps (gw_step = 0): read-modify-write by the one lane that owns it, in the order of the products.
   const ChainPtr c = as_const(a.chain);
   const int lane = threadIdx.x;
   const int64_t s_wave = (int64_t)blockIdx.x * 64;
@@ -32,6 +37,34 @@
     double* const x = pacc + (int64_t)(10 * f) * p.ld;
 #pragma unroll
     for (int k = 0; k < 10; ++k) x[k * p.ld] += g[k];
+  };
+#endif
+
+#if RDYN_ADJ_EXT
+  const RdynExtArgs& x = ax.x;
+  const double* const xp = x.w + s * x.ss;
+  ExtEval xe;
+  xe.rec = xp;
+  xe.se = x.se;
+  xe.one = x.one;
+  xe.l = xe.a = mk(0, 0, 0);
+  const int n_rec = x.one ? 6 : 6 * (NJ + 1);  // doubles of one step's record of the lane
+  double* const gwp = ax.gw ? ax.gw + s * x.ss : nullptr;
+  double* gw = gwp;  // the record the products of the step add to
+  if (gwp && !ax.gw_step)
+  {
+#pragma unroll 1
+    for (int e = 0; e < n_rec; ++e) gwp[e * x.se] = 0.0;
+  }
+  auto ext_out = [&](int link, V3 lin, V3 ang) {
+    if (x.one != 0 && x.one != link + 1) return;  // wave-uniform
+    double* const p = gw + (x.one ? 0 : (int64_t)(6 * link) * x.se);
+    p[0] += lin.x;
+    p[x.se] += lin.y;
+    p[2 * x.se] += lin.z;
+    p[3 * x.se] += ang.x;
+    p[4 * x.se] += ang.y;
+    p[5 * x.se] += ang.z;
   };
 #endif
 
@@ -69,6 +102,16 @@
       load_record<NJ>(c, t == 0 ? a.dq + so : a.dq_traj + ro, a.in_sj, dq);
       load_record<NJ>(c, a.tau + (int64_t)t * a.tau_step + so, a.in_sj, tau);
     }
+#if RDYN_ADJ_EXT
+    xe.rec = xp + (int64_t)t * x.step;
+    if (x.one) ext_load6(xe.rec, x.se, xe.l, xe.a);
+    if (gwp && ax.gw_step)
+    {
+      gw = gwp + (int64_t)t * ax.gw_step;
+#pragma unroll 1
+      for (int e = 0; e < n_rec; ++e) gw[e * x.se] = 0.0;
+    }
+#endif
     bool ok = true;
     if (INTEGRATOR == RDYN_INTEGRATOR_SEMI_IMPLICIT_EULER)
     {
@@ -83,6 +126,9 @@
       ok = fwd_dyn_vjp_params_eval<NJ>(per_evaluation(c), a.t, [&](int f, int) { return q[f]; }, [&](int f, int) { return dq[f]; }, tau, gt, qb,
                                        vb, true, true, [](bool, double (&)[NJ]) {}, link);
       component_parameter_rows<NJ>(c, a.t, q, dq, gt, pacc + (int64_t)(10 * NJ) * p.ld, p.ld);
+#elif RDYN_ADJ_EXT
+      ok = fwd_dyn_vjp_ext_eval<NJ>(per_evaluation(c), a.t, [&](int f, int) { return q[f]; }, [&](int f, int) { return dq[f]; }, tau, gt, qb, vb,
+                                    true, true, [](bool, double (&)[NJ]) {}, xe, gwp != nullptr, ext_out);
 #else
       ok = fwd_dyn_vjp_eval<NJ>(per_evaluation(c), a.t, [&](int f, int) { return q[f]; }, [&](int f, int) { return dq[f]; }, tau, gt, qb, vb, true,
                                 true, [](bool, double (&)[NJ]) {});
@@ -118,7 +164,11 @@
             rhs[f] = tau[f];
             if (idx >= 0) rhs[f] -= joint_component_torque(a.t, idx, sq[f], kq[f]);
           }
+#if RDYN_ADJ_EXT
+          fwd_dyn_eval_ext<NJ>(per_evaluation(c), sq, kq, rhs, xe);
+#else
           fwd_dyn_eval<NJ>(per_evaluation(c), sq, kq, rhs);  // (its pivot test runs again inside the stage's product)
+#endif
           const double cdt = stage == 2 ? dt : 0.5 * dt;  // of the NEXT stage
 #pragma unroll
           for (int f = 0; f < NJ; ++f)
@@ -163,6 +213,10 @@
                                          qb, vb, true, true, [](bool, double (&)[NJ]) {}, link) &&
              ok;
         component_parameter_rows<NJ>(c, a.t, sq, sv, mu, pacc + (int64_t)(10 * NJ) * p.ld, p.ld);
+#elif RDYN_ADJ_EXT
+        ok = fwd_dyn_vjp_ext_eval<NJ>(per_evaluation(c), a.t, [&](int f, int) { return sq[f]; }, [&](int f, int) { return sv[f]; }, rhs, mu, qb,
+                                      vb, true, true, [](bool, double (&)[NJ]) {}, xe, gwp != nullptr, ext_out) &&
+             ok;
 #else
         ok = fwd_dyn_vjp_eval<NJ>(per_evaluation(c), a.t, [&](int f, int) { return sq[f]; }, [&](int f, int) { return sv[f]; }, rhs, mu, qb, vb,
                                 true, true, [](bool, double (&)[NJ]) {}) &&
@@ -195,6 +249,13 @@
       gt[f] = alive ? gt[f] : qnan;
       gsum[f] += gt[f];
     }
+#if RDYN_ADJ_EXT
+    if (gwp && ax.gw_step && !alive)
+    {
+#pragma unroll 1
+      for (int e = 0; e < n_rec; ++e) gw[e * x.se] = qnan;
+    }
+#endif
     if (a.gtau && a.gtau_step)
     {
       const int64_t go = (int64_t)t * a.gtau_step;
@@ -219,6 +280,13 @@
   }
 
   if (a.status) a.status[s] = alive ? 1 : -1;
+#if RDYN_ADJ_EXT
+  if (gwp && !ax.gw_step && !alive)
+  {
+#pragma unroll 1
+    for (int e = 0; e < n_rec; ++e) gwp[e * x.se] = qnan;
+  }
+#endif
 #if RDYN_ADJ_PARAMS
   p.status[s] = alive ? 1 : -1;
 #endif

@@ -24,7 +24,9 @@ template <int NJ, int INTEGRATOR>
 __global__ __launch_bounds__(64) void k_rollout_adjoint_params(const RdynRolloutAdjointArgs a, const RdynAdjointParamAcc p)
 {
 #define RDYN_ADJ_PARAMS 1
+#define RDYN_ADJ_EXT 0
 #include "rdyn_rollout_adjoint_body.inc"
+#undef RDYN_ADJ_EXT
 #undef RDYN_ADJ_PARAMS
 }
 

@@ -970,6 +970,31 @@ public:
     chk(rdyn_forward_dynamics_vjp(m_h, &b, comps.empty() ? nullptr : comps.data(), (int)comps.size(), tau, DDq_bar, q_bar, Dq_bar, tau_bar, ddq, status,
                                   chunk_samples, workspace, workspace_bytes));
   }
+  // ... both with external link wrenches (rdyn_forward_dynamics_vjp_ext, rdyn_rollout_adjoint_ext; ext.w a device pointer): ext_bar / gext.gw
+  // in the layout of ext.w, may be null; chains swept in registers only (others throw what RDYN_ERR_UNSUPPORTED throws)
+  size_t getJointAccelerationVjpWorkspaceBytes(const rdyn_ext_wrenches& ext, int64_t chunk_samples = 0) const
+  {
+    return rdyn_forward_dynamics_vjp_ext_workspace_bytes(m_h, &ext, chunk_samples);
+  }
+  void getJointAccelerationVjpBatch(const std::vector<rdyn_component>& comps, const rdyn_ext_wrenches& ext, const rdyn_batch& b, const double* tau,
+                                    const double* DDq_bar, double* q_bar, double* Dq_bar, double* tau_bar, double* ext_bar, double* ddq,
+                                    int32_t* status, int64_t chunk_samples, void* workspace, size_t workspace_bytes) const
+  {
+    chk(rdyn_forward_dynamics_vjp_ext(m_h, &b, comps.empty() ? nullptr : comps.data(), (int)comps.size(), &ext, tau, DDq_bar, q_bar, Dq_bar, tau_bar,
+                                      ext_bar, ddq, status, chunk_samples, workspace, workspace_bytes));
+  }
+  size_t rolloutAdjointWorkspaceBytes(const rdyn_rollout_adjoint_desc& desc, const rdyn_ext_wrenches& ext, int64_t n_samples,
+                                      int64_t chunk_samples = 0) const
+  {
+    return rdyn_rollout_adjoint_ext_workspace_bytes(m_h, &desc, &ext, n_samples, chunk_samples);
+  }
+  void rolloutAdjointBatch(const std::vector<rdyn_component>& comps, const rdyn_ext_wrenches& ext, const rdyn_ext_wrench_gradient& gext,
+                           const rdyn_batch& b, const rdyn_rollout_adjoint_desc& desc, int64_t chunk_samples, void* workspace,
+                           size_t workspace_bytes) const
+  {
+    chk(rdyn_rollout_adjoint_ext(m_h, &b, &desc, comps.empty() ? nullptr : comps.data(), (int)comps.size(), &ext, &gext, chunk_samples, workspace,
+                                 workspace_bytes));
+  }
   // ---- gradients with respect to the model's parameters (no reference counterpart)
   // the chain with the inertial parameters pi (10 per chain joint, the order of getNominalParameters; stored as given): an independent
   // chain equal to clone() in everything else: rdyn_chain_with_parameters

@@ -1,0 +1,58 @@
+"""The reverse-mode calls with external wrenches of the C++ facade (rosdyn_chain_facade.hpp: getJointAccelerationVjpBatch / rolloutAdjointBatch
+with a rdyn_ext_wrenches and their workspace queries) through tests/cpp/rollout_adjoint_ext_facade.cpp: it builds host-only, pedantic,
+against the stand-in Eigen headers, and on the GPU its results are the Python binding's bits."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import FIXTURES, ROOT
+from test_forward_dynamics_ext_facade import CHAINS, _value
+
+
+def _build(tmp_path):
+    exe = tmp_path / "rollout_adjoint_ext_facade"
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-pedantic", "-D__HIP_PLATFORM_AMD__", "-isystem", "/opt/rocm/include",
+                           "-I" + os.path.join(ROOT, "tests", "mock_include"), "-I" + os.path.join(ROOT, "rosdyn_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "cpp", "rollout_adjoint_ext_facade.cpp"), "-o", str(exe),
+                           "-L" + os.path.join(ROOT, "rosdyn_amd"), "-lrdyn_hip", "-L/opt/rocm/lib", "-lamdhip64",
+                           "-Wl,-rpath," + os.path.join(ROOT, "rosdyn_amd"), "-Wl,-rpath,/opt/rocm/lib"])
+    return str(exe)
+
+
+def test_the_caller_builds_pedantic_against_the_stand_in_eigen_headers(tmp_path):
+    exe = _build(tmp_path)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 2 and "usage" in r.stderr
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("urdf,base,tool", CHAINS)
+def test_the_facade_gives_the_python_binding_own_bits(tmp_path, urdf, base, tool):
+    torch = pytest.importorskip("torch")
+    from rosdyn_amd import Chain
+    exe = _build(tmp_path)
+    r = subprocess.run([exe, os.path.join(FIXTURES, urdf), base, tool], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.rstrip().endswith("ok"), r.stdout + r.stderr
+    got = {ln.split()[0]: np.array([float(x) for x in ln.split()[1:]]) for ln in r.stdout.splitlines() if " " in ln}
+    chain = Chain(os.path.join(FIXTURES, urdf), base, tool, (0.0, 0.0, -9.806))
+    n, L, N, T = chain.getActiveJointsNumber(), chain.getLinksNumber(), 5, 3
+    grid = lambda k, m=n: np.array([[_value(s, i, k) for i in range(m)] for s in range(N)])
+    dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    flat = lambda t: t.cpu().numpy().ravel()
+    q, dq, seed = dev(grid(0)), dev(grid(1)), dev(grid(9))
+    tau = dev(np.stack([0.5 * grid(2 + t) for t in range(T)]))
+    w_all = dev(0.25 * grid(11, 6 * L).reshape(N, L, 6))
+    w_tool = dev(np.stack([0.5 * grid(12 + t, 6) for t in range(T)]))
+    out = chain.getJointAccelerationVjp(q, dq, tau[0], seed, want=("q", "dq", "tau", "ext", "ddq"), ext_wrenches=w_all)
+    assert bool((out[0] == 1).all())
+    for key, t in zip(("q_bar", "dq_bar", "tau_bar", "ext_bar", "ddq"), out[1:]):
+        assert np.array_equal(got[key], flat(t)), key
+    for suffix, kw, sum_ext in (("", {"ext_wrenches": w_all}, True), ("_tool", {"ext_wrenches": w_tool, "ext_link": chain.getLinksName()[-1]}, False)):
+        fw = chain.rollout(q, dq, tau, 1e-3, integrator="rk4", trajectory_every=1, **kw)
+        g = chain.rolloutAdjoint(q, dq, tau, 1e-3, fw[3], fw[4], gq_end=seed, integrator="rk4", want_ext=True, sum_ext=sum_ext, **kw)
+        assert bool((g[3] == 1).all())
+        for key, t in zip(("gq0", "gdq0", "gtau", "gext"), (g[0], g[1], g[2], g[4])):
+            assert np.array_equal(got[key + suffix], flat(t)), key + suffix
+    assert not np.array_equal(got["gq0_tool"], got["gq0"])
