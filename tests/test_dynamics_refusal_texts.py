@@ -7,11 +7,9 @@ import ctypes as C
 
 import pytest
 
-from test_forward_dynamics_cabi import _chain
-from test_rollout_adjoint_cabi import _comp
+from _cabi import FAKE, _chain, _comp
 
 INVALID = 1
-FAKE = 4096
 N = 7
 CHAINS = ["ur10_like", "rev11"]   # one chain swept in registers (no workspace), one on the chunked route
 CHUNKED = {"rev11"}

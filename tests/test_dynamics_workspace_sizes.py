@@ -2,53 +2,11 @@
 tests/golden/dynamics_workspace_bytes.json (tools/record_dynamics_workspace_bytes.py wrote it; it is recorded once and not
 regenerated from the build under test), and the nesting the layouts promise.  A workspace a caller sized with an earlier build
 must still fit.  Nothing here touches a device."""
-import ctypes as C
 import json
-import os
 
 import pytest
 
-from conftest import GOLDEN
-from test_forward_dynamics_cabi import CHUNKED, SWEPT, _chain
-
-GOLDEN_FILE = os.path.join(GOLDEN, "dynamics_workspace_bytes.json")
-CHUNKS = (0, 1, 64, 1000, 16384)
-SAMPLES = (0, 1, 4096)
-INTEGRATORS = (0, 1)   # semi-implicit Euler, RK4
-FAKE = 4096
-
-
-def _rollout_desc(integrator):
-    from rosdyn_amd._lib import RolloutDesc
-    d = RolloutDesc()
-    d.n_steps, d.integrator, d.dt, d.tau, d.q_end = 5, integrator, 1e-3, FAKE, FAKE
-    return d
-
-
-def _adjoint_desc(integrator):
-    from rosdyn_amd._lib import RolloutAdjointDesc
-    d = RolloutAdjointDesc()
-    d.n_steps, d.integrator, d.dt, d.tau, d.gq0 = 5, integrator, 1e-3, FAKE, FAKE
-    return d
-
-
-def measure(name):
-    """Every pinned query of one chain: {query: {key: bytes}}; key = "chunk" or "integrator/n_samples/chunk"."""
-    from rosdyn_amd._lib import lib
-    chain = _chain(name)   # (kept alive while its handle is in use)
-    l, h = lib(), chain._h
-    out = {"forward": {}, "derivatives": {}, "vjp": {}, "rollout": {}, "adjoint": {}}
-    for chunk in CHUNKS:
-        out["forward"][str(chunk)] = l.rdyn_forward_dynamics_workspace_bytes(h, chunk)
-        out["derivatives"][str(chunk)] = l.rdyn_forward_dynamics_derivatives_workspace_bytes(h, chunk)
-        out["vjp"][str(chunk)] = l.rdyn_forward_dynamics_vjp_workspace_bytes(h, chunk)
-        for integrator in INTEGRATORS:
-            rd, ad = _rollout_desc(integrator), _adjoint_desc(integrator)
-            for N in SAMPLES:
-                key = "%d/%d/%d" % (integrator, N, chunk)
-                out["rollout"][key] = l.rdyn_rollout_workspace_bytes(h, C.byref(rd), N, chunk)
-                out["adjoint"][key] = l.rdyn_rollout_adjoint_workspace_bytes(h, C.byref(ad), N, chunk)
-    return out
+from _cabi import CHUNKED, CHUNKS, GOLDEN_FILE, INTEGRATOR_CODES as INTEGRATORS, SAMPLES, SWEPT, measure
 
 
 @pytest.fixture(scope="module")

@@ -1,33 +1,10 @@
 """CPU tests (no GPU): argument checks and the workspace query of rdyn_forward_dynamics (ddq = M^-1 (tau - h), include/rdyn.h).
 Nothing here touches a device: every call either has no samples or fails its checks first."""
 import ctypes as C
-import os
 
 import pytest
 
-from conftest import FIXTURES
-from test_gpu_longkin import generated_long_chain, generated_revolute_chain
-
-RDYN_OK = 0
-RDYN_ERR_INVALID_ARGUMENT = 1
-FAKE = 4096   # never dereferenced: the checks come first
-PERMUTED_12 = ["j13", "j0", "j9", "j4", "j16", "j1", "j7", "j19", "j3", "j10", "j6", "j12"]   # test_gpu_long_ik.py's input list
-
-
-def _chain(name):
-    from rosdyn_amd import Chain
-    if name == "ur10_like":
-        return Chain(os.path.join(FIXTURES, "ur10_like.urdf"), "base_link", "tool0")
-    if name == "panda_like":
-        return Chain(os.path.join(FIXTURES, "panda_like.urdf"), "link0", "hand")
-    if name == "ur10_public":
-        return Chain(os.path.join(FIXTURES, "ur10_public.urdf"), "base_link", "tool0")
-    if name == "gen20_permuted":
-        chain = Chain(generated_long_chain(20, 2020), "l0", "l20")
-        assert chain.setInputJointsName(PERMUTED_12)
-        return chain
-    nj = int(name[3:])
-    return Chain(generated_revolute_chain(nj, 1000 + nj), "l0", "l%d" % nj)
+from _cabi import CHUNKED, FAKE, RDYN_ERR_INVALID_ARGUMENT, RDYN_OK, SWEPT, _chain
 
 
 def _query(chain, chunk_samples=0):
@@ -47,10 +24,6 @@ def _call(chain, n_samples, q=FAKE, dq=FAKE, tau=FAKE, ddq=FAKE, status=FAKE, ch
     if workspace_bytes is None:
         workspace_bytes = _query(chain, max(chunk_samples, 0))
     return lib().rdyn_forward_dynamics(chain._h, C.byref(b) if batch else None, tau, ddq, status, chunk_samples, workspace, workspace_bytes)
-
-
-SWEPT = ["ur10_like", "panda_like", "ur10_public"]
-CHUNKED = ["rev11", "rev20", "rev32", "gen20_permuted"]
 
 
 @pytest.mark.parametrize("name", SWEPT + CHUNKED)

@@ -4,12 +4,9 @@ import ctypes as C
 
 import pytest
 
-from test_forward_dynamics_cabi import CHUNKED, SWEPT, _chain
-from test_rollout_components_cabi import FRICTION1, FRICTION2, SPRING, _comps
+from _cabi import CHUNKED, FAKE, RDYN_ERR_INVALID_ARGUMENT, RDYN_OK, SWEPT, _chain, _comps
+from _components import FRICTION1, FRICTION2, SPRING
 
-RDYN_OK = 0
-RDYN_ERR_INVALID_ARGUMENT = 1
-FAKE = 4096   # never dereferenced: the checks come first
 ONE_SWEPT, ONE_CHUNKED = SWEPT[0], CHUNKED[1]
 
 

@@ -8,23 +8,8 @@ import re
 import pytest
 
 from conftest import FIXTURES, ROOT
-from test_forward_dynamics_cabi import CHUNKED, SWEPT, _chain
-from test_rollout_cabi import EULER, FAKE, RDYN_ERR_INVALID_ARGUMENT, RDYN_OK, RK4, _desc, _query
-from test_rollout_components_cabi import FRICTION1, SPRING, _comps
-
-
-def _ext(w=FAKE, link=-1, step_stride=0):
-    from rosdyn_amd._lib import ExtWrenches
-    x = ExtWrenches()
-    x.w, x.link, x.step_stride = w, link, step_stride
-    return x
-
-
-def _batch(N, q=FAKE, dq=FAKE, layout=0):
-    from rosdyn_amd._lib import Batch
-    b = Batch()
-    b.n_samples, b.q, b.dq, b.layout, b.device = N, q, dq, layout, 0
-    return b
+from _cabi import CHUNKED, EULER, FAKE, RDYN_ERR_INVALID_ARGUMENT, RDYN_OK, RK4, SWEPT, _batch, _chain, _comps, _ext, _query, _rollout_desc as _desc
+from _components import FRICTION1, SPRING
 
 
 def _rollout(chain, N, ext, comps=None, n_comps=0, desc=True, chunk_samples=0, workspace=FAKE, workspace_bytes=None, q=FAKE, dq=FAKE, batch=True,

@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 from conftest import FIXTURES, ROOT
-
-CHAINS = [("ur10_like.urdf", "base_link", "tool0"), ("mixed_joints.urdf", "world", "tip")]
+from _arrays import _value
+from _chains import FACADE_CHAINS as CHAINS
 
 
 def _build(tmp_path):
@@ -27,10 +27,6 @@ def test_the_caller_builds_pedantic_against_the_stand_in_eigen_headers(tmp_path)
     exe = _build(tmp_path)
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 2 and "usage" in r.stderr
-
-
-def _value(s, i, k):
-    return ((s * 7 + i * 3 + k * 5) % 17 - 8) / 16.0
 
 
 @pytest.mark.gpu

@@ -7,19 +7,19 @@ both layouts."""
 import numpy as np
 import pytest
 
-import test_gpu_fuzz_dynamics as fz
-import test_gpu_fuzz_gradients as fg
-from test_gpu_forward_dynamics import _inf
-from test_gpu_forward_dynamics_derivatives import FRICTION1, FRICTION2, MAX_VELOCITY, MIN_VELOCITY, SPRING, _pin_the_closed_form_to_the_oracle
-from test_gpu_torque_derivatives import _reference
+from _arrays import INTEGRATORS, PRISMATIC, _inf
+from _components import FRICTION1, FRICTION2, MAX_VELOCITY, MIN_VELOCITY, SPRING, _pin_the_closed_form_to_the_oracle
+from _fuzz import FUZZ_OFFSET, case, rollout_bound, seed_class
+from _references import _reference
+import _fuzz as fg
 
 
 @pytest.fixture(scope="module")
 def regular():
-    if fz.FUZZ_OFFSET != 0:
+    if FUZZ_OFFSET != 0:
         pytest.skip("the pinned facts are those of the committed seeds (RDYN_FUZZ_OFFSET=0)")
-    cases = [c for c in (fz.case(seed) for seed in range(64)) if c.full.n > 0]
-    out = [c for c in cases if fz.seed_class(c) == "regular"]
+    cases = [c for c in (case(seed) for seed in range(64)) if c.full.n > 0]
+    out = [c for c in cases if seed_class(c) == "regular"]
     assert len(out) == 58
     return out
 
@@ -46,7 +46,7 @@ def test_the_friction_joints_see_the_linear_band_and_the_saturation(regular):
     assert band >= 0.2 and sat >= 0.1, (band, sat)
 
 
-@pytest.mark.parametrize("integrator", fz.INTEGRATORS)
+@pytest.mark.parametrize("integrator", INTEGRATORS)
 def test_the_run_time_rollout_bound_with_components_is_small_and_the_components_matter(regular, integrator):
     worst, least, fastest = 0.0, np.inf, 0.0
     for c in regular:
@@ -56,7 +56,7 @@ def test_the_run_time_rollout_bound_with_components_is_small_and_the_components_
         worst = max(worst, dev)
         fastest = max(fastest, float(np.abs(dqr).max()))
         # the same oracle rollout without components: away from the one with them by more than the bound, on some sample
-        _, _, qp, dqp = fz.rollout_bound(c, integrator)
+        _, _, qp, dqp = rollout_bound(c, integrator)
         scale = np.maximum(1.0, np.maximum(_inf(qr), _inf(dqr)))
         moved = float((np.maximum(_inf(qp - qr), _inf(dqp - dqr)) / scale).max())
         assert moved > bound, (c.seed, moved, bound)
@@ -85,7 +85,8 @@ def test_the_closed_form_slopes_are_the_oracle_s_on_the_fuzz_inputs(regular):
 def test_the_slopes_move_the_derivative_residuals_above_one_in_a_million(regular):
     """test_forward_dynamics_derivatives asserts that the residual without the slopes exceeds 1e-6.  Here the same ratio, in the units of
     _residual_ratios, for the oracle's exact X = -M_ref^-1 (D_ref + diag slopes) at the oracle's own ddq: the inputs allow the assertion."""
-    from test_gpu_forward_dynamics_derivatives import _norm_inf, _slopes
+    from _components import _slopes
+    from _references import _norm_inf
     least = {"dddq_dq": np.inf, "dddq_dv": np.inf}
     for c in regular:
         specs = fg.fuzz_specs(c)
@@ -111,6 +112,6 @@ def test_the_seeds_reach_what_the_gradient_kernels_had_not_seen(regular):
     locked = [c for c in regular if c.inputs is not None and len(c.inputs) < c.full.n]
     assert locked and any(c.inputs != [nm for nm in c.full.spec.moveable if nm in c.inputs] for c in locked)   # locked AND permuted
     assert any(c.ref.nJ > c.full.n for c in regular)                        # fixed joints inside the chain
-    assert any(fz.PRISMATIC in c.oracle_types() for c in regular) and any(c.oracle_types().count(fz.PRISMATIC) >= 2 for c in regular)
+    assert any(PRISMATIC in c.oracle_types() for c in regular) and any(c.oracle_types().count(PRISMATIC) >= 2 for c in regular)
     assert {c.layout for c in regular} == {"sample", "element"}
     print("%d regular seeds; %d subset seeds with a locked moveable joint; nJ %s" % (len(regular), len(locked), sorted({c.ref.nJ for c in regular})))

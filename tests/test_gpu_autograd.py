@@ -7,29 +7,11 @@ piecewise linear in Dq: they are included only where every |Dq| of the horizon k
 import numpy as np
 import pytest
 
-from test_gpu_forward_dynamics import _chain
-from test_gpu_rollout import INTEGRATORS, TAU_SCALE
+from _arrays import AUTOGRAD_DT as DT, AUTOGRAD_T as T, INTEGRATORS, _leaves
+from _chains import _chain
+from _components import AUTOGRAD_MAX_VELOCITY as MAX_VELOCITY, AUTOGRAD_MIN_VELOCITY as MIN_VELOCITY, _autograd_components as _components
 
 pytestmark = pytest.mark.gpu
-N, T, DT = 3, 4, 1e-2
-FRICTION1, SPRING = 0, 2
-MIN_VELOCITY, MAX_VELOCITY = 0.05, 1000.0
-
-
-def _leaves(torch, name, n, steps=None, seed=8100, dq_offset=0.0):
-    from rosdyn_amd.samples import uniform_pm1
-    q = uniform_pm1(seed, (N, n))
-    dq = uniform_pm1(seed + 1, (N, n)) + dq_offset
-    tau = TAU_SCALE[name] * uniform_pm1(seed + 2, (N, n) if steps is None else (steps, N, n))
-    return tuple(torch.from_numpy(x).cuda().requires_grad_(True) for x in (q, dq, tau))
-
-
-def _components(n):
-    """friction on the first two joints (band +-0.05, saturation far away), a spring on joint 0"""
-    from rosdyn_amd.components import ComponentSet
-    return ComponentSet([dict(type=FRICTION1, joint=0, min_velocity=MIN_VELOCITY, max_velocity=MAX_VELOCITY, parameters=[0.3, 0.2, 0.0]),
-                         dict(type=FRICTION1, joint=1, min_velocity=MIN_VELOCITY, max_velocity=MAX_VELOCITY, parameters=[0.1, 0.05, 0.0]),
-                         dict(type=SPRING, joint=0, min_velocity=0.0, max_velocity=0.0, parameters=[2.0, -0.1, 0.0])], n)
 
 
 def _away_from_the_kinks(dq):

@@ -4,9 +4,9 @@ wrench held over the horizon (its gradient the sum over the steps) and for one r
 tolerances compares the backward with central differences of the wrappers' own forward calls."""
 import pytest
 
-from test_gpu_autograd import DT, N, T, _components, _leaves
-from test_gpu_forward_dynamics import _chain
-from test_gpu_rollout import INTEGRATORS, TAU_SCALE
+from _arrays import AUTOGRAD_DT as DT, AUTOGRAD_N as N, AUTOGRAD_T as T, INTEGRATORS, TAU_SCALE, _leaves
+from _chains import _chain
+from _components import _autograd_components as _components
 
 pytestmark = pytest.mark.gpu
 

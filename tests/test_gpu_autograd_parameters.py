@@ -4,11 +4,9 @@ leaves the gradients of the state and the torques those of the existing path, an
 import numpy as np
 import pytest
 
-from test_gpu_forward_dynamics import _dev
-from test_gpu_forward_dynamics_derivatives import _set, _specs
-from test_gpu_rollout import INTEGRATORS, _dev_seq
-from test_gpu_rollout_adjoint import _inputs
-from test_gpu_rollout_components import _cpair
+from _arrays import INTEGRATORS, _adjoint_inputs as _inputs, _dev, _dev_seq
+from _chains import _cpair
+from _components import _set, _specs
 
 pytestmark = pytest.mark.gpu
 

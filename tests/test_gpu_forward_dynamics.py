@@ -20,87 +20,12 @@ import numpy as np
 import pytest
 
 from conftest import FIXTURES, ROOT
-from test_gpu_longkin import generated_long_chain, generated_revolute_chain
+from _arrays import EPS, _dev, _host, _inf, _inputs, _solve
+from _chains import CHAINS, GRAV, _chain, _pair
+from _references import _solver_bound_check
+from rosdyn_amd.urdf_gen import generated_revolute_chain
 
 pytestmark = pytest.mark.gpu
-GRAV = (0.0, 0.0, -9.806)
-EPS = np.finfo(np.float64).eps
-PERMUTED_12 = ["j13", "j0", "j9", "j4", "j16", "j1", "j7", "j19", "j3", "j10", "j6", "j12"]
-
-FILES = {
-    "ur10_like": ("ur10_like.urdf", "base_link", "tool0"),
-    "ur10_public": ("ur10_public.urdf", "base_link", "tool0"),
-    "panda_like": ("panda_like.urdf", "link0", "hand"),
-    "mixed_joints": ("mixed_joints.urdf", "world", "tip"),
-    "ur10_public_long": ("ur10_public_long.urdf", "base_link", "tcp"),
-    "planar_2r": ("planar_2r.urdf", "base", "l2"),
-}
-SWEPT = list(FILES) + ["rev%d" % k for k in range(1, 11)]
-CHUNKED = ["rev14", "rev20", "rev32", "gen20", "gen32", "gen20_permuted"]
-CHAINS = SWEPT + CHUNKED
-
-
-def _spec(name):
-    if name in FILES:
-        f, base, tool = FILES[name]
-        return os.path.join(FIXTURES, f), base, tool, None
-    if name.startswith("rev"):
-        nj = int(name[3:])
-        return generated_revolute_chain(nj, 1000 + nj), "l0", "l%d" % nj, None
-    if name == "gen32":
-        return generated_long_chain(32, 3232), "l0", "l32", None
-    return generated_long_chain(20, 2020), "l0", "l20", (PERMUTED_12 if name == "gen20_permuted" else None)
-
-
-def _pair(name):
-    from oracle.oracle import OracleChain
-    from rosdyn_amd import Chain
-    xml, base, tool, inputs = _spec(name)
-    chain, ref = Chain(xml, base, tool, GRAV), OracleChain(xml, base, tool, GRAV, input_joint_names=inputs)
-    if inputs:
-        assert chain.setInputJointsName(inputs)
-    assert chain.getActiveJointsNumber() == ref.n
-    return chain, ref
-
-
-def _chain(name):
-    from rosdyn_amd import Chain
-    xml, base, tool, inputs = _spec(name)
-    chain = Chain(xml, base, tool, GRAV)
-    if inputs:
-        assert chain.setInputJointsName(inputs)
-    return chain
-
-
-def _inputs(n, N, seed=77):
-    from rosdyn_amd.samples import uniform_pm1
-    return uniform_pm1(seed, (N, n)), uniform_pm1(seed + 1, (N, n)), 50.0 * uniform_pm1(seed + 2, (N, n))
-
-
-def _dev(torch, x, layout):
-    return torch.from_numpy(np.ascontiguousarray(x.T if layout == "element" else x)).cuda()
-
-
-def _host(t, layout):
-    a = t.cpu().numpy()
-    return np.moveaxis(a, -1, 0) if layout == "element" else a
-
-
-def _solve(torch, chain, q, dq, tau, layout, **kw):
-    ddq, st = chain.getJointAcceleration(_dev(torch, q, layout), _dev(torch, dq, layout), _dev(torch, tau, layout), layout=layout, **kw)
-    return _host(ddq, layout), st.cpu().numpy()
-
-
-def _inf(x):
-    return np.abs(x).reshape(len(x), -1).max(axis=1)
-
-
-def _solver_bound_check(ddq, M, h, tau, what):
-    ddq_host = np.linalg.solve(M, (tau - h)[:, :, None])[:, :, 0]
-    cond = np.linalg.cond(M)
-    ratio = _inf(ddq - ddq_host) / (EPS * cond * np.maximum(1.0, _inf(ddq_host)))
-    print("%s: solver ratio max %.3g (bound 64), cond2 %.3g .. %.3g" % (what, ratio.max(), cond.min(), cond.max()))
-    assert (ratio <= 64.0).all(), (what, float(ratio.max()), int(np.argmax(ratio)))
 
 
 @pytest.mark.parametrize("name", CHAINS)

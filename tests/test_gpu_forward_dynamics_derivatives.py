@@ -37,54 +37,15 @@ import numpy as np
 import pytest
 
 from conftest import FIXTURES, ROOT
-from test_gpu_forward_dynamics import GRAV, _chain, _dev, _host, _inf, _inputs, _pair
-from test_gpu_longkin import generated_revolute_chain
-from test_gpu_torque_derivatives import _input_types, _mat, _reference
+from _arrays import DERIVATIVE_NAMES as NAMES, _derivatives_call as _call, _dev, _host, _inputs
+from _chains import GRAV, _chain, _pair
+from _components import MAX_VELOCITY, MIN_VELOCITY, _pin_the_closed_form_to_the_oracle, _set, _slopes, _specs
+from _references import _derivative_residual_ratios as _residual_ratios, _input_types
+from rosdyn_amd.urdf_gen import generated_revolute_chain
 
 pytestmark = pytest.mark.gpu
-FRICTION1, FRICTION2, SPRING = 0, 1, 2
-MIN_VELOCITY, MAX_VELOCITY = 0.3, 0.8   # Dq uniform in +-1: about 30 % of the entries in the band, 20 % saturated
-NAMES = ("dq", "dv", "dtau")
 # worst err(2^-7) / scale of the oracle's own directional check, this module's inputs (the docstring's table)
 DIRECTIONAL_WORST = {"ur10_public": 3.82e-5, "mixed_joints": 1.02e-4, "panda_like": 2.26e-3, "rev14": 1.82e-4, "gen20": 6.87e-4}
-
-
-def _call(torch, chain, q, dq, tau, layout, want=NAMES, **kw):
-    """host arrays: ddq (N, n), status (N,), then the wanted matrices as (N, n, n) with [s, i, k] = d DDq_i / d x_k"""
-    out = chain.getJointAccelerationDerivatives(_dev(torch, q, layout), _dev(torch, dq, layout), _dev(torch, tau, layout), layout=layout,
-                                                want=want, **kw)
-    return (_host(out[0], layout), out[1].cpu().numpy()) + tuple(_mat(t, layout) for t in out[2:])
-
-
-def _norm_inf(M):
-    return np.abs(M).sum(axis=2).max(axis=1)
-
-
-def _residual_ratios(ref, types, q, dq, ddq, Xq, Xv, Minv, slopes=None, cached=None):
-    """worst ratio residual / scale per output over the samples given, and the construction gap of the reference.
-    cached: None, or what test_gpu_forward_dynamics_vjp._cached_reference returns for these very (q, dq, ddq) -- (M_ref, Dq_ref, Dv_ref,
-    tau_ref, gscale), its construction gap asserted there -- so that the reference is computed once for both modules' residuals."""
-    N, n = q.shape
-    if cached is None:
-        Dq_ref, Dv_ref, tau_ref, gap = _reference(ref, types, q, dq, ddq)
-        gscale = np.maximum(_inf(Dq_ref), _inf(Dv_ref)) + _inf(tau_ref)
-        assert (gap <= 1e-12 * gscale).all(), ("spectral reference, 8 against 16 points", float((gap / gscale).max()))
-        M = ref.joint_inertia(q)
-    else:
-        M, Dq_ref, Dv_ref, tau_ref = cached[:4]
-        Dq_ref, Dv_ref = Dq_ref.copy(), Dv_ref.copy()
-    if slopes is not None:
-        idx = np.arange(n)
-        Dq_ref[:, idx, idx] += slopes[0]
-        Dv_ref[:, idx, idx] += slopes[1]
-    mn = _norm_inf(M)
-    out = {}
-    for what, X, D in (("dddq_dq", Xq, Dq_ref), ("dddq_dv", Xv, Dv_ref)):
-        res = _inf(np.einsum("sij,sjk->sik", M, X) + D)
-        out[what] = float((res / (mn * _inf(X) + _inf(D) + _inf(tau_ref))).max())
-    res = _inf(np.einsum("sij,sjk->sik", M, Minv) - np.eye(n)[None])
-    out["minv"] = float((res / (mn * _inf(Minv) + 1.0)).max())
-    return out
 
 
 ORACLE_CHAINS = ["planar_2r", "rev1", "mixed_joints", "ur10_public", "panda_like", "ur10_public_long", "rev8", "rev10", "rev14",
@@ -114,61 +75,6 @@ def test_against_the_oracle_in_residual_form(name, N, layout):
 
 
 # ---- 2. components
-def _specs(n):
-    """(type, joint, min_velocity, max_velocity, parameters) in list order: two friction components and a spring on joint 0, a FRICTION2 on
-    the last input joint, a spring on joint 1"""
-    specs = [(FRICTION1, 0, MIN_VELOCITY, MAX_VELOCITY, (2.0, 1.5, 0.0)),
-             (FRICTION2, n - 1, MIN_VELOCITY, MAX_VELOCITY, (1.0, 0.8, -0.6)),
-             (SPRING, 1, 0.0, 0.0, (3.0, -0.4, 0.0)),
-             (SPRING, 0, 0.0, 0.0, (-1.5, 0.3, 0.0)),
-             (FRICTION2, 0, MIN_VELOCITY, MAX_VELOCITY, (0.5, 0.2, 0.4))]
-    return specs
-
-
-def _set(specs, n):
-    from rosdyn_amd.components import ComponentSet
-    return ComponentSet([dict(type=t, joint=j, min_velocity=lo, max_velocity=hi, parameters=list(p)) for t, j, lo, hi, p in specs], n)
-
-
-def _slopes(specs, q, dq):
-    """closed form: (d tau_c / d q, d tau_c / d dq), each (N, n) -- the diagonals"""
-    sq, sv = np.zeros_like(q), np.zeros_like(dq)
-    for ty, j, lo, hi, p in specs:
-        if ty == SPRING:
-            sq[:, j] += p[0]
-            continue
-        x = dq[:, j]
-        w = np.clip(x, -hi, hi)
-        dw = (np.abs(x) < hi).astype(float)
-        band = np.abs(w) < lo
-        sg = np.where(band, w / lo, np.sign(w))
-        dsg = np.where(band, 1.0 / lo, 0.0)
-        s = p[0] * dsg + p[1]
-        if ty == FRICTION2:
-            s = s + p[2] * (2.0 * w * sg + w * w * dsg)
-        sv[:, j] += dw * s
-    return sq, sv
-
-
-def _pin_the_closed_form_to_the_oracle(specs, n, q, dq):
-    from oracle.oracle import components_regressor
-    h = 2.0 ** -10
-    tau_c = lambda qq, vv: components_regressor(specs, n, qq, vv)[1]
-    stencil = lambda f: (-f(2 * h) + 8.0 * f(h) - 8.0 * f(-h) + f(-2 * h)) / (12.0 * h)
-    num_q = stencil(lambda d: tau_c(q + d, dq))
-    num_v = stencil(lambda d: tau_c(q, dq + d))
-    sq, sv = _slopes(specs, q, dq)
-    big = np.abs(tau_c(q, dq)).max()
-    assert (np.abs(num_q - sq) <= 1e-11 * (np.abs(sq) + big / h)).all()
-    far = np.ones_like(dq, dtype=bool)
-    for kink in (-MAX_VELOCITY, -MIN_VELOCITY, MIN_VELOCITY, MAX_VELOCITY):
-        far &= np.abs(dq - kink) >= 2.0 ** -8
-    left_out = 1.0 - far.mean()
-    err = np.abs(num_v - sv) / (np.abs(sv) + big / h)
-    print("closed form against the oracle's stencil: worst ratio %.3g (bound 1e-11), %.2f %% of the entries left out (cap 5 %%)"
-          % (err[far].max(), 100.0 * left_out))
-    assert left_out <= 0.05
-    assert (err[far] <= 1e-11).all()
 
 
 @pytest.mark.parametrize("name", ["ur10_public", "mixed_joints", "rev14"])

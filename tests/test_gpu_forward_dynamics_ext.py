@@ -12,85 +12,16 @@ Yardsticks (each bound holds per sample, no sample is excused):
                           + |tau_E|_inf): the residual test of test_gpu_forward_dynamics.py with the wrench torque in the scale.  This pins the
                           reference's wrench convention, twist-form transform included."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
-from conftest import FIXTURES
-from test_gpu_forward_dynamics import EPS, FILES, GRAV, _chain, _dev, _host, _inf, _pair, _solve, _spec
-from test_gpu_rollout import TAU_SCALE, _inputs as _rollout_inputs
-from test_gpu_rollout_components import _cpair, _set, _specs
+from _arrays import LAYOUTS, SIZES, _dev, _dev_w, _inf, _solve, _state, _wrenches
+from _chains import WRENCH_CHAINS as CHAINS, _chain, _trio
+from _components import _named_components as _components
+from _references import _bound, _tau_e
 
 pytestmark = pytest.mark.gpu
-# planar_2r: the smallest chain; ur10_like, panda_like: 6 and 7 joints; mixed_joints: prismatic joints; ur10_public: fixed head and tail links
-# inside a swept chain, the tool a fixed link; ur10_permuted: input order differs from chain order; rev10: the largest register kernel;
-# ur10_public_long: a reduced companion without wrenches, the chunked route on the original chain with them; rev14, gen20_permuted: the
-# chunked route, permuted
-CHAINS = ["planar_2r", "ur10_like", "panda_like", "mixed_joints", "ur10_public", "ur10_permuted", "rev10", "ur10_public_long", "rev14",
-          "gen20_permuted"]
-SCALE = dict(TAU_SCALE, ur10_permuted=TAU_SCALE["ur10_like"], ur10_public=TAU_SCALE["ur10_like"])
-SIZES = (1, 63, 64, 65, 200)
-LAYOUTS = ("sample", "element")
-
-
-def _trio(name, oracle=False):
-    """(chain, oracle chain or None, the same chain with zero gravity)"""
-    from rosdyn_amd import Chain
-    if name == "ur10_permuted":
-        chain, ref = _cpair(name, oracle)
-        f, base, tool = FILES["ur10_like"]
-        xml, inputs = os.path.join(FIXTURES, f), chain.getActiveJointsName()
-    else:
-        xml, base, tool, inputs = _spec(name)
-        chain, ref = _pair(name) if oracle else (_chain(name), None)
-    chain0 = Chain(xml, base, tool, (0.0, 0.0, 0.0))
-    if inputs:
-        assert chain0.setInputJointsName(inputs)
-    assert chain0.getActiveJointsName() == chain.getActiveJointsName() and chain0.getLinksName() == chain.getLinksName()
-    return chain, ref, chain0
-
-
-def _state(name, n, N, seed):
-    """q, dq in +-1, tau in +- the chain's torque scale: test_gpu_rollout.py's inputs, one step of them"""
-    key = name if name in TAU_SCALE else "ur10_like"
-    q, dq, tau = _rollout_inputs(key, n, N, 1, seed=seed)
-    return q, dq, tau[0]
-
-
-def _wrenches(name, N, L, seed):
-    """(N, L, 6), force and torque entries uniform in +-1 times the chain's torque scale"""
-    from rosdyn_amd.samples import uniform_pm1
-    return SCALE[name] * uniform_pm1(seed, (N, L * 6)).reshape(N, L, 6)
-
-
-def _dev_w(torch, W, layout):
-    """host (N, L, 6) or (N, 6) -> the device tensor of the layout: (N, L, 6) / (L * 6, N), (N, 6) / (6, N)"""
-    flat = W.reshape(len(W), -1)
-    if layout == "element":
-        return torch.from_numpy(np.ascontiguousarray(flat.T)).cuda()
-    return torch.from_numpy(np.ascontiguousarray(W)).cuda()
-
-
-def _tau_e(torch, chain0, q, W):
-    """the library's own wrench torque at host arrays: getJointTorqueExt(q, 0, 0, W) on the zero-gravity chain"""
-    tq = _dev(torch, q, "sample")
-    z = torch.zeros_like(tq)
-    return chain0.getJointTorqueExt(tq, z, z, _dev_w(torch, W, "sample")).cpu().numpy()
-
-
-def _bound(torch, chain, q, dq, tau, tau_e, ddq):
-    """64 eps (cond2(M) max(1, |ddq|_inf) + |M^-1|_2 (|tau|_2 + |h|_2 + |tau_E|_2)) per sample, M and h the library's own"""
-    tq, tdq = _dev(torch, q, "sample"), _dev(torch, dq, "sample")
-    M = chain.getJointInertia(tq).cpu().numpy()
-    h = chain.getJointTorqueNonLinearPart(tq, tdq).cpu().numpy()
-    sv = np.linalg.svd(M, compute_uv=False)
-    l2 = lambda x: np.sqrt((x * x).sum(axis=1))
-    return 64.0 * EPS * (sv[:, 0] / sv[:, -1] * np.maximum(1.0, _inf(ddq)) + (l2(tau) + l2(h) + l2(tau_e)) / sv[:, -1])
-
-
-def _components(name, n):
-    return _set(_specs(name if name in TAU_SCALE or name == "ur10_permuted" else "ur10_like", n), n)
 
 
 def _ext_solve(torch, chain, q, dq, tau, W, layout, link=None, **kw):

@@ -14,62 +14,15 @@ diagonals of D_ref."""
 import numpy as np
 import pytest
 
-from test_gpu_forward_dynamics import GRAV, _chain, _dev, _host, _inf, _inputs, _pair
-from test_gpu_forward_dynamics_derivatives import MAX_VELOCITY, MIN_VELOCITY, _set, _slopes, _specs
-from test_gpu_torque_derivatives import _input_types, _reference
+from _arrays import VJP_NAMES as NAMES, _dev, _host, _inputs, _seed, _vjp_call as _call
+from _chains import GRAV, _chain, _pair
+from _components import MAX_VELOCITY, MIN_VELOCITY, _set, _slopes, _specs
+from _references import _cached_reference, _input_types, _vjp_residual_ratios as _residual_ratios
 
 pytestmark = pytest.mark.gpu
-NAMES = ("q", "dq", "tau")
 ORACLE_CHAINS = ["planar_2r", "rev1", "mixed_joints", "ur10_public", "panda_like", "ur10_public_long", "rev8", "rev10", "rev14",
                  "gen20_permuted", "rev32"]
 SIZES = (1, 63, 64, 65, 200)
-
-
-def _seed(n, N, seed=77):
-    from rosdyn_amd.samples import uniform_pm1
-    return uniform_pm1(seed + 3, (N, n))
-
-
-def _call(torch, chain, q, dq, tau, a, layout, want=NAMES + ("ddq",), **kw):
-    """host arrays: status (N,), then the wanted vectors as (N, n)"""
-    out = chain.getJointAccelerationVjp(_dev(torch, q, layout), _dev(torch, dq, layout), _dev(torch, tau, layout), _dev(torch, a, layout),
-                                        layout=layout, want=want, **kw)
-    return (out[0].cpu().numpy(),) + tuple(_host(t, layout) for t in out[1:])
-
-
-_REF = {}
-
-
-def _cached_reference(key, ref, types, q, dq, ddq):
-    """the oracle's M, D and tau at the library's ddq: computed once per (chain, inputs) and shared by the layouts (the same ddq bits)"""
-    if key not in _REF:
-        Dq_ref, Dv_ref, tau_ref, gap = _reference(ref, types, q, dq, ddq)
-        gscale = np.maximum(_inf(Dq_ref), _inf(Dv_ref)) + _inf(tau_ref)
-        assert (gap <= 1e-12 * gscale).all(), ("spectral reference, 8 against 16 points", float((gap / gscale).max()))
-        for x in (Dq_ref, Dv_ref, tau_ref, gscale):
-            x.setflags(write=False)
-        M = ref.joint_inertia(q)
-        M.setflags(write=False)
-        _REF[key] = (ddq.copy(), M, Dq_ref, Dv_ref, tau_ref, gscale)
-    assert np.array_equal(_REF[key][0], ddq), "the layouts must give the same ddq bits"
-    return _REF[key][1:]
-
-
-def _residual_ratios(cached, a, qb, vb, tb, slopes=None):
-    M, Dq_ref, Dv_ref, tau_ref, gscale = cached
-    n = a.shape[1]
-    if slopes is not None:
-        idx = np.arange(n)
-        Dq_ref, Dv_ref = Dq_ref.copy(), Dv_ref.copy()
-        Dq_ref[:, idx, idx] += slopes[0]
-        Dv_ref[:, idx, idx] += slopes[1]
-    mn = np.abs(M).sum(axis=2).max(axis=1)
-    out = {"tau_bar": float((_inf(np.einsum("sij,sj->si", M, tb) - a) / (mn * _inf(tb) + _inf(a))).max())}
-    l1 = np.abs(tb).sum(axis=1)
-    l1 = np.where(l1 > 0, l1, 1.0)
-    out["q_bar"] = float((_inf(qb + np.einsum("sik,si->sk", Dq_ref, tb)) / (gscale * l1)).max())
-    out["dq_bar"] = float((_inf(vb + np.einsum("sik,si->sk", Dv_ref, tb)) / (gscale * l1)).max())
-    return out
 
 
 # ---- 1. the oracle, residual form

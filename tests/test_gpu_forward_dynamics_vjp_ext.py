@@ -17,25 +17,16 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_gpu_forward_dynamics import _chain, _dev, _host, _inf
-from test_gpu_forward_dynamics_derivatives import _set, _slopes, _specs
-from test_gpu_forward_dynamics_ext import LAYOUTS, SIZES, _bound, _dev_w, _state, _tau_e, _trio, _wrenches
-from test_gpu_forward_dynamics_vjp import _seed
-from test_gpu_torque_derivatives import _input_types, _reference
+from _arrays import LAYOUTS, SIZES, _dev, _dev_w, _host, _host_w, _inf, _seed, _state, _wrenches
+from _chains import _chain, _trio
+from _components import _set, _slopes, _specs
+from _references import _WrenchTorque, _bound, _input_types, _reference, _tau_e, _wrench_matrix
 
 pytestmark = pytest.mark.gpu
 # planar_2r: the smallest chain; mixed_joints: prismatic joints; ur10_like, panda_like: 6 and 7 joints; ur10_public: fixed head and tail
 # links inside a swept chain, the tool a fixed link; ur10_permuted: input order differs from chain order; rev10: the largest register kernel
 CHAINS = ["planar_2r", "mixed_joints", "ur10_like", "panda_like", "ur10_public", "ur10_permuted", "rev10"]
 EVERY = ("q", "dq", "tau", "ext", "ddq")
-
-
-def _host_w(t, layout, N):
-    """device wrench-shaped tensor -> host (N, L, 6) or (N, 6)"""
-    a = t.cpu().numpy()
-    if layout == "element":
-        a = np.ascontiguousarray(a.T)
-    return a.reshape(N, -1, 6) if a.size > 6 * N else a.reshape(N, 6)
 
 
 def _call(torch, chain, q, dq, tau, a, W, layout, link=None, want=EVERY, **kw):
@@ -56,18 +47,6 @@ def _modes(W, L):
             Wl = np.zeros_like(W)
             Wl[:, link] = W[:, link]
             yield link, W[:, link], Wl
-
-
-class _WrenchTorque:
-    """the oracle's wrench torque tau_E(q) of fixed wrenches W in the shape of an oracle chain, for _reference"""
-
-    def __init__(self, ref, W):
-        self.ref, self.W = ref, W
-
-    def joint_torque(self, q, dq, ddq):
-        Wt = np.tile(self.W, (len(q) // len(self.W), 1, 1))
-        z = np.zeros_like(q)
-        return self.ref.joint_torque(q, z, z, ext=Wt) - self.ref.joint_torque(q, z, z)
 
 
 # ---- 1. the oracle, residual form
@@ -132,17 +111,6 @@ def test_against_the_oracle_in_residual_form(name, N, with_components):
 
 
 # ---- 2. ext_bar, exact linear duality
-def _wrench_matrix(torch, chain0, q, L):
-    """A[s, i, 6 l + e] = tau_E,i of the unit wrench e on link l: the library's own getJointTorqueExt on the zero-gravity chain"""
-    N, n = q.shape
-    tq = _dev(torch, q, "sample")
-    z = torch.zeros_like(tq)
-    A = np.zeros((N, n, 6 * L))
-    for col in range(6 * L):
-        U = torch.zeros((N, L, 6), dtype=torch.float64, device="cuda")
-        U[:, col // 6, col % 6] = 1.0
-        A[:, :, col] = chain0.getJointTorqueExt(tq, z, z, U).cpu().numpy()
-    return A
 
 
 @pytest.mark.parametrize("with_components", [False, True], ids=["plain", "components"])

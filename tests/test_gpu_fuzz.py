@@ -6,62 +6,10 @@ import os
 
 import numpy as np
 import pytest
+from _fuzz import FUZZ_OFFSET, random_chain_xml, random_long_chain_xml
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-11
-
-
-def _fmt(v):
-    return " ".join("%.17g" % float(x) for x in v)
-
-
-# RDYN_FUZZ_OFFSET=k shifts the seeds of the fuzzed chains (extended campaigns: tools/gpu_suite.sh runs the committed seeds)
-FUZZ_OFFSET = int(os.environ.get("RDYN_FUZZ_OFFSET", "0"))
-
-
-def random_chain_xml(seed):
-    rng = np.random.default_rng(seed)
-    nj = int(rng.integers(1, 11))
-    kinds = ["revolute", "continuous", "prismatic", "fixed", "floating", "planar"]
-    probs = [0.45, 0.15, 0.15, 0.15, 0.05, 0.05]
-    links, joints = ["<link name='L0'/>"], []
-    n_moving = 0
-    for i in range(nj):
-        kind = str(rng.choice(kinds, p=probs))
-        if i == nj - 1 and n_moving == 0:
-            kind = "revolute"                                   # at least one moveable joint
-        n_moving += kind in ("revolute", "continuous", "prismatic")
-        origin = ""
-        if rng.random() < 0.85:
-            origin = "<origin xyz='%s' rpy='%s'/>" % (_fmt(0.3 * rng.uniform(-1, 1, 3)), _fmt(rng.uniform(-3.1, 3.1, 3)))
-            if rng.random() < 0.15:
-                origin = "<origin xyz='%s'/>" % _fmt(0.3 * rng.uniform(-1, 1, 3))       # rpy missing
-        axis = ""
-        if rng.random() < 0.8:
-            axis = "<axis xyz='%s'/>" % _fmt(rng.uniform(-1, 1, 3) * rng.choice([1.0, 2.5]))   # not normalised
-        limit = ""
-        if kind in ("revolute", "prismatic") or rng.random() < 0.3:
-            limit = "<limit lower='%.17g' upper='%.17g' effort='50' velocity='2'/>" % (-rng.uniform(1.5, 3), rng.uniform(1.5, 3))
-        joints.append("<joint name='J%d' type='%s'><parent link='L%d'/><child link='L%d'/>%s%s%s</joint>"
-                      % (i, kind, i, i + 1, origin, axis, limit))
-        inertial = ""
-        if rng.random() < 0.85:
-            B = rng.normal(size=(3, 3))
-            I = B @ B.T * 0.01 + 0.01 * np.eye(3)
-            io = "<origin xyz='%s' rpy='%s'/>" % (_fmt(0.1 * rng.uniform(-1, 1, 3)), _fmt(rng.uniform(-3, 3, 3))) if rng.random() < 0.8 else ""
-            inertial = ("<inertial>%s<mass value='%.17g'/><inertia ixx='%.17g' ixy='%.17g' ixz='%.17g' iyy='%.17g' iyz='%.17g' "
-                        "izz='%.17g'/></inertial>" % (io, rng.uniform(0.2, 5), I[0, 0], I[0, 1], I[0, 2], I[1, 1], I[1, 2], I[2, 2]))
-        links.append("<link name='L%d'>%s</link>" % (i + 1, inertial))
-        if rng.random() < 0.25:                                  # a side branch hanging off the chain
-            links.append("<link name='S%d'><inertial><mass value='1'/><inertia ixx='1' ixy='0' ixz='0' iyy='1' iyz='0' izz='1'/></inertial></link>" % i)
-            joints.append("<joint name='B%d' type='revolute'><parent link='L%d'/><child link='S%d'/><axis xyz='0 1 0'/>"
-                          "<limit lower='-1' upper='1' effort='1' velocity='1'/></joint>" % (i, i, i))
-    order = rng.permutation(len(links) + len(joints))           # element order in the file must not matter
-    elems = links + joints
-    body = "".join(elems[k] for k in order)
-    lo = int(rng.integers(0, max(1, nj // 3 + 1)))               # chain = a sub-path of the tree
-    hi = nj
-    return "<robot name='fuzz%d'>%s</robot>" % (seed, body), "L%d" % lo, "L%d" % hi, rng
 
 
 @pytest.mark.parametrize("seed", range(64))
@@ -266,31 +214,6 @@ def test_extreme_input_ranges(scale_q, scale_dq, scale_ddq):
     close(chain.getJointInertia(tq).cpu().numpy().transpose(0, 2, 1), ref.joint_inertia(q), "M")
     close(chain.getTransformations(tq).cpu().numpy().transpose(0, 1, 3, 2), ref.fk(q), "T")
     close(chain.getDTwist(tq, tdq, tddq).cpu().numpy(), ref.dtwist(q, dq, ddq), "dtwist")
-
-
-def random_long_chain_xml(seed):
-    """2..16 chain joints, at most 7 of them moving (revolute / continuous / prismatic), fixed frames anywhere -- head, middle, tail --
-    so that chains LONGER than the kernels sweep (> 10 joints) and every reduced-companion shape occur."""
-    rng = np.random.default_rng(seed)
-    nj = int(rng.integers(2, 17))
-    n_move = int(rng.integers(2, min(7, nj) + 1))
-    moving = set(rng.choice(nj, size=n_move, replace=False).tolist())
-    links, joints = ["<link name='L0'/>"], []
-    for i in range(nj):
-        kind = str(rng.choice(["revolute", "continuous", "prismatic"], p=[0.6, 0.2, 0.2])) if i in moving else str(rng.choice(["fixed", "floating", "planar"], p=[0.8, 0.1, 0.1]))
-        origin = "<origin xyz='%s' rpy='%s'/>" % (_fmt(0.3 * rng.uniform(-1, 1, 3)), _fmt(rng.uniform(-3.1, 3.1, 3))) if rng.random() < 0.9 else ""
-        axis = "<axis xyz='%s'/>" % _fmt(rng.uniform(-1, 1, 3)) if rng.random() < 0.85 else ""
-        limit = "<limit lower='-2' upper='2' effort='50' velocity='2'/>" if kind in ("revolute", "prismatic") else ""
-        joints.append("<joint name='J%d' type='%s'><parent link='L%d'/><child link='L%d'/>%s%s%s</joint>" % (i, kind, i, i + 1, origin, axis, limit))
-        inertial = ""
-        if rng.random() < 0.8:
-            B = rng.normal(size=(3, 3))
-            I = B @ B.T * 0.01 + 0.01 * np.eye(3)
-            io = "<origin xyz='%s' rpy='%s'/>" % (_fmt(0.1 * rng.uniform(-1, 1, 3)), _fmt(rng.uniform(-3, 3, 3)))
-            inertial = ("<inertial>%s<mass value='%.17g'/><inertia ixx='%.17g' ixy='%.17g' ixz='%.17g' iyy='%.17g' iyz='%.17g' "
-                        "izz='%.17g'/></inertial>" % (io, rng.uniform(0.2, 5), I[0, 0], I[0, 1], I[0, 2], I[1, 1], I[1, 2], I[2, 2]))
-        links.append("<link name='L%d'>%s</link>" % (i + 1, inertial))
-    return "<robot name='long%d'>%s%s</robot>" % (seed, "".join(links), "".join(joints)), "L0", "L%d" % nj, rng
 
 
 @pytest.mark.parametrize("seed", range(24))

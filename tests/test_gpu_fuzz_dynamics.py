@@ -21,140 +21,14 @@ Bounds, each per sample:
   input subsets      the full chain with the unselected joints held at q = dq = 0 (forward dynamics: and at ddq = 0, by the oracle's
                      holding torque) gives the subset chain's outputs on the selected joints: the same bits for the derivatives, the
                      64 eps cond2 solver bound for ddq."""
-import functools
-import re
-
 import numpy as np
 import pytest
 
-from test_gpu_forward_dynamics import EPS, _dev, _host, _inf, _solver_bound_check
-from test_gpu_fuzz import FUZZ_OFFSET, random_chain_xml
-from test_gpu_rollout import _euler_residual_check, _np_rollout, _oracle_fd, _rollout
-from test_gpu_torque_derivatives import PRISMATIC, REVOLUTE, _input_types, _mat, _reference
+from _arrays import EPS, INTEGRATORS, PRISMATIC, _dev, _host, _inf, _mat, _rollout
+from _fuzz import DT, FUZZ_OFFSET, N, T, _chain, _get, _regular_neighbour, case, classify, reference_derivatives, rollout_bound, seed_class
+from _references import _euler_residual_check, _input_types, _solver_bound_check
 
 pytestmark = pytest.mark.gpu
-N = 257
-T, DT = 4, 1e-3
-INTEGRATORS = ["semi_implicit_euler", "rk4"]
-REGULAR_LAMBDA, SINGULAR_DIAGONAL = 1e-8, 1e-14
-
-
-class Case(object):
-    """One fuzzed chain as test_fuzzed_chain_all_entry_points builds it (the same draws from the same generator), oracle side only."""
-
-    def __init__(self, seed, inertia_scale=1.0):
-        from oracle.oracle import OracleChain
-        from rosdyn_amd.samples import uniform_pm1
-        self.seed = seed
-        self.data_seed = data_seed = 1000 + seed + FUZZ_OFFSET
-        self.xml, self.base, self.tool, rng = random_chain_xml(data_seed)
-        if inertia_scale != 1.0:   # every mass and every inertia tensor times a power of two: M, h and the torques scale with it
-            self.xml = re.sub(r"\b(value|ixx|ixy|ixz|iyy|iyz|izz)='([^']+)'", lambda m: "%s='%.17g'" % (m.group(1), float(m.group(2)) * inertia_scale),
-                              self.xml)
-        self.grav = tuple(rng.uniform(-10, 10, 3))
-        self.full = OracleChain(self.xml, self.base, self.tool, self.grav)
-        self.inputs = None
-        if self.full.n == 0:
-            return
-        if seed % 2 == 1 and self.full.n >= 2:                       # permuted subset of the moveable joints
-            names = list(self.full.spec.moveable)
-            k = int(rng.integers(1, len(names) + 1))
-            self.inputs = [names[i] for i in rng.permutation(len(names))[:k]]
-        self.ref = OracleChain(self.xml, self.base, self.tool, self.grav, input_joint_names=self.inputs)
-        self.layout = "element" if seed % 3 == 0 else "sample"
-        n = self.n = self.ref.n
-        self.q, self.dq = uniform_pm1(data_seed, (N, n)), uniform_pm1(data_seed + 1, (N, n))
-        self.M = self.ref.joint_inertia(self.q)
-        self.h = self.ref.joint_torque(self.q, self.dq, np.zeros_like(self.q))
-        self.regular, self.singular, self.lam = classify(self.M)
-        # forward dynamics: accelerations of order 50 on regular samples
-        self.a = 50.0 * uniform_pm1(data_seed + 2, (N, n))
-        self.tau = np.einsum("sij,sj->si", self.M, self.a) + self.h if self.regular.all() else uniform_pm1(data_seed + 2, (N, n))
-        # derivatives
-        self.ddq = 3.0 * uniform_pm1(data_seed + 3, (N, n))
-        # rollouts: torques built from the reference at the start state keep |ddq| of order 1e2 over the four steps
-        self.a_seq = 100.0 * uniform_pm1(data_seed + 4, (T, N, n))
-        if self.regular.all():
-            self.tau_seq = np.einsum("sij,tsj->tsi", self.M, self.a_seq) + self.h[None]
-        else:
-            self.tau_seq = uniform_pm1(data_seed + 4, (T, N, n))
-
-    def oracle_types(self):
-        """rdyn_joint_type of every input joint from the oracle's reader (continuous joints are revolute to the kernels)"""
-        joints = self.ref.spec.joints
-        return [PRISMATIC if joints[c].urdf_type == 2 else REVOLUTE for c in self.ref.spec.input_chain_index]
-
-    def positions_in_full(self):
-        """index of every selected joint among the moveable joints of the full chain, in input order"""
-        names = list(self.full.spec.moveable)
-        return [names.index(nm) for nm in self.inputs]
-
-    def scatter(self, x):
-        """(N, n) of the subset chain -> (N, n_full) of the full chain, 0 at the unselected joints"""
-        out = np.zeros((len(x), self.full.n))
-        out[:, self.positions_in_full()] = x
-        return out
-
-
-@functools.lru_cache(maxsize=None)
-def case(seed, inertia_scale=1.0):
-    return Case(seed, inertia_scale)
-
-
-def classify(M):
-    """(regular, singular, lam) per sample from the oracle's inertia matrices alone"""
-    diag = np.einsum("sii->si", M)
-    trace = diag.sum(axis=1)
-    lam = np.full(len(M), -np.inf)
-    pos = trace > 0.0
-    lam[pos] = np.linalg.eigvalsh(M[pos]).min(axis=1) / trace[pos]
-    regular = pos & (lam >= REGULAR_LAMBDA)
-    singular = (trace == 0.0) | (diag.min(axis=1) <= SINGULAR_DIAGONAL * trace)
-    return regular, singular, lam
-
-
-def seed_class(c):
-    """"regular" / "singular" when every sample of the seed is; anything else fails (no sample is excused)"""
-    assert (c.regular | c.singular).all(), ("samples in neither class", int((~(c.regular | c.singular)).sum()), float(c.lam.min()))
-    assert c.regular.all() or c.singular.all(), ("a seed with samples of both classes", int(c.regular.sum()), int(c.singular.sum()))
-    return "regular" if c.regular.all() else "singular"
-
-
-def reference_derivatives(c):
-    """_reference of test_gpu_torque_derivatives.py on the case's inputs, computed once per seed"""
-    if not hasattr(c, "_deriv"):
-        c._deriv = _reference(c.ref, c.oracle_types(), c.q, c.dq, c.ddq)
-    return c._deriv
-
-
-def rollout_bound(c, integrator):
-    """(bound, dev, qr, dqr): the definition above MULTI_STEP in test_gpu_rollout.py at run time.  dev = the largest deviation of the end
-    state between the plain oracle rollout and one whose every ddq is multiplied by (1 + 1e-11 xi), xi uniform in +-1 from a generator
-    seeded by the test seed, relative to max(1, |q|_inf, |dq|_inf) of the sample; bound = 8 dev."""
-    key = "_rollout_" + integrator
-    if not hasattr(c, key):
-        qr, dqr = _np_rollout(_oracle_fd(c.ref), c.q, c.dq, c.tau_seq, DT, T, integrator)
-        qp, dqp = _np_rollout(_oracle_fd(c.ref, perturb=np.random.default_rng(c.data_seed)), c.q, c.dq, c.tau_seq, DT, T, integrator)
-        scale = np.maximum(1.0, np.maximum(_inf(qr), _inf(dqr)))
-        dev = float((np.maximum(_inf(qp - qr), _inf(dqp - dqr)) / scale).max())
-        setattr(c, key, (8.0 * dev, dev, qr, dqr))
-    return getattr(c, key)
-
-
-def _get(seed):
-    c = case(seed)
-    if c.full.n == 0:
-        pytest.skip("sub-path without a moveable joint")
-    return c
-
-
-def _chain(c, subset=True):
-    from rosdyn_amd import Chain
-    chain = Chain(c.xml, c.base, c.tool, c.grav)
-    if subset and c.inputs is not None:
-        assert chain.setInputJointsName(c.inputs)
-    assert chain.getActiveJointsNumber() == (c.ref.n if subset else c.full.n)
-    return chain
 
 
 def _fd(torch, chain, q, dq, tau, layout):
@@ -175,15 +49,6 @@ def _forward_dynamics_regular(torch, c, chain, what):
     h = chain.getJointTorqueNonLinearPart(tq, tdq).cpu().numpy()
     _solver_bound_check(ddq, M, h, c.tau, what)
     return ddq
-
-
-def _regular_neighbour(seed):
-    """the next seed whose chain is regular: evaluated after a singular one, in the same process"""
-    for k in range(1, 64):
-        c = case((seed + k) % 64)
-        if c.full.n > 0 and c.regular.all():
-            return c
-    raise AssertionError("no regular seed")
 
 
 @pytest.mark.parametrize("seed", range(64))

@@ -33,57 +33,16 @@ The exact reference costs a fraction of a second per seed at these sizes, so all
 import numpy as np
 import pytest
 
-import test_gpu_forward_dynamics_derivatives as fdd
-import test_gpu_forward_dynamics_vjp as fdv
-from test_gpu_forward_dynamics import EPS, _dev, _host, _inf, _solve
-from test_gpu_fuzz_dynamics import DT, INTEGRATORS, N, T, Case, _chain, _get, _regular_neighbour, case, classify, seed_class   # noqa: F401
-from test_gpu_rollout import _dev_seq, _np_rollout, _rollout
-from test_gpu_rollout_adjoint import _adjoint, _forward, _lib_abs_vjp, _lib_fd, _lib_vjp, _np_step_adjoint, _seeds
-from test_gpu_rollout_components import _oracle_fd_c
-from test_gpu_torque_derivatives import _input_types
+from _arrays import (DERIVATIVE_NAMES, EPS, INTEGRATORS, VJP_NAMES, _adjoint, _derivatives_call, _dev,
+                     _dev_seq, _forward, _host, _inf, _rollout, _seeds, _solve, _vjp_call)
+from _components import _set, _slopes as _component_slopes
+from _fuzz import DT, N, T, _chain, _get, _regular_neighbour, component_torque_ref, fuzz_specs, rollout_bound_c, seed_class
+from _references import (_cached_reference, _derivative_residual_ratios, _input_types, _lib_abs_vjp,
+                         _lib_fd, _lib_vjp, _np_step_adjoint, _vjp_residual_ratios)
 
 pytestmark = pytest.mark.gpu
 COMPONENTS = pytest.mark.parametrize("with_components", [False, True], ids=["plain", "components"])
 SEEDS = pytest.mark.parametrize("seed", range(64))
-
-
-def component_scale(c):
-    """s: the largest power of two not above the smallest diagonal entry of M_ref over the samples and joints (1 when that is not
-    positive): component torques and slopes of the order of the lightest joint's inertia, whatever the chain weighs"""
-    d = float(np.einsum("sii->si", c.M).min())
-    return 2.0 ** np.floor(np.log2(d)) if d > 0.0 else 1.0
-
-
-def fuzz_specs(c):
-    """(type, joint, min_velocity, max_velocity, parameters) in list order for the seed's chain, see the module docstring"""
-    if not hasattr(c, "_specs"):
-        n, s = c.n, component_scale(c)
-        five = fdd._specs(n)   # FRICTION1 on 0, FRICTION2 on n - 1, SPRING on 1, SPRING on 0, FRICTION2 on 0
-        keep = [True, n >= 2, n >= 3, True, True]
-        c._specs = [(ty, j, lo, hi, tuple(s * p for p in par)) for (ty, j, lo, hi, par), k in zip(five, keep) if k]
-        assert all(0 <= sp[1] < n for sp in c._specs)
-    return c._specs
-
-
-def rollout_bound_c(c, integrator):
-    """(bound, dev, qr, dqr): rollout_bound of test_gpu_fuzz_dynamics.py over the oracle's forward dynamics with the components of
-    fuzz_specs(c): dev = the largest deviation of the end state between the plain oracle rollout and one whose every ddq is multiplied by
-    (1 + 1e-11 xi), xi uniform in +-1 from a generator seeded by the test seed, relative to max(1, |q|_inf, |dq|_inf); bound = 8 dev."""
-    key = "_rollout_c_" + integrator
-    if not hasattr(c, key):
-        specs = fuzz_specs(c)
-        qr, dqr = _np_rollout(_oracle_fd_c(c.ref, specs), c.q, c.dq, c.tau_seq, DT, T, integrator)
-        qp, dqp = _np_rollout(_oracle_fd_c(c.ref, specs, perturb=np.random.default_rng(c.data_seed)), c.q, c.dq, c.tau_seq, DT, T, integrator)
-        scale = np.maximum(1.0, np.maximum(_inf(qr), _inf(dqr)))
-        dev = float((np.maximum(_inf(qp - qr), _inf(dqp - dqr)) / scale).max())
-        setattr(c, key, (8.0 * dev, dev, qr, dqr))
-    return getattr(c, key)
-
-
-def component_torque_ref(c):
-    """tau_c_ref (N, n) at the seed's (q, dq) from the oracle"""
-    from oracle.oracle import components_regressor
-    return components_regressor(fuzz_specs(c), c.n, c.q, c.dq)[1]
 
 
 def _what(c, *more):
@@ -91,7 +50,7 @@ def _what(c, *more):
 
 
 def _cs(c, with_components=True):
-    return fdd._set(fuzz_specs(c), c.n) if with_components else None
+    return _set(fuzz_specs(c), c.n) if with_components else None
 
 
 def _other(layout):
@@ -172,18 +131,18 @@ def _shared_reference(c, with_components, types, ddq):
     """(M_ref, Dq_ref, Dv_ref, tau_ref, gscale), read-only; asserts the construction gap (1e-12) when it builds the reference and, on
     every call, that ddq has the bits the reference was built at"""
     assert types == c.oracle_types()
-    return fdv._cached_reference(("fuzz", c.data_seed, bool(with_components)), c.ref, types, c.q, c.dq, ddq)
+    return _cached_reference(("fuzz", c.data_seed, bool(with_components)), c.ref, types, c.q, c.dq, ddq)
 
 
 def _slopes(c, with_components):
-    return fdd._slopes(fuzz_specs(c), c.q, c.dq) if with_components else None
+    return _component_slopes(fuzz_specs(c), c.q, c.dq) if with_components else None
 
 
 # ---- c. forward-dynamics derivatives
 def _derivatives_regular(torch, c, chain, with_components, what):
     cs = _cs(c, with_components)
     n = c.n
-    full = fdd._call(torch, chain, c.q, c.dq, c.tau, c.layout, components=cs)
+    full = _derivatives_call(torch, chain, c.q, c.dq, c.tau, c.layout, components=cs)
     ddq, st, Xq, Xv, Minv = full
     assert st.shape == (N,) and (st == 1).all(), np.unique(st)
     assert ddq.shape == (N, n) and all(X.shape == (N, n, n) and np.isfinite(X).all() for X in (Xq, Xv, Minv))
@@ -192,23 +151,23 @@ def _derivatives_regular(torch, c, chain, with_components, what):
     types = _input_types(chain)
     cached = _shared_reference(c, with_components, types, ddq)
     slopes = _slopes(c, with_components)
-    worst = fdd._residual_ratios(c.ref, types, c.q, c.dq, ddq, Xq, Xv, Minv, slopes=slopes, cached=cached)
+    worst = _derivative_residual_ratios(c.ref, types, c.q, c.dq, ddq, Xq, Xv, Minv, slopes=slopes, cached=cached)
     print("%s: worst residual ratio dddq_dq %.3g dddq_dv %.3g minv %.3g (bound 1e-11)" % (what, worst["dddq_dq"], worst["dddq_dv"], worst["minv"]))
     for k, r in worst.items():
         assert r <= 1e-11, (k, r)
     if with_components:
         # the slopes matter at this bound, and land on the right diagonal entry: without them the residual is far off
-        bare = fdd._residual_ratios(c.ref, types, c.q, c.dq, ddq, Xq, Xv, Minv, cached=cached)
+        bare = _derivative_residual_ratios(c.ref, types, c.q, c.dq, ddq, Xq, Xv, Minv, cached=cached)
         print("%s: without the slopes dddq_dq %.3g dddq_dv %.3g (must exceed 1e-6)" % (what, bare["dddq_dq"], bare["dddq_dv"]))
         must = [k for k, sl in zip(("dddq_dq", "dddq_dv"), slopes) if n >= 2 or np.abs(sl).max() > 0.0]
         assert must and all(bare[k] > 1e-6 for k in must), (must, bare)
     assert np.array_equal(Minv, np.swapaxes(Minv, 1, 2)), "minv: the same bits in both triangles"
     for mask in range(1, 7):
-        names = tuple(k for b, k in enumerate(fdd.NAMES) if mask >> b & 1)
-        part = fdd._call(torch, chain, c.q, c.dq, c.tau, c.layout, want=names, components=cs)
+        names = tuple(k for b, k in enumerate(DERIVATIVE_NAMES) if mask >> b & 1)
+        part = _derivatives_call(torch, chain, c.q, c.dq, c.tau, c.layout, want=names, components=cs)
         assert np.array_equal(part[0], ddq) and np.array_equal(part[1], st)
         for k, t in zip(names, part[2:]):
-            assert np.array_equal(t, full[2 + fdd.NAMES.index(k)]), (names, k)
+            assert np.array_equal(t, full[2 + DERIVATIVE_NAMES.index(k)]), (names, k)
 
 
 @SEEDS
@@ -222,8 +181,8 @@ def test_forward_dynamics_derivatives(seed, with_components):
     if kind == "regular":
         _derivatives_regular(torch, c, chain, with_components, what)
         return
-    for names in (fdd.NAMES, ("dv",)):
-        out = fdd._call(torch, chain, c.q, c.dq, c.tau, c.layout, want=names, components=_cs(c, with_components))
+    for names in (DERIVATIVE_NAMES, ("dv",)):
+        out = _derivatives_call(torch, chain, c.q, c.dq, c.tau, c.layout, want=names, components=_cs(c, with_components))
         assert out[1].shape == (N,) and (out[1] == -1).all(), np.unique(out[1])
         assert out[0].shape == (N, c.n) and np.isnan(out[0]).all()
         assert all(X.shape == (N, c.n, c.n) and np.isnan(X).all() for X in out[2:])
@@ -244,30 +203,30 @@ def test_forward_dynamics_vjp(seed, with_components):
     cs = _cs(c, with_components)
     what = _what(c, "components" if with_components else "plain")
     a = uniform_pm1(c.data_seed + 5, (N, c.n))
-    every = fdv.NAMES + ("ddq",)
-    full = fdv._call(torch, chain, c.q, c.dq, c.tau, a, c.layout, components=cs)
+    every = VJP_NAMES + ("ddq",)
+    full = _vjp_call(torch, chain, c.q, c.dq, c.tau, a, c.layout, components=cs)
     st, qb, vb, tb, ddq = full
     assert st.shape == (N,) and all(x.shape == (N, c.n) for x in full[1:])
     if kind == "singular":
         assert (st == -1).all(), np.unique(st)
         assert all(np.isnan(x).all() for x in full[1:])
-        other = fdv._call(torch, chain, c.q, c.dq, c.tau, a, _other(c.layout), want=("tau",), components=cs)
+        other = _vjp_call(torch, chain, c.q, c.dq, c.tau, a, _other(c.layout), want=("tau",), components=cs)
         assert (other[0] == -1).all() and np.isnan(other[1]).all()
         print("%s: singular, status -1 and NaN in every output on all %d samples" % (what, N))
         return
     assert (st == 1).all(), np.unique(st)
     assert all(np.isfinite(x).all() for x in full[1:])
     cached = _shared_reference(c, with_components, _input_types(chain), ddq)   # asserts: the derivative call's ddq bits
-    worst = fdv._residual_ratios(cached, a, qb, vb, tb, slopes=_slopes(c, with_components))
+    worst = _vjp_residual_ratios(cached, a, qb, vb, tb, slopes=_slopes(c, with_components))
     print("%s: worst residual ratio tau_bar %.3g q_bar %.3g dq_bar %.3g (bound 1e-11)" % (what, worst["tau_bar"], worst["q_bar"], worst["dq_bar"]))
     for k, r in worst.items():
         assert r <= 1e-11, (k, r)
     # the other layout: the same bits
-    for x, y in zip(full, fdv._call(torch, chain, c.q, c.dq, c.tau, a, _other(c.layout), components=cs)):
+    for x, y in zip(full, _vjp_call(torch, chain, c.q, c.dq, c.tau, a, _other(c.layout), components=cs)):
         assert np.array_equal(x, y)
     # tau_bar written over the seed, alone and with the other products: the same bits
     dev = lambda x: _dev(torch, x, c.layout)
-    for names in (("tau",), fdv.NAMES):
+    for names in (("tau",), VJP_NAMES):
         ta = dev(a)
         out = chain.getJointAccelerationVjp(dev(c.q), dev(c.dq), dev(c.tau), ta, layout=c.layout, want=names, out={"tau": ta}, components=cs)
         assert out[1 + names.index("tau")].data_ptr() == ta.data_ptr() and np.array_equal(out[0].cpu().numpy(), st)

@@ -8,10 +8,10 @@ import numpy as np
 import pytest
 
 from conftest import FIXTURES
-from test_gpu_longkin import generated_long_chain, generated_revolute_chain
+from _chains import WIDE_GRAV as GRAV, _chain_case, _ur6
+from rosdyn_amd.urdf_gen import generated_revolute_chain
 
 pytestmark = pytest.mark.gpu
-GRAV = (0.2, -0.3, -9.7)
 
 
 def _fro(a, b):
@@ -76,22 +76,6 @@ def test_gram_wide_matches_numpy(n_cols, with_b):
             assert _fro(cw.cpu().numpy(), cn.cpu().numpy()) <= 1e-13
 
 
-def _chain_case(case):
-    from oracle.oracle import OracleChain
-    from rosdyn_amd import Chain
-    inputs = None
-    if case.startswith("rev"):
-        nj = int(case[3:])
-        xml, tool = generated_revolute_chain(nj, 1000 + nj), "l%d" % nj
-    else:   # gen20_twelve_permuted: fixed joints and 12 input joints out of chain order
-        xml, tool = generated_long_chain(20, 2020), "l20"
-        inputs = ["j13", "j0", "j9", "j4", "j16", "j1", "j7", "j19", "j3", "j10", "j6", "j12"]
-    chain, ref = Chain(xml, "l0", tool, GRAV), OracleChain(xml, "l0", tool, GRAV, input_joint_names=inputs)
-    if inputs:
-        assert chain.setInputJointsName(inputs)
-    return chain, ref
-
-
 @pytest.mark.parametrize("case", ["rev12", "rev14", "rev20", "rev32", "gen20_twelve_permuted"])
 def test_regressor_gram_wide_matches_oracle(case):
     """A = regressor(q, dq, ddq).reshape(N n, P): A'A, A'tau, tau'tau for chains of 12 to 32 input joints, both input layouts, the
@@ -127,13 +111,6 @@ def test_regressor_gram_wide_matches_oracle(case):
     assert not Gz.abs().max().item() and not cz.abs().max().item() and not bbz.abs().max().item()
     chain.getRegressorGramWide(*empty, out=out, accumulate=True)
     assert all(_fro(x.cpu().numpy(), 2 * y.cpu().numpy()) <= 1e-15 for x, y in zip(out, first))
-
-
-def _ur6():
-    from oracle.oracle import OracleChain
-    from rosdyn_amd import Chain
-    path = os.path.join(FIXTURES, "ur10_like.urdf")
-    return Chain(path, "base_link", "wrist_3_link", GRAV), OracleChain(path, "base_link", "wrist_3_link", GRAV)
 
 
 @pytest.mark.parametrize("case", ["rev14_mixed", "ur6_26_friction"])

@@ -7,7 +7,7 @@ input joints); a numpy restatement of the whole loop (BVLS per update, the oracl
 import numpy as np
 import pytest
 
-from test_gpu_longkin import generated_long_chain, generated_revolute_chain
+from rosdyn_amd.urdf_gen import generated_long_chain, generated_revolute_chain
 
 pytestmark = pytest.mark.gpu
 WEIGHT = (1.0, 2.0, 0.5, 0.3, 1.5, 0.8)

@@ -4,30 +4,10 @@ import os
 
 import numpy as np
 import pytest
+from rosdyn_amd.urdf_gen import generated_short_chain
 
 pytestmark = pytest.mark.gpu
 GRAV = (0.3, -0.4, -9.7)
-
-
-def _chain_xml(nj, seed):
-    from rosdyn_amd.samples import uniform_pm1
-    r = uniform_pm1(seed, (nj + 1, 16))
-    links = ["<link name='l0'/>"]
-    joints = []
-    for i in range(nj):
-        k = r[i]
-        typ = "prismatic" if (i % 4 == 3) else "revolute"
-        joints.append(
-            "<joint name='j%d' type='%s'><parent link='l%d'/><child link='l%d'/>"
-            "<origin xyz='%.17g %.17g %.17g' rpy='%.17g %.17g %.17g'/><axis xyz='%.17g %.17g %.17g'/>"
-            "<limit lower='-3' upper='3' effort='10' velocity='2'/></joint>"
-            % (i, typ, i, i + 1, 0.2 * k[0], 0.2 * k[1], 0.15 + 0.1 * k[2], k[3], k[4], k[5], k[6], k[7], 1.0 + 0.5 * k[8]))
-        links.append(
-            "<link name='l%d'><inertial><origin xyz='%.17g %.17g %.17g' rpy='%.17g %.17g 0'/><mass value='%.17g'/>"
-            "<inertia ixx='%.17g' ixy='%.17g' ixz='%.17g' iyy='%.17g' iyz='%.17g' izz='%.17g'/></inertial></link>"
-            % (i + 1, 0.05 * k[9], 0.05 * k[10], 0.05 * k[11], 0.3 * k[12], 0.3 * k[13], 1.5 + k[14],
-               0.02, 0.002 * k[15], -0.001, 0.03, 0.0015, 0.025))
-    return "<robot name='gen%d'>%s%s</robot>" % (nj, "".join(links), "".join(joints))
 
 
 @pytest.mark.parametrize("nj", [1, 2, 3, 9, 10])
@@ -36,7 +16,7 @@ def test_generated_chain_parity(nj):
     from oracle.oracle import OracleChain
     from rosdyn_amd import Chain
     from rosdyn_amd.samples import trajectory_batch
-    xml = _chain_xml(nj, 100 + nj)
+    xml = generated_short_chain(nj, 100 + nj)
     chain, ref = Chain(xml, "l0", "l%d" % nj, GRAV), OracleChain(xml, "l0", "l%d" % nj, GRAV)
     N, n, P = 700, ref.n, ref.P
     q, dq, ddq = trajectory_batch(5 + nj, N, n)
@@ -178,7 +158,7 @@ def test_r_factor_with_nine_and_ten_input_joints(nj, N, permute):
     from rosdyn_amd import Chain
     from rosdyn_amd.components import ComponentSet
     from rosdyn_amd.samples import trajectory_batch
-    xml = _chain_xml(nj, 300 + nj)
+    xml = generated_short_chain(nj, 300 + nj)
     names = ["j%d" % i for i in range(nj)]
     if permute:
         names = names[3:] + names[:3][::-1]
@@ -220,7 +200,7 @@ def test_long_chain_per_sample_images_expanded_in_the_image_kernel(pick):
     import tempfile
     from oracle.oracle import OracleChain
     from rosdyn_amd import Chain
-    from test_gpu_longkin import generated_long_chain
+    from rosdyn_amd.urdf_gen import generated_long_chain
     xml = generated_long_chain(20, 2020)
     with tempfile.NamedTemporaryFile("w", suffix=".urdf", delete=False) as f:
         f.write(xml)

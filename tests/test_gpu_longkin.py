@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import FIXTURES
+from rosdyn_amd.urdf_gen import generated_long_chain, generated_revolute_chain
 
 pytestmark = pytest.mark.gpu
 GRAV = (0.2, -0.3, -9.7)
@@ -20,31 +21,6 @@ def _close(a, b, what):
     scale = max(1.0, float(np.abs(b).max()))
     err = float(np.abs(np.asarray(a) - b).max())
     assert err <= TOL * scale, "%s: %.3e > %.1e * %.3g" % (what, err, TOL, scale)
-
-
-def generated_long_chain(nj, seed):
-    """nj chain joints: every third one fixed, every fifth prismatic, the rest revolute; links with and without inertial data."""
-    from rosdyn_amd.samples import uniform_pm1
-    r = uniform_pm1(seed, (nj + 1, 16))
-    links = ["<link name='l0'/>"]
-    joints = []
-    for i in range(nj):
-        k = r[i]
-        typ = "fixed" if i % 3 == 2 else ("prismatic" if i % 5 == 3 else "revolute")
-        joints.append(
-            "<joint name='j%d' type='%s'><parent link='l%d'/><child link='l%d'/>"
-            "<origin xyz='%.17g %.17g %.17g' rpy='%.17g %.17g %.17g'/><axis xyz='%.17g %.17g %.17g'/>"
-            "<limit lower='-3' upper='3' effort='10' velocity='2'/></joint>"
-            % (i, typ, i, i + 1, 0.1 * k[0], 0.1 * k[1], 0.08 + 0.05 * k[2], k[3], k[4], k[5], k[6], k[7], 1.0 + 0.5 * k[8]))
-        if i % 7 == 4:
-            links.append("<link name='l%d'/>" % (i + 1))
-        else:
-            links.append(
-                "<link name='l%d'><inertial><origin xyz='%.17g %.17g %.17g' rpy='%.17g %.17g 0'/><mass value='%.17g'/>"
-                "<inertia ixx='%.17g' ixy='%.17g' ixz='%.17g' iyy='%.17g' iyz='%.17g' izz='%.17g'/></inertial></link>"
-                % (i + 1, 0.05 * k[9], 0.05 * k[10], 0.05 * k[11], 0.3 * k[12], 0.3 * k[13], 1.2 + k[14],
-                   0.02, 0.002 * k[15], -0.001, 0.03, 0.0015, 0.025))
-    return "<robot name='long%d'>%s%s</robot>" % (nj, "".join(links), "".join(joints))
 
 
 def _cases():
@@ -156,26 +132,6 @@ def test_long_chain_permuted_inputs_regressor_torque_inertia(case):
     _close(Ys.cpu().numpy().reshape(P, N, n).transpose(1, 2, 0), Yr, "Y stacked")
     _close(chain.getJointTorque(tq, tdq, tddq).cpu().numpy(), tr, "getJointTorque")
     _close(chain.getJointInertia(eq, layout="element").cpu().numpy().transpose(2, 1, 0), ref.joint_inertia(q), "M")
-
-
-def generated_revolute_chain(nj, seed):
-    """nj REVOLUTE joints, every one an input joint, every link with inertial data."""
-    from rosdyn_amd.samples import uniform_pm1
-    r = uniform_pm1(seed, (nj + 1, 16))
-    links, joints = ["<link name='l0'/>"], []
-    for i in range(nj):
-        k = r[i]
-        joints.append(
-            "<joint name='j%d' type='revolute'><parent link='l%d'/><child link='l%d'/>"
-            "<origin xyz='%.17g %.17g %.17g' rpy='%.17g %.17g %.17g'/><axis xyz='%.17g %.17g %.17g'/>"
-            "<limit lower='-3' upper='3' effort='10' velocity='2'/></joint>"
-            % (i, i, i + 1, 0.1 * k[0], 0.1 * k[1], 0.08 + 0.05 * k[2], k[3], k[4], k[5], k[6], k[7], 1.0 + 0.5 * k[8]))
-        links.append(
-            "<link name='l%d'><inertial><origin xyz='%.17g %.17g %.17g' rpy='%.17g %.17g 0'/><mass value='%.17g'/>"
-            "<inertia ixx='%.17g' ixy='%.17g' ixz='%.17g' iyy='%.17g' iyz='%.17g' izz='%.17g'/></inertial></link>"
-            % (i + 1, 0.05 * k[9], 0.05 * k[10], 0.05 * k[11], 0.3 * k[12], 0.3 * k[13], 1.2 + k[14],
-               0.02, 0.002 * k[15], -0.001, 0.03, 0.0015, 0.025))
-    return "<robot name='rev%d'>%s%s</robot>" % (nj, "".join(links), "".join(joints))
 
 
 @pytest.mark.parametrize("case", ["rev14", "rev20", "rev32", "gen20_all", "gen32_all", "gen20_twelve_permuted"])

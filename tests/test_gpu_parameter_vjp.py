@@ -18,10 +18,9 @@ rev14 takes the chunked route (more than 10 input joints): its rows and sums do 
 import numpy as np
 import pytest
 
-from test_gpu_forward_dynamics import _dev, _host, _inputs
-from test_gpu_forward_dynamics_derivatives import MAX_VELOCITY, MIN_VELOCITY, _set, _specs
-from test_gpu_forward_dynamics_vjp import _seed
-from test_gpu_rollout_components import _cpair
+from _arrays import _dev, _host, _inputs, _seed
+from _chains import _cpair
+from _components import MAX_VELOCITY, MIN_VELOCITY, _set, _specs
 
 pytestmark = pytest.mark.gpu
 CHAINS = ["planar_2r", "ur10_public", "mixed_joints", "panda_like", "ur10_permuted", "rev10", "ur10_public_long", "rev14"]
@@ -192,7 +191,7 @@ def test_an_indefinite_inertia_gives_nan_rows_and_zero_sums(layout):
     torch = pytest.importorskip("torch")
     from conftest import FIXTURES
     from rosdyn_amd import Chain
-    from test_gpu_forward_dynamics import GRAV
+    from _chains import GRAV
     chain = Chain(os.path.join(FIXTURES, "ur10_public.urdf"), "base_link", "tool0", GRAV)
     moving = ["shoulder_pan_joint", "shoulder_lift_joint", "elbow_joint", "wrist_1_joint", "wrist_2_joint", "wrist_3_joint"]
     assert chain.setInputJointsName(moving[:3] + ["flange-tool0"] + moving[3:])

@@ -10,77 +10,16 @@ import numpy as np
 import pytest
 
 from conftest import FIXTURES, ROOT
-from test_gpu_forward_dynamics import EPS, GRAV, _chain, _dev, _host, _inf, _pair
-from test_gpu_longkin import generated_revolute_chain
+from _arrays import DT, EPS, INTEGRATORS, REV_EXTRA, _dev, _dev_seq, _host, _inf, _rollout, _rollout_inputs as _inputs
+from _chains import GRAV, _chain, _pair
+from _references import _euler_residual_check, _np_rollout, _oracle_fd
+from rosdyn_amd.urdf_gen import generated_revolute_chain
 
 pytestmark = pytest.mark.gpu
 CHAINS = ["planar_2r", "ur10_like", "panda_like", "mixed_joints", "ur10_public_long", "rev10", "rev14", "gen20_permuted"]
-INTEGRATORS = ["semi_implicit_euler", "rk4"]
-DT = 1e-3
-# torque amplitude per chain: |ddq| of the oracle stays below about 1e3 on the inputs used here (measured on the CPU over every
-# evaluation of the multi-step test: the last column of MULTI_STEP; the wrists of the UR10 models and the last links of mixed_joints are light)
-TAU_SCALE = {"planar_2r": 2.0, "ur10_like": 0.4, "panda_like": 3.0, "mixed_joints": 0.1, "ur10_public_long": 3.0, "rev10": 5.0,
-             "rev14": 5.0, "gen20_permuted": 5.0}
-# k_rollout<NJ, .> of the joint counts CHAINS leaves out (one step and the split horizon only: MULTI_STEP has no row for them)
-REV_EXTRA = ["rev1", "rev3", "rev4", "rev5", "rev8", "rev9"]
-TAU_SCALE.update({name: 5.0 for name in REV_EXTRA})
-
-
-def _inputs(name, n, N, T, seed=4100):
-    from rosdyn_amd.samples import uniform_pm1
-    return uniform_pm1(seed, (N, n)), uniform_pm1(seed + 1, (N, n)), TAU_SCALE[name] * uniform_pm1(seed + 2, (T, N, n))
-
-
-def _dev_seq(torch, tau, layout):
-    return torch.from_numpy(np.ascontiguousarray(np.transpose(tau, (0, 2, 1)) if layout == "element" else tau)).cuda()
-
-
-def _host_seq(t, layout):
-    a = t.cpu().numpy()
-    return np.transpose(a, (0, 2, 1)) if layout == "element" else a
-
-
-def _rollout(torch, chain, q, dq, tau, dt, integrator, layout="sample", n_steps=None, **kw):
-    """tau: (T, N, n) or (N, n) host arrays; returns host arrays in (N, n) / (records, N, n) shape"""
-    ttau = _dev_seq(torch, tau, layout) if tau.ndim == 3 else _dev(torch, tau, layout)
-    r = chain.rollout(_dev(torch, q, layout), _dev(torch, dq, layout), ttau, dt, integrator=integrator, n_steps=n_steps, layout=layout, **kw)
-    out = (_host(r[0], layout), _host(r[1], layout), r[2].cpu().numpy())
-    if len(r) == 5:
-        out += (_host_seq(r[3], layout), _host_seq(r[4], layout))
-    return out
 
 
 # ---- the same integrators in numpy over any forward dynamics fd(q, dq, tau) -> ddq
-def _oracle_fd(ref, perturb=None):
-    def fd(q, dq, tau):
-        M = ref.joint_inertia(q)
-        h = ref.joint_torque(q, dq, np.zeros_like(q))
-        a = np.linalg.solve(M, (tau - h)[:, :, None])[:, :, 0]
-        if perturb is not None:
-            a = a * (1.0 + 1e-11 * perturb.uniform(-1.0, 1.0, a.shape))
-        return a
-    return fd
-
-
-def _np_step(fd, q, dq, tau, dt, integrator):
-    if integrator == "semi_implicit_euler":
-        dq1 = dq + dt * fd(q, dq, tau)
-        return q + dt * dq1, dq1
-    a1 = fd(q, dq, tau)
-    v2 = dq + 0.5 * dt * a1
-    a2 = fd(q + 0.5 * dt * dq, v2, tau)
-    v3 = dq + 0.5 * dt * a2
-    a3 = fd(q + 0.5 * dt * v2, v3, tau)
-    v4 = dq + dt * a3
-    a4 = fd(q + dt * v3, v4, tau)
-    return q + dt * (dq / 6 + v2 / 3 + v3 / 3 + v4 / 6), dq + dt * (a1 / 6 + a2 / 3 + a3 / 3 + a4 / 6)
-
-
-def _np_rollout(fd, q, dq, tau, dt, T, integrator):
-    """tau: (T, N, n), or (N, n) held for all steps"""
-    for t in range(T):
-        q, dq = _np_step(fd, q, dq, tau[t] if tau.ndim == 3 else tau, dt, integrator)
-    return q, dq
 
 
 # ---- 1. one step against what already exists
@@ -139,20 +78,6 @@ def test_one_step_against_the_library_own_forward_dynamics(name, integrator):
 
 
 # ---- 2. one Euler step against the oracle, residual form
-def _euler_residual_check(torch, chain, ref, name, N, layout, seed, inputs=None):
-    """inputs: None (this module's inputs for the chain `name`), or (q0, dq0, tau) with tau of shape (1, N, n) and `name` a label"""
-    q0, dq0, tau = inputs if inputs is not None else _inputs(name, ref.n, N, 1, seed=seed)
-    q1, dq1, st = _rollout(torch, chain, q0, dq0, tau, DT, "semi_implicit_euler", layout)
-    assert (st == 1).all(), np.unique(st)
-    ddq = (dq1 - dq0) / DT
-    M = ref.joint_inertia(q0)
-    h = ref.joint_torque(q0, dq0, np.zeros_like(q0))
-    Minf = np.abs(M).sum(axis=2).max(axis=1)
-    res = _inf(np.einsum("sij,sj->si", M, ddq) + h - tau[0])
-    bound = 1e-11 * (Minf * _inf(ddq) + _inf(tau[0]) + _inf(h)) + (4 * EPS / DT) * (_inf(dq0) + DT * _inf(ddq)) * Minf
-    print("%s %s N=%d: residual/bound max %.3g" % (name, layout, N, (res / bound).max()))
-    assert (res <= bound).all(), (float((res / bound).max()), int(np.argmax(res / bound)))
-    assert (_inf(q1 - (q0 + DT * dq1)) <= 4 * EPS * (_inf(q0) + DT * _inf(dq1))).all()
 
 
 @pytest.mark.parametrize("name", CHAINS)

@@ -13,114 +13,17 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_gpu_forward_dynamics import EPS, _chain, _dev, _host, _pair
-from test_gpu_forward_dynamics_derivatives import _set, _specs
-from test_gpu_rollout import INTEGRATORS, TAU_SCALE, _dev_seq, _host_seq, _np_rollout, _np_step, _oracle_fd
-from test_gpu_torque_derivatives import _input_types, _mat, _reference
+from _arrays import EPS, INTEGRATORS, _adjoint, _adjoint_inputs as _inputs, _dev, _dev_seq, _directional_inputs, _forward, _host, _host_seq, _seeds
+from _chains import _chain, _pair
+from _components import _set, _specs
+from _references import _input_types, _lib_abs_vjp, _lib_fd, _lib_vjp, _np_adjoint, _np_rollout, _np_step, _np_step_adjoint, _oracle_fd, _reference
 
 pytestmark = pytest.mark.gpu
 SWEPT = ["planar_2r", "ur10_like", "panda_like", "mixed_joints", "ur10_public_long", "rev10"]
 LONG = ["rev14", "gen20_permuted"]
-B4 = (1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0)
-
-
-def _inputs(name, n, N, T, seed):
-    from rosdyn_amd.samples import uniform_pm1
-    return uniform_pm1(seed, (N, n)), uniform_pm1(seed + 1, (N, n)), TAU_SCALE[name] * uniform_pm1(seed + 2, (T, N, n))
-
-
-def _seeds(n, N, T, seed):
-    """end seeds (N, n) x 2 and running seeds (T, N, n) x 2, uniform in +-1"""
-    from rosdyn_amd.samples import uniform_pm1
-    return (uniform_pm1(seed + 10, (N, n)), uniform_pm1(seed + 11, (N, n)), uniform_pm1(seed + 12, (T, N, n)), uniform_pm1(seed + 13, (T, N, n)))
-
-
-def _forward(torch, chain, q0, dq0, tau, dt, integrator, layout="sample", components=None, **kw):
-    """device tensors of the forward call with one record per step: (tq0, tdq0, ttau, q_traj, dq_traj), and the host status"""
-    tq, tdq, ttau = _dev(torch, q0, layout), _dev(torch, dq0, layout), _dev_seq(torch, tau, layout)
-    r = chain.rollout(tq, tdq, ttau, dt, integrator=integrator, layout=layout, trajectory_every=1, components=components, **kw)
-    return (tq, tdq, ttau, r[3], r[4]), r[2].cpu().numpy()
-
-
-def _adjoint(torch, chain, fw, dt, integrator, layout="sample", gq_end=None, gdq_end=None, gq_traj=None, gdq_traj=None, **kw):
-    """host arrays (gq0, gdq0, gtau, status); fw: _forward's tensors (or a tuple with None for the records of a one-step horizon)"""
-    d = lambda x: None if x is None else (_dev_seq(torch, x, layout) if x.ndim == 3 else _dev(torch, x, layout))
-    tq, tdq, ttau, q_traj, dq_traj = fw
-    r = chain.rolloutAdjoint(tq, tdq, ttau, dt, q_traj, dq_traj, gq_end=d(gq_end), gDq_end=d(gdq_end), gq_traj=d(gq_traj), gDq_traj=d(gdq_traj),
-                             integrator=integrator, layout=layout, **kw)
-    gtau = _host_seq(r[2], layout) if r[2].dim() == 3 else _host(r[2], layout)
-    return _host(r[0], layout), _host(r[1], layout), gtau, r[3].cpu().numpy()
 
 
 # ---- the step transposes in numpy over any product vjp(q, v, tau, seed) -> (q_bar, v_bar, tau_bar) and forward dynamics fd(q, v, tau) -> ddq
-def _np_stage_states(fd, q, v, tau, dt):
-    X = [(q, v)]
-    for c in (0.5 * dt, 0.5 * dt, dt):
-        a = fd(X[-1][0], X[-1][1], tau)
-        X.append((q + c * X[-1][1], v + c * a))
-    return X
-
-
-def _np_step_adjoint(vjp, fd, q, v, tau, lq, lv, dt, integrator):
-    """(lq, lv, gtau) of one backward step, by the formulas of include/rdyn.h in their order"""
-    if integrator == "semi_implicit_euler":
-        lvs = lv + dt * lq
-        qb, vb, tb = vjp(q, v, tau, dt * lvs)
-        return lq + qb, lvs + vb, tb
-    X = _np_stage_states(fd, q, v, tau, dt)
-    kq = [dt * b * lq for b in B4]
-    kv = [dt * b * lv for b in B4]
-    xq, xv, gtau = lq.copy(), lv.copy(), np.zeros_like(lq)
-    c = (None, 0.5 * dt, 0.5 * dt, dt)
-    for i in (3, 2, 1, 0):
-        qb, vb, tb = vjp(X[i][0], X[i][1], tau, kv[i])
-        Xq, Xv = qb, kq[i] + vb
-        gtau = gtau + tb
-        xq, xv = xq + Xq, xv + Xv
-        if i > 0:
-            kq[i - 1] = kq[i - 1] + c[i] * Xq
-            kv[i - 1] = kv[i - 1] + c[i] * Xv
-    return xq, xv, gtau
-
-
-def _np_adjoint(vjp, fd, q0, dq0, tau, q_traj, dq_traj, gq_end, gdq_end, dt, integrator, gq_traj=None, gdq_traj=None):
-    """(gq0, gdq0, gtau (T, N, n)) over the whole horizon; x_t from the trajectory given (record k = x_{k + 1})"""
-    T = tau.shape[0]
-    lq, lv = gq_end.copy(), gdq_end.copy()
-    if gq_traj is not None and T > 0:
-        lq, lv = lq + gq_traj[T - 1], lv + gdq_traj[T - 1]
-    gtau = np.zeros_like(tau)
-    for t in range(T - 1, -1, -1):
-        q, v = (q0, dq0) if t == 0 else (q_traj[t - 1], dq_traj[t - 1])
-        lq, lv, gtau[t] = _np_step_adjoint(vjp, fd, q, v, tau[t], lq, lv, dt, integrator)
-        if t >= 1 and gq_traj is not None:
-            lq, lv = lq + gq_traj[t - 1], lv + gdq_traj[t - 1]
-    return lq, lv, gtau
-
-
-def _lib_fd(torch, chain, components=None):
-    def fd(q, v, tau):
-        a, st = chain.getJointAcceleration(_dev(torch, q, "sample"), _dev(torch, v, "sample"), _dev(torch, tau, "sample"), components=components)
-        assert (st.cpu().numpy() == 1).all()
-        return a.cpu().numpy()
-    return fd
-
-
-def _lib_vjp(torch, chain, components=None):
-    def vjp(q, v, tau, seed):
-        out = chain.getJointAccelerationVjp(*(_dev(torch, x, "sample") for x in (q, v, tau, seed)), components=components)
-        assert (out[0].cpu().numpy() == 1).all()
-        return tuple(t.cpu().numpy() for t in out[1:])
-    return vjp
-
-
-def _lib_abs_vjp(torch, chain, components=None):
-    """the product on magnitudes: |dddq_dq|' m, |dddq_dv|' m, |minv| m -- the sum of the absolute terms of every entry of the product"""
-    def vjp(q, v, tau, m):
-        out = chain.getJointAccelerationDerivatives(*(_dev(torch, x, "sample") for x in (q, v, tau)), components=components)
-        Xq, Xv, Mi = (np.abs(_mat(t, "sample")) for t in out[2:])   # [s, i, k]
-        return np.einsum("sik,si->sk", Xq, m), np.einsum("sik,si->sk", Xv, m), np.einsum("sik,si->sk", Mi, m)
-    return vjp
 
 
 # ---- 1. one step against the library's own product
@@ -219,14 +122,6 @@ DIRECTIONAL = {
     "rev14": ((3.66e-5, 3.68e-5), (3.09e-5, 3.85e-5)),
 }
 DIRECTIONAL_CHAINS = ["planar_2r", "ur10_like", "panda_like", "mixed_joints", "rev10", "rev14"]
-
-
-def _directional_inputs(name, n, N=200, T=8):
-    from rosdyn_amd.samples import uniform_pm1
-    q0, dq0, tau = _inputs(name, n, N, T, seed=6700)
-    cq, cv, e, f = (uniform_pm1(6710 + i, (N, n)) for i in range(4))
-    g = TAU_SCALE[name] * uniform_pm1(6714, (T, N, n))
-    return q0, dq0, tau, cq, cv, e, f, g
 
 
 def _directional_errors(loss, grads, q0, dq0, tau, e, f, g):

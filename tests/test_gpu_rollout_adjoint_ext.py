@@ -16,14 +16,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_gpu_forward_dynamics import EPS, _chain, _dev, _host, _inf
-from test_gpu_forward_dynamics_derivatives import _set, _specs
-from test_gpu_forward_dynamics_ext import SCALE, _dev_w, _tau_e, _trio, _wrenches
-from test_gpu_forward_dynamics_vjp_ext import _WrenchTorque, _host_w, _wrench_matrix
-from test_gpu_rollout import INTEGRATORS, _dev_seq, _host_seq, _np_rollout, _np_step
-from test_gpu_rollout_adjoint import _np_adjoint, _np_step_adjoint, _seeds
-from test_gpu_rollout_ext import _dev_wseq, _inputs, _oracle_fd_ext
-from test_gpu_torque_derivatives import _input_types, _mat, _reference
+from _arrays import (EPS, INTEGRATORS, WRENCH_SCALE as SCALE, _dev, _dev_seq, _dev_w, _dev_wseq,
+                     _host, _host_seq, _host_w, _mat, _seeds, _wrench_rollout_inputs as _inputs, _wrenches)
+from _chains import _chain, _trio
+from _components import _set, _specs
+from _references import (_WrenchTorque, _input_types, _np_adjoint, _np_rollout, _np_step,
+                         _np_step_adjoint, _oracle_fd_ext, _reference, _tau_e, _wrench_matrix)
 
 pytestmark = pytest.mark.gpu
 CHAINS = ["planar_2r", "mixed_joints", "ur10_like", "panda_like", "ur10_public", "ur10_permuted", "rev10"]

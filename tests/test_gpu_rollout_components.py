@@ -10,64 +10,23 @@ import numpy as np
 import pytest
 
 from conftest import FIXTURES, ROOT
-from test_gpu_forward_dynamics import EPS, GRAV, FILES, _chain, _dev, _host, _inf, _pair, _solve
-from test_gpu_longkin import generated_revolute_chain
-from test_gpu_rollout import DT, INTEGRATORS, TAU_SCALE, _inputs as _rollout_inputs, _np_rollout, _oracle_fd, _rollout
+from _arrays import DT, EPS, INTEGRATORS, _dev, _host, _inf, _rollout, _rollout_inputs, _solve
+from _chains import GRAV, _chain, _cpair
+from _components import FRICTION1, FRICTION2, ROLLOUT_MIN_VELOCITY as MIN_VELOCITY, SPRING, _scaled_specs as _specs, _set
+from _references import _np_rollout, _oracle_fd_c
+from rosdyn_amd.urdf_gen import generated_revolute_chain
 
 pytestmark = pytest.mark.gpu
 # planar_2r: the smallest chain; ur10_like, panda_like: 6 and 7 joints; mixed_joints: prismatic joints; ur10_public_long: the reduced
 # companion (are component indices still input indices?); ur10_permuted: input order differs from chain order; rev10: the largest
 # register kernel; rev14, gen20_permuted: the chunked route, permuted
 CHAINS = ["planar_2r", "ur10_like", "panda_like", "mixed_joints", "ur10_public_long", "ur10_permuted", "rev10", "rev14", "gen20_permuted"]
-SCALE = dict(TAU_SCALE, ur10_permuted=TAU_SCALE["ur10_like"])
 SIZES = (1, 63, 64, 65, 200)
-FRICTION1, FRICTION2, SPRING = 0, 1, 2
-MIN_VELOCITY, MAX_VELOCITY = 0.05, 0.8   # |dq| <= 1: a few percent of the joints inside the linear band, the velocity saturation is hit
 
 
 def _inputs(name, n, N, T, seed):
     """test_gpu_rollout.py's inputs; ur10_permuted is ur10_like with its input joints permuted and takes its torque scale"""
     return _rollout_inputs("ur10_like" if name == "ur10_permuted" else name, n, N, T, seed=seed)
-
-
-def _cpair(name, oracle=True):
-    """(chain, oracle chain or None) of this module's chain names"""
-    if name != "ur10_permuted":
-        return _pair(name) if oracle else (_chain(name), None)
-    from oracle.oracle import OracleChain
-    from rosdyn_amd import Chain
-    f, base, tool = FILES["ur10_like"]
-    chain = Chain(os.path.join(FIXTURES, f), base, tool, GRAV)
-    names = chain.getActiveJointsName()
-    order = [names[i] for i in (4, 0, 5, 2, 1, 3)]
-    assert chain.setInputJointsName(order) and chain.getActiveJointsName() == order
-    ref = OracleChain(os.path.join(FIXTURES, f), base, tool, GRAV, input_joint_names=order) if oracle else None
-    return chain, ref
-
-
-# Coulomb parameters shrunk per chain until the oracle alone keeps dev of MULTI_STEP_C below 1e-9 (the in-band slope coulomb / min_velocity
-# against the light last links of these chains); 1 where not listed
-COULOMB = {"ur10_like": 0.3, "panda_like": 0.3, "mixed_joints": 0.3, "ur10_public_long": 0.3, "rev14": 0.3}
-
-
-def _specs(name, n, coulomb=None):
-    """(type, joint, min_velocity, max_velocity, parameters) in list order: a FRICTION1 and, later in the list, a SPRING on joint 0 (two
-    components share a joint, list order matters), a FRICTION2 on the last input joint, a SPRING on joint 1; with n >= 4 the joints
-    2 .. n - 2 have no component.  Parameters of order 1 times the chain's torque scale."""
-    s = SCALE[name]
-    coulomb = COULOMB.get(name, 1.0) if coulomb is None else coulomb
-    specs = [(FRICTION1, 0, MIN_VELOCITY, MAX_VELOCITY, (0.9 * coulomb * s, 0.7 * s, 0.0))]
-    if n >= 2:
-        specs.append((FRICTION2, n - 1, MIN_VELOCITY, MAX_VELOCITY, (0.8 * coulomb * s, 0.5 * s, -0.6 * s)))
-    if n >= 3:
-        specs.append((SPRING, 1, 0.0, 0.0, (1.1 * s, -0.4 * s, 0.0)))
-    specs.append((SPRING, 0, 0.0, 0.0, (-0.8 * s, 0.3 * s, 0.0)))
-    return specs
-
-
-def _set(specs, n):
-    from rosdyn_amd.components import ComponentSet
-    return ComponentSet([dict(type=t, joint=j, min_velocity=lo, max_velocity=hi, parameters=list(p)) for t, j, lo, hi, p in specs], n)
 
 
 def _tau_add(torch, cs, q, dq):
@@ -184,10 +143,6 @@ def test_one_step_against_the_library_own_pieces(name, integrator):
 
 
 # ---- 4. multi-step against the oracle
-def _oracle_fd_c(ref, specs, perturb=None):
-    from oracle.oracle import components_regressor
-    fd = _oracle_fd(ref, perturb)
-    return lambda q, dq, tau: fd(q, dq, tau - components_regressor(specs, ref.n, q, dq)[1])
 
 
 def _multi_step_inputs(name, n):

@@ -9,21 +9,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_gpu_forward_dynamics import EPS, _dev, _host, _inf
-from test_gpu_forward_dynamics_ext import CHAINS, LAYOUTS, SCALE, SIZES, _components, _dev_w, _trio, _wrenches
-from test_gpu_rollout import DT, INTEGRATORS, TAU_SCALE, _dev_seq, _inputs as _rollout_inputs, _np_rollout, _rollout
+from _arrays import (DT, EPS, INTEGRATORS, LAYOUTS, SIZES, _dev, _dev_seq,
+                     _dev_w, _dev_wseq, _host, _inf, _rollout, _wrench_rollout_inputs as _inputs, _wrenches)
+from _chains import WRENCH_CHAINS as CHAINS, _trio
+from _components import _named_components as _components
+from _references import _np_rollout, _oracle_fd_ext
 
 pytestmark = pytest.mark.gpu
-
-
-def _inputs(name, n, N, T, seed):
-    """test_gpu_rollout.py's inputs; the UR10 variants it has no scale for take ur10_like's"""
-    return _rollout_inputs(name if name in TAU_SCALE else "ur10_like", n, N, T, seed=seed)
-
-
-def _dev_wseq(torch, W, layout):
-    """host (T, N, L, 6) or (T, N, 6) -> (T,) + the record shape of the layout"""
-    return torch.stack([_dev_w(torch, w, layout) for w in W])
 
 
 def _ext_rollout(torch, chain, q, dq, tau, W, integrator, layout="sample", link=None, seq=False, **kw):
@@ -128,14 +120,6 @@ MULTI_STEP_E = {
     ("gen20_permuted", "semi_implicit_euler"): (6.15e-12, 4.92e-11, 538),
     ("gen20_permuted", "rk4"): (4.26e-12, 3.41e-11, 538),
 }
-
-
-def _oracle_fd_ext(ref, W):
-    def fd(q, dq, tau):
-        M = ref.joint_inertia(q)
-        h = ref.joint_torque(q, dq, np.zeros_like(q), ext=W)
-        return np.linalg.solve(M, (tau - h)[:, :, None])[:, :, 0]
-    return fd
 
 
 @pytest.mark.parametrize("name", CHAINS)

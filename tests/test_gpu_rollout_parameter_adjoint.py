@@ -18,11 +18,10 @@ Measured once on an MI355X: 1 at most 8e-14 of the sum of the absolute rows (rev
 import numpy as np
 import pytest
 
-from test_gpu_forward_dynamics import _dev, _host
-from test_gpu_forward_dynamics_derivatives import _set, _specs
-from test_gpu_rollout import INTEGRATORS, _dev_seq, _host_seq
-from test_gpu_rollout_adjoint import _adjoint, _forward, _inputs, _lib_fd, _np_adjoint, _seeds
-from test_gpu_rollout_components import _cpair
+from _arrays import INTEGRATORS, _adjoint, _adjoint_inputs as _inputs, _dev, _dev_seq, _forward, _host, _host_seq, _seeds
+from _chains import _cpair
+from _components import _set, _specs
+from _references import _lib_fd, _np_adjoint
 
 pytestmark = pytest.mark.gpu
 CHAINS = ["planar_2r", "ur10_like", "mixed_joints", "ur10_public_long", "rev10"]
@@ -253,8 +252,9 @@ def test_replays_from_a_captured_graph(integrator):
 @pytest.mark.parametrize("name", ["planar_2r", "ur10_like", "panda_like"])
 def test_directional_consistency_with_central_differences_over_with_parameters(name, integrator):
     torch = pytest.importorskip("torch")
-    from test_gpu_rollout_adjoint import _directional_inputs
-    from test_parameter_gradient_inputs import DT as DT_CD, H, N, ORACLE_WORST, T, _direction
+    from _arrays import _directional_inputs
+    from _arrays import DIRECTIONAL_DT as DT_CD, DIRECTIONAL_H as H, DIRECTIONAL_N as N, DIRECTIONAL_T as T, _direction
+    from _references import ORACLE_WORST
     chain, _ = _cpair(name, oracle=False)
     n = chain.getActiveJointsNumber()
     q0, dq0, tau, cq, cv = _directional_inputs(name, n, N, T)[:5]

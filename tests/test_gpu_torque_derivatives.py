@@ -27,67 +27,17 @@ import numpy as np
 import pytest
 
 from conftest import FIXTURES, ROOT
-from test_gpu_forward_dynamics import CHAINS, _chain, _dev, _inf, _pair, _spec
-from test_gpu_longkin import generated_revolute_chain
+from _arrays import _dev, _inf, _mat
+from _chains import CHAINS, _chain, _pair, _spec
+from _references import _input_types, _reference
+from rosdyn_amd.urdf_gen import generated_revolute_chain
 
 pytestmark = pytest.mark.gpu
-REVOLUTE, PRISMATIC = 0, 1   # rdyn_joint_type
 
 
 def _inputs(n, N, seed=77):
     from rosdyn_amd.samples import uniform_pm1
     return uniform_pm1(seed, (N, n)), uniform_pm1(seed + 1, (N, n)), 3.0 * uniform_pm1(seed + 2, (N, n))
-
-
-def _input_types(chain):
-    """rdyn_joint_type of every input joint, in input order"""
-    from rosdyn_amd._lib import lib
-    L, h = lib(), chain._h
-    kind = {L.rdyn_chain_joint_name(h, j).decode(): L.rdyn_chain_joint_type(h, j) for j in range(L.rdyn_chain_joints_number(h))}
-    return [kind[name] for name in chain.getActiveJointsName()]
-
-
-def _spectral(ref, q, dq, ddq, k, points):
-    """d tau / d q_k of every sample by spectral differentiation over `points` equispaced samples of q_k: (N, n)"""
-    N, n = q.shape
-    Q = np.repeat(q[None], points, axis=0)
-    Q[:, :, k] += (2.0 * np.pi / points) * np.arange(points)[:, None]
-    T = ref.joint_torque(Q.reshape(-1, n), np.tile(dq, (points, 1)), np.tile(ddq, (points, 1))).reshape(points, N, n)
-    c = np.fft.fft(T, axis=0) / points
-    freq = np.fft.fftfreq(points, 1.0 / points)
-    c[points // 2] = 0.0   # the Nyquist mode has no derivative on the grid (and no content: degree <= 2)
-    return (1j * freq[:, None, None] * c).sum(axis=0).real   # the grid starts AT q_k: the derivative there is sum_m i m c_m
-
-
-def _central(ref, q, dq, ddq, k, which):
-    e = np.zeros_like(q)
-    e[:, k] = 1.0
-    if which == 0:
-        return 0.5 * (ref.joint_torque(q + e, dq, ddq) - ref.joint_torque(q - e, dq, ddq))
-    return 0.5 * (ref.joint_torque(q, dq + e, ddq) - ref.joint_torque(q, dq - e, ddq))
-
-
-def _reference(ref, types, q, dq, ddq):
-    """(Dq_ref, Dv_ref, tau_ref, construction gap): D[s, i, k] = d tau_i / d x_k"""
-    N, n = q.shape
-    Dq, Dv = np.zeros((N, n, n)), np.zeros((N, n, n))
-    gap = np.zeros(N)
-    for k in range(n):
-        if types[k] == REVOLUTE:
-            Dq[:, :, k] = _spectral(ref, q, dq, ddq, k, 8)
-            gap = np.maximum(gap, _inf(Dq[:, :, k] - _spectral(ref, q, dq, ddq, k, 16)))
-        else:
-            Dq[:, :, k] = _central(ref, q, dq, ddq, k, 0)
-        Dv[:, :, k] = _central(ref, q, dq, ddq, k, 1)
-    return Dq, Dv, ref.joint_torque(q, dq, ddq), gap
-
-
-def _mat(t, layout):
-    """library record -> (N, n, n) with [s, i, k] = d tau_i / d x_k"""
-    a = t.cpu().numpy()
-    if layout == "element":
-        a = np.moveaxis(a, -1, 0)   # (N, k, i)
-    return np.swapaxes(a, 1, 2)
 
 
 def _derivs(torch, chain, q, dq, ddq, layout, want=("dq", "dv", "M")):

@@ -4,7 +4,7 @@ and the C oracle."""
 import numpy as np
 import pytest
 
-from test_gpu_gram_wide import GRAV, _chain_case, _ur6
+from _chains import WIDE_GRAV as GRAV, _chain_case, _ur6
 
 pytestmark = pytest.mark.gpu
 

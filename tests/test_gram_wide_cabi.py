@@ -6,12 +6,11 @@ import os
 import pytest
 
 from conftest import FIXTURES
-
-RDYN_ERR_INVALID_ARGUMENT = 1
+from _cabi import RDYN_ERR_INVALID_ARGUMENT
 
 
 def _long_xml(nj, seed):
-    from test_gpu_longkin import generated_revolute_chain
+    from rosdyn_amd.urdf_gen import generated_revolute_chain
     return generated_revolute_chain(nj, seed)
 
 
@@ -43,7 +42,7 @@ def test_regressor_gram_wide_workspace_for_many_input_joints(nj):
 
 
 def test_regressor_gram_wide_workspace_permuted_inputs_and_fixed_joints():
-    from test_gpu_longkin import generated_long_chain
+    from rosdyn_amd.urdf_gen import generated_long_chain
     from rosdyn_amd import Chain
     from rosdyn_amd._lib import lib
     c = Chain(generated_long_chain(20, 2020), "l0", "l20")

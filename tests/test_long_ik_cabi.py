@@ -5,12 +5,8 @@ import ctypes as C
 
 import pytest
 
-from test_gpu_longkin import generated_revolute_chain
-
-RDYN_OK = 0
-RDYN_ERR_INVALID_ARGUMENT = 1
-RDYN_ERR_UNSUPPORTED = 5
-FAKE = 4096   # never dereferenced: the checks come first
+from _cabi import FAKE, RDYN_ERR_INVALID_ARGUMENT, RDYN_OK
+from rosdyn_amd.urdf_gen import generated_revolute_chain
 
 
 def _call(chain, n_samples, T_target=FAKE, damping=1e-3, q=FAKE, max_iterations=10, toll=1e-6):

@@ -5,12 +5,7 @@ import ctypes as C
 
 import pytest
 
-from test_forward_dynamics_cabi import CHUNKED, SWEPT, _chain
-from test_rollout_adjoint_cabi import _comp
-
-RDYN_OK = 0
-RDYN_ERR_INVALID_ARGUMENT = 1
-FAKE = 4096   # never dereferenced: the checks come first
+from _cabi import CHUNKED, FAKE, RDYN_ERR_INVALID_ARGUMENT, RDYN_OK, SWEPT, _chain, _comp
 
 
 def _query(chain, N, comps=None, n_comps=0, chunk_samples=0):
@@ -112,7 +107,7 @@ def _padj_query(chain, d, N, comps=None, n_comps=0, chunk_samples=0):
 def _padj(chain, N, desc=True, comps=None, n_comps=0, chunk_samples=0, workspace=FAKE, workspace_bytes=None, q=FAKE, dq=FAKE, batch=True, layout=0,
           pg=True, gpi=FAKE, gcomp=FAKE, accumulate=0, **kw):
     from rosdyn_amd._lib import Batch, ParameterGradient, lib
-    from test_rollout_adjoint_cabi import _desc
+    from _cabi import _adjoint_desc as _desc
     b = Batch()
     b.n_samples, b.q, b.dq, b.layout, b.device = N, q, dq, layout, 0
     d = _desc(chain.getActiveJointsNumber(), max(N, 0), **kw)
@@ -157,7 +152,7 @@ def test_rollout_call_no_samples_is_ok_and_every_listed_refusal(name):
     # gq0, gdq0 and gtau may all be null here
     assert _padj(chain, 0, gq0=None, gdq0=None, gtau=None) == RDYN_OK
     # the workspace: the lanes' accumulators, one status word per sample, the column sums
-    from test_rollout_adjoint_cabi import _desc
+    from _cabi import _adjoint_desc as _desc
     nj = chain.getJointsNumber()
     three = _comp(ctype=1)
     for M in (1, 65, 4096):

@@ -23,23 +23,11 @@ Measured (`python tests/test_parameter_gradient_inputs.py`), worst err(H) / scal
 import numpy as np
 import pytest
 
-from test_gpu_forward_dynamics import GRAV, _spec
-from test_gpu_rollout import INTEGRATORS, _np_rollout, _oracle_fd
-from test_gpu_rollout_adjoint import _directional_inputs
+from _arrays import DIRECTIONAL_DT as DT, DIRECTIONAL_H as H, DIRECTIONAL_N as N, DIRECTIONAL_T as T, INTEGRATORS, _direction, _directional_inputs
+from _chains import GRAV, _spec
+from _references import ORACLE_WORST, _np_rollout, _oracle_fd
 
 CHAINS = ["planar_2r", "ur10_like", "panda_like"]
-H, N, T, DT = 1.0, 200, 8, 1e-2
-# chain: worst err(H) / scale on the oracle (semi-implicit Euler, RK4): the table above
-ORACLE_WORST = {
-    "planar_2r": (7.839e-05, 8.097e-05), "ur10_like": (5.840e-05, 6.196e-05), "panda_like": (4.089e-04, 3.272e-04),
-}
-
-
-def _direction(pi):
-    """delta (P,): every parameter 1 % of its own nominal size times uniform(-1, 1).  (1 % of the LINK's largest parameter on every entry
-    makes the inertia of a heavy, compact link indefinite -- 0.1 kg m^2 on 0.01 -- and the oracle's rollout of ur10_like and panda_like
-    diverges; relative to each entry the perturbed links stay physical.)"""
-    return 0.01 * np.abs(pi) * np.random.default_rng(4242).uniform(-1.0, 1.0, pi.shape)
 
 
 def _oracle_with_parameters(name, pi):

@@ -4,26 +4,10 @@ import ctypes as C
 
 import pytest
 
-from test_forward_dynamics_cabi import CHUNKED, SWEPT, _chain
-
-RDYN_OK = 0
-RDYN_ERR_INVALID_ARGUMENT = 1
-FAKE = 4096   # never dereferenced: the checks come first
-EULER, RK4 = 0, 1
-
-
-def _comp(joint=0, ctype=0):
-    from rosdyn_amd._lib import Component
-    c = Component()
-    c.type, c.joint, c.min_velocity, c.max_velocity = ctype, joint, 1e-2, 10.0
-    c.parameters[0], c.parameters[1], c.parameters[2] = 1.0, 0.5, 0.0
-    return c
+from _cabi import CHUNKED, EULER, FAKE, RDYN_ERR_INVALID_ARGUMENT, RDYN_OK, RK4, SWEPT, _adj_query, _adjoint_desc as _desc, _chain, _comp, _vjp_query
 
 
 # ---- rdyn_forward_dynamics_vjp ------------------------------------------------------------------------------------
-def _vjp_query(chain, chunk_samples=0):
-    from rosdyn_amd._lib import lib
-    return lib().rdyn_forward_dynamics_vjp_workspace_bytes(chain._h, chunk_samples)
 
 
 def _vjp(chain, N, q=FAKE, dq=FAKE, tau=FAKE, seed=FAKE, q_bar=FAKE, dq_bar=FAKE, tau_bar=FAKE, ddq=FAKE, status=FAKE, comps=None, n_comps=0,
@@ -101,24 +85,6 @@ def test_vjp_workspace_of_the_chunked_route(name):
 
 
 # ---- rdyn_rollout_adjoint -----------------------------------------------------------------------------------------
-def _desc(n, N, **kw):
-    from rosdyn_amd._lib import RolloutAdjointDesc
-    d = RolloutAdjointDesc()
-    d.n_steps, d.integrator, d.dt = 5, RK4, 1e-3
-    d.tau, d.tau_step_stride = FAKE, n * N
-    d.q_traj, d.dq_traj, d.traj_step_stride = FAKE, FAKE, n * N
-    d.gq_end, d.gdq_end = FAKE, FAKE
-    d.gq_traj, d.gdq_traj, d.gtraj_step_stride = FAKE, FAKE, n * N
-    d.gq0, d.gdq0, d.gtau, d.gtau_step_stride = FAKE, FAKE, FAKE, n * N
-    d.status = FAKE
-    for k, v in kw.items():
-        setattr(d, k, v)
-    return d
-
-
-def _adj_query(chain, d, N, chunk_samples=0):
-    from rosdyn_amd._lib import lib
-    return lib().rdyn_rollout_adjoint_workspace_bytes(chain._h, C.byref(d), N, chunk_samples)
 
 
 def _adj(chain, N, desc=True, comps=None, n_comps=0, chunk_samples=0, workspace=FAKE, workspace_bytes=None, q=FAKE, dq=FAKE, batch=True, layout=0,

@@ -8,11 +8,8 @@ import re
 import pytest
 
 from conftest import FIXTURES, ROOT
-from test_forward_dynamics_cabi import CHUNKED, SWEPT, _chain
-from test_forward_dynamics_ext_cabi import _batch, _ext
-from test_rollout_adjoint_cabi import EULER, FAKE, RDYN_ERR_INVALID_ARGUMENT, RDYN_OK, RK4, _adj_query, _comp, _desc, _vjp_query
-
-RDYN_ERR_UNSUPPORTED = 5
+from _cabi import (CHUNKED, EULER, FAKE, RDYN_ERR_INVALID_ARGUMENT, RDYN_ERR_UNSUPPORTED, RDYN_OK, RK4,
+                   SWEPT, _adj_query, _adjoint_desc as _desc, _batch, _chain, _comp, _ext, _vjp_query)
 
 
 def _gext(gw=FAKE, step_stride=0):

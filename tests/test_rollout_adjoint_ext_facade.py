@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 from conftest import FIXTURES, ROOT
-from test_forward_dynamics_ext_facade import CHAINS, _value
+from _arrays import _value
+from _chains import FACADE_CHAINS as CHAINS
 
 
 def _build(tmp_path):

@@ -4,30 +4,7 @@ import ctypes as C
 
 import pytest
 
-from test_forward_dynamics_cabi import CHUNKED, SWEPT, _chain
-
-RDYN_OK = 0
-RDYN_ERR_INVALID_ARGUMENT = 1
-FAKE = 4096   # never dereferenced: the checks come first
-EULER, RK4 = 0, 1
-
-
-def _desc(n, N, **kw):
-    from rosdyn_amd._lib import RolloutDesc
-    d = RolloutDesc()
-    d.n_steps, d.integrator, d.dt = 5, RK4, 1e-3
-    d.tau, d.tau_step_stride = FAKE, n * N
-    d.q_end, d.dq_end, d.q_traj, d.dq_traj = FAKE, FAKE, None, None
-    d.traj_step_stride, d.traj_every = 0, 0
-    d.status = FAKE
-    for k, v in kw.items():
-        setattr(d, k, v)
-    return d
-
-
-def _query(chain, d, N, chunk_samples=0):
-    from rosdyn_amd._lib import lib
-    return lib().rdyn_rollout_workspace_bytes(chain._h, C.byref(d), N, chunk_samples)
+from _cabi import CHUNKED, EULER, FAKE, RDYN_ERR_INVALID_ARGUMENT, RDYN_OK, RK4, SWEPT, _chain, _query, _rollout_desc as _desc
 
 
 def _call(chain, N, desc=True, chunk_samples=0, workspace=FAKE, workspace_bytes=None, q=FAKE, dq=FAKE, batch=True, layout=0, **kw):

@@ -7,19 +7,8 @@ import re
 import pytest
 
 from conftest import ROOT
-from test_forward_dynamics_cabi import CHUNKED, SWEPT, _chain
-from test_rollout_cabi import EULER, FAKE, RDYN_ERR_INVALID_ARGUMENT, RDYN_OK, RK4, _desc, _query
-
-FRICTION1, FRICTION2, SPRING = 0, 1, 2
-
-
-def _comps(specs):
-    from rosdyn_amd._lib import Component
-    arr = (Component * max(len(specs), 1))()
-    for a, (ty, joint) in zip(arr, specs):
-        a.type, a.joint, a.min_velocity, a.max_velocity = ty, joint, 0.05, 0.8
-        a.parameters[:] = [1.0, 0.5, 0.25]
-    return arr
+from _cabi import CHUNKED, EULER, FAKE, RDYN_ERR_INVALID_ARGUMENT, RDYN_OK, RK4, SWEPT, _chain, _comps, _query, _rollout_desc as _desc
+from _components import FRICTION1, FRICTION2, SPRING
 
 
 def _rollout(chain, N, comps, n_comps, desc=True, chunk_samples=0, workspace=FAKE, workspace_bytes=None, q=FAKE, dq=FAKE, batch=True, layout=0, **kw):

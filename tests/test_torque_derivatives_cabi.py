@@ -4,11 +4,7 @@ import ctypes as C
 
 import pytest
 
-from test_forward_dynamics_cabi import CHUNKED, SWEPT, _chain
-
-RDYN_OK = 0
-RDYN_ERR_INVALID_ARGUMENT = 1
-FAKE = 4096   # never dereferenced: the checks come first
+from _cabi import CHUNKED, FAKE, RDYN_ERR_INVALID_ARGUMENT, RDYN_OK, SWEPT, _chain
 
 
 def _call(chain, n_samples, q=FAKE, dq=FAKE, ddq=FAKE, dtau_dq=FAKE, dtau_dv=FAKE, M=FAKE, batch=True, layout=0):

@@ -1,7 +1,7 @@
+from _cabi import RDYN_ERR_INVALID_ARGUMENT, RDYN_ERR_UNSUPPORTED
+
 """CPU tests (no GPU): workspace sizing and argument checks of the R factor wider than 112 columns (include/rdyn.h: rdyn_tsqr_wide,
 rdyn_tsqr_wide_last_report).  Nothing here touches a device."""
-RDYN_ERR_INVALID_ARGUMENT = 1
-RDYN_ERR_UNSUPPORTED = 5
 
 
 def test_tsqr_wide_workspace_by_width():
@@ -59,7 +59,7 @@ def test_tsqr_wide_report_of_a_narrow_width_is_route_0():
 
 
 def _rev(nj):
-    from test_gpu_longkin import generated_revolute_chain
+    from rosdyn_amd.urdf_gen import generated_revolute_chain
     from rosdyn_amd import Chain
     return Chain(generated_revolute_chain(nj, 1000 + nj), "l0", "l%d" % nj)
 
@@ -80,7 +80,7 @@ def test_tsqr_wide_workspace_fixed_joints_components_and_hand_off():
     import ctypes as C
     import os
     from conftest import FIXTURES
-    from test_gpu_longkin import generated_long_chain
+    from rosdyn_amd.urdf_gen import generated_long_chain
     from rosdyn_amd import Chain
     from rosdyn_amd._lib import lib
     from rosdyn_amd.components import FRICTION1, ComponentSet

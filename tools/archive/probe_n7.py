@@ -2,11 +2,11 @@
 """GPU probe: why do 7-joint chains write the regressor at ~5.6 TB/s where 6- and 8-joint chains reach 6.3-6.8?  N sweep, element-major."""
 import os, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, ROOT)
 from rosdyn_amd import Chain
-from test_gpu_longchain import _chain_xml
+from rosdyn_amd.urdf_gen import generated_short_chain
 for nj in (6, 7, 8):
-    c = Chain(_chain_xml(nj, 100 + nj), "l0", "l%d" % nj, (0, 0, -9.806))
+    c = Chain(generated_short_chain(nj, 100 + nj), "l0", "l%d" % nj, (0, 0, -9.806))
     n, P = c.getActiveJointsNumber(), 10 * c.getJointsNumber()
     for N in (250000, 500000, 1000000, 1048576, 1500000):
         q, dq, ddq = (torch.rand((n, N), dtype=torch.float64, device="cuda") * 2 - 1 for _ in range(3))

@@ -2,13 +2,13 @@
 """GPU probe: per-sample regressor images at padded strides (alignment classes of the copy-out), 7-joint generated chain."""
 import ctypes as C, os, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, ROOT)
 from rosdyn_amd import Chain
 from rosdyn_amd._lib import Batch, RegressorLayout, check, lib
-from test_gpu_longchain import _chain_xml
+from rosdyn_amd.urdf_gen import generated_short_chain
 N = 1000000
 for nj, pads in ((7, (0, 6, 22)), (6, (0, 8, 24))):
-    c = Chain(_chain_xml(nj, 100 + nj), "l0", "l%d" % nj, (0, 0, -9.806))
+    c = Chain(generated_short_chain(nj, 100 + nj), "l0", "l%d" % nj, (0, 0, -9.806))
     n, P = nj, 10 * nj
     q, dq, ddq = (torch.rand((N, n), dtype=torch.float64, device="cuda") * 2 - 1 for _ in range(3))
     for pad in pads:

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Host-side sanitizer run (CPU only; GPU sanitizers are not available on the pool): the URDF reader and chain ingest
-# (rdyn_urdf.cpp, rdyn_chain.cpp) under ASan + UBSan over 300 fuzzed chains (tests/test_gpu_fuzz.py generator) and 400
+# (rdyn_urdf.cpp, rdyn_chain.cpp) under ASan + UBSan over 300 fuzzed chains (the generators of tests/_fuzz.py) and 400
 # malformed variants of a fixture (truncations, byte flips, deleted / duplicated chunks); round 3: plus the rigid-body reduction of
 # every parsed chain (as parsed, with every other input joint dropped, on a clone); round 4: plus 100 chains of up to 16 joints.
 # Expected: no report.
@@ -12,7 +12,7 @@ python3 - "$ROOT" <<'PY'
 import os, random, sys
 root = sys.argv[1]
 sys.path.insert(0, os.path.join(root, "tests")); sys.path.insert(0, root)
-from test_gpu_fuzz import random_chain_xml, random_long_chain_xml
+from _fuzz import random_chain_xml, random_long_chain_xml
 os.makedirs("in", exist_ok=True)
 for s in range(300):
     xml, b, t, _ = random_chain_xml(5000 + s)

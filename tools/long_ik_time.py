@@ -20,12 +20,11 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 from oracle.oracle import OracleChain                                     # noqa: E402
 from rosdyn_amd import Chain                                              # noqa: E402
 from rosdyn_amd._lib import lib                                           # noqa: E402
 from rosdyn_amd.samples import uniform_pm1                                # noqa: E402
-from test_gpu_longkin import generated_long_chain, generated_revolute_chain  # noqa: E402
+from rosdyn_amd.urdf_gen import generated_long_chain, generated_revolute_chain  # noqa: E402
 from tools.probe import timeit                                            # noqa: E402
 
 lines = []

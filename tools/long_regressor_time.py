@@ -8,9 +8,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 from rosdyn_amd import Chain                     # noqa: E402
-from test_gpu_longkin import generated_revolute_chain  # noqa: E402
+from rosdyn_amd.urdf_gen import generated_revolute_chain  # noqa: E402
 from tools.probe import timeit                   # noqa: E402
 
 print("%-44s %10s %12s %10s" % ("call", "us / call", "B / eval", "GB/s"))

@@ -4,12 +4,11 @@ partial lines: 8 joints = 5 120-byte images = 40 whole lines)."""
 import os, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 from rosdyn_amd import Chain
-from test_gpu_longchain import _chain_xml
+from rosdyn_amd.urdf_gen import generated_short_chain
 N = 1000000
 for nj in (4, 6, 7, 8):
-    c = Chain(_chain_xml(nj, 100 + nj), "l0", "l%d" % nj, (0, 0, -9.806))
+    c = Chain(generated_short_chain(nj, 100 + nj), "l0", "l%d" % nj, (0, 0, -9.806))
     n, P = c.getActiveJointsNumber(), 10 * c.getJointsNumber()
     q, dq, ddq = (torch.rand((N, n), dtype=torch.float64, device="cuda") * 2 - 1 for _ in range(3))
     qe, dqe, ddqe = (x.t().contiguous() for x in (q, dq, ddq))

@@ -10,7 +10,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-import test_dynamics_workspace_sizes as t                                 # noqa: E402
+import _cabi as t                                                        # noqa: E402
 
 if __name__ == "__main__":
     dst = sys.argv[1] if len(sys.argv) > 1 else t.GOLDEN_FILE

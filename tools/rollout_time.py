@@ -46,10 +46,9 @@ def run_case(name, N, integrator):
     import numpy as np
     import torch
     sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
     from rosdyn_amd import Chain
     from rosdyn_amd._lib import lib
-    from test_gpu_longkin import generated_revolute_chain
+    from rosdyn_amd.urdf_gen import generated_revolute_chain
     fixtures, grav = os.path.join(ROOT, "tests", "fixtures"), (0.0, 0.0, -9.806)
     if name == "ur10_like":
         chain = Chain(os.path.join(fixtures, "ur10_like.urdf"), "base_link", "wrist_3_link", grav)

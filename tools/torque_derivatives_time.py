@@ -24,10 +24,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 from rosdyn_amd import Chain                                              # noqa: E402
 from rosdyn_amd._lib import lib                                           # noqa: E402
-from test_gpu_longkin import generated_revolute_chain                     # noqa: E402
+from rosdyn_amd.urdf_gen import generated_revolute_chain                     # noqa: E402
 
 FIXTURES = os.path.join(ROOT, "tests", "fixtures")
 GRAV = (0.0, 0.0, -9.806)

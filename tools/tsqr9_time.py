@@ -7,14 +7,13 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 from rosdyn_amd import Chain                 # noqa: E402
 from tools.probe import timeit               # noqa: E402
-from test_gpu_longchain import _chain_xml    # noqa: E402
+from rosdyn_amd.urdf_gen import generated_short_chain    # noqa: E402
 
 N = 1000000
 for nj in (9, 10):
-    chain = Chain(_chain_xml(nj, 300 + nj), "l0", "l%d" % nj, (0.3, -0.4, -9.7))
+    chain = Chain(generated_short_chain(nj, 300 + nj), "l0", "l%d" % nj, (0.3, -0.4, -9.7))
     q, dq, ddq = (torch.rand((N, nj), dtype=torch.float64, device="cuda") * 2 - 1 for _ in range(3))
     tau = chain.getJointTorque(q, dq, ddq)
     t = timeit(lambda: chain.getRegressorTsqr(q, dq, ddq, tau), reps=3, warm=1)

@@ -12,10 +12,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 from rosdyn_amd import Chain                     # noqa: E402
 from rosdyn_amd.gram import gram, gram_wide       # noqa: E402
-from test_gpu_longkin import generated_revolute_chain  # noqa: E402
+from rosdyn_amd.urdf_gen import generated_revolute_chain  # noqa: E402
 from tools.probe import timeit                   # noqa: E402
 
 PEAK, ISSUE = 78.6, 58.0   # TFLOP/s: datasheet fp64 matrix; measured back-to-back issue ceiling at one wave per SIMD (tools/fp64_issue.hip)
