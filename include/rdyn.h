@@ -519,6 +519,65 @@ size_t rdyn_rollout_ext_workspace_bytes(const rdyn_chain* chain, const rdyn_roll
 int rdyn_rollout_ext(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_rollout_desc* desc, const rdyn_component* comps,
                      int n_comps, const rdyn_ext_wrenches* ext, int64_t chunk_samples, void* workspace, size_t workspace_bytes);
 
+/* Closed-loop rollouts (no reference counterpart): rdyn_rollout_ext with a joint-space PD controller and actuator limits in the loop.  A
+ * feedback torque depends on the state, so like the components it cannot be folded into tau across steps.  n = the number of active
+ * joints; every array of rdyn_feedback is in INPUT order.  At an evaluation with state (q, Dq) in step t, per sample and joint j,
+ *     u_j = fma(kd_j, Dq_ref[t]_j - Dq_j, fma(kp_j, q_ref[t]_j - q_j, tau_ff[t]_j))        (this order, on every route)
+ *     u_j = u_j > lim_j ? lim_j : (u_j < -lim_j ? -lim_j : u_j)                             (only with tau_limit)
+ *     DDq = FD_E(q, Dq, u, ext_t)
+ * tau_ff is the descriptor's tau sequence, unchanged in meaning: it is now the feed-forward term.  FD_E is the function of
+ * rdyn_rollout_ext: the clamp acts on the actuator command alone, component and wrench torques are applied behind it as before.  The
+ * clamp is two comparisons, so a NaN command stays NaN.  kd == NULL: the velocity term is not formed and dq_ref is not read; dq_ref ==
+ * NULL with kd: Dq_ref = 0.
+ *   hold = 1   the digital controller: the command is formed once per step from the state at the start of the step and held over all
+ *              stages of the step, exactly as tau_t is held.
+ *   hold = 0   the continuous law: the command is formed anew at every integrator stage at that stage's own (q, Dq), as the components
+ *              are (RK4: the stage state and the stage velocity).
+ * Semi-implicit Euler has one evaluation per step, at the start state: the two modes are the same computation and give the same bits.
+ * References: step t at q_ref + t * ref_step_stride (and dq_ref likewise), addressed like batch->q; ref_step_stride = 0 is a constant
+ * set point.  Gains: gains_per_sample = 0: kp, kd hold n values shared by all samples; 1: addressed like batch->q.  tau_limit: n values,
+ * shared; positive values are the caller's business.
+ * tau_traj (optional output, layout of batch->q): record k, at + k * desc->traj_step_stride, holds the command u of the FIRST evaluation of
+ * step (k + 1) * traj_every - 1 -- the step whose end state is state record k; under hold = 1 that is the command of the whole step.  It
+ * counts as an output for the "every output is null" rule and needs traj_every >= 1 and the stride condition of the state trajectories.
+ * A sample whose status was already -1 when the step began gets quiet NaN; in the step at which a sample fails the record holds the
+ * command that was applied (NaN by propagation where a NaN input caused the failure).
+ * fb == NULL IS rdyn_rollout_ext: the same kernels, the same bits, the same workspace query.  ext == NULL (or ext->w == NULL) and
+ * n_comps = 0 behave as in rdyn_rollout_ext.  Sticky status, aliasing of the end state, trajectory records and independence from the chunk
+ * size are rdyn_rollout's.  A horizon split anywhere into chained calls gives the same bits: the later call starts its references at
+ * + t0 * ref_step_stride, as it does for torques and wrenches.
+ * Status: a non-finite entry of a reference, a gain or a limit follows the rule of non-finite wrenches (rdyn_rollout_ext): the command and
+ * with it the state become NaN by propagation, the NaN state fails the pivot rule at the next evaluation, so the sample's status is -1 and
+ * its state quiet NaN from then on (unless the entry was first read in the last evaluation of the horizon: NaN end state, status 1).
+ * Neighbouring samples are untouched.
+ * Chains swept in registers (rdyn_rollout's rule; with wrenches rdyn_rollout_ext's): still ONE launch for the horizon, no workspace.
+ * The chunked route: one element-wise launch forms u before the pass of every evaluation whose command is formed anew (once per step
+ * under hold = 1, once per stage under hold = 0) into one more state array of the workspace:
+ *     rdyn_rollout_feedback_workspace_bytes = rdyn_rollout_ext_workspace_bytes + align256(n * n_samples * sizeof(double))
+ * (align256 rounds up to a multiple of 256 bytes; 0 stays 0 where the ext query answers 0).
+ * Errors, all RDYN_ERR_INVALID_ARGUMENT before any device work: every argument error of rdyn_rollout_ext; NULL q_ref or NULL kp; a
+ * negative ref_step_stride or a non-zero one below n * n_samples; hold or gains_per_sample outside {0, 1}; tau_traj without traj_every >= 1
+ * and traj_step_stride >= n * n_samples.  n_samples = 0 is RDYN_OK.  No allocation and no synchronisation: capturable into a graph once
+ * the chain has been used on the device.
+ * Reverse mode: rdyn_rollout_adjoint does not transpose the feedback law, and rosdyn_amd.autograd does not serve the closed loop yet. */
+typedef struct rdyn_feedback
+{
+  const double* q_ref;        /* step t at q_ref + t * ref_step_stride, addressed like batch->q; required */
+  const double* dq_ref;       /* same addressing; NULL = zero */
+  int64_t ref_step_stride;    /* doubles; 0 = a constant set point; otherwise >= n * n_samples */
+  const double* kp;           /* required */
+  const double* kd;           /* NULL = zero (dq_ref is then not read) */
+  int32_t gains_per_sample;   /* 0: kp, kd hold n values in input order, shared by all samples; 1: addressed like batch->q */
+  int32_t hold;               /* 1: the command of the step's start state serves the whole step; 0: formed at every stage */
+  const double* tau_limit;    /* n values in input order; NULL = no limit */
+  double* tau_traj;           /* optional output: the command records, see above */
+} rdyn_feedback;
+size_t rdyn_rollout_feedback_workspace_bytes(const rdyn_chain* chain, const rdyn_rollout_desc* desc, const rdyn_ext_wrenches* ext,
+                                             const rdyn_feedback* fb, int64_t n_samples, int64_t chunk_samples);
+int rdyn_rollout_feedback(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_rollout_desc* desc, const rdyn_component* comps,
+                          int n_comps, const rdyn_ext_wrenches* ext, const rdyn_feedback* fb, int64_t chunk_samples, void* workspace,
+                          size_t workspace_bytes);
+
 /* Derivatives of the forward dynamics (no reference counterpart): the linearisation of DDq = FD_c(q, Dq, tau).  Per sample, with FD_c the
  * function of rdyn_forward_dynamics_components for the chain AS CONFIGURED (input-joint selection and order, locked joints, the reduced
  * companion, gravity; n_comps = 0 is rdyn_forward_dynamics),

@@ -51,6 +51,11 @@ class ExtWrenches(C.Structure):
     _fields_ = [("w", C.c_void_p), ("link", C.c_int32), ("step_stride", C.c_int64)]
 
 
+class Feedback(C.Structure):
+    _fields_ = [("q_ref", C.c_void_p), ("dq_ref", C.c_void_p), ("ref_step_stride", C.c_int64), ("kp", C.c_void_p), ("kd", C.c_void_p),
+                ("gains_per_sample", C.c_int32), ("hold", C.c_int32), ("tau_limit", C.c_void_p), ("tau_traj", C.c_void_p)]
+
+
 class ExtWrenchGradient(C.Structure):
     _fields_ = [("gw", C.c_void_p), ("step_stride", C.c_int64)]
 
@@ -129,6 +134,10 @@ SYMBOLS = {
     "rdyn_forward_dynamics_ext": (_I, [_VP, _BP, _VP, _I, C.POINTER(ExtWrenches), _VP, _VP, _VP, C.c_int64, _VP, C.c_size_t]),
     "rdyn_rollout_ext_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(RolloutDesc), C.POINTER(ExtWrenches), C.c_int64, C.c_int64]),
     "rdyn_rollout_ext": (_I, [_VP, _BP, C.POINTER(RolloutDesc), _VP, _I, C.POINTER(ExtWrenches), C.c_int64, _VP, C.c_size_t]),
+    "rdyn_rollout_feedback_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(RolloutDesc), C.POINTER(ExtWrenches), C.POINTER(Feedback), C.c_int64,
+                                                           C.c_int64]),
+    "rdyn_rollout_feedback": (_I, [_VP, _BP, C.POINTER(RolloutDesc), _VP, _I, C.POINTER(ExtWrenches), C.POINTER(Feedback), C.c_int64, _VP,
+                                   C.c_size_t]),
     "rdyn_joint_torque_derivatives": (_I, [_VP, _BP, _VP, _VP, _VP]),
     "rdyn_forward_dynamics_derivatives_workspace_bytes": (C.c_size_t, [_VP, C.c_int64]),
     "rdyn_forward_dynamics_derivatives": (_I, [_VP, _BP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP, C.c_size_t]),

@@ -429,8 +429,57 @@ class Chain(object):
                                                          status.data_ptr(), chunk_samples, *ws))
         return DDq, status
 
+    def _feedback(self, q0, feedback, steps):
+        """The rdyn_feedback of a closed-loop rollout from a rosdyn_amd.Feedback (shape rules there)"""
+        torch = _torch()
+        n, rec = self.getActiveJointsNumber(), tuple(q0.shape)
+
+        def dev(t):
+            if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or t.device != q0.device:
+                raise ValueError("inputs must be contiguous float64 CUDA tensors")
+            return t
+
+        f = _lib.Feedback()
+        strides = set()
+        for name, ref in (("q_ref", feedback.q_ref), ("dq_ref", feedback.Dq_ref)):
+            if ref is None:
+                if name == "q_ref":
+                    raise ValueError("feedback needs q_ref and kp")
+                continue
+            dev(ref)
+            if tuple(ref.shape) == rec:
+                strides.add(0)
+            elif ref.dim() == len(rec) + 1 and tuple(ref.shape[1:]) == rec and ref.shape[0] >= steps:
+                strides.add(q0.numel())
+            else:
+                raise ValueError("Input data dimensions mismatch")
+            setattr(f, name, ref.data_ptr())
+        if len(strides) != 1:
+            raise ValueError("q_ref and Dq_ref must both be per step or both constant")
+        f.ref_step_stride = strides.pop()
+        if feedback.kp is None:
+            raise ValueError("feedback needs q_ref and kp")
+        shapes = set()
+        for name, g in (("kp", feedback.kp), ("kd", feedback.kd)):
+            if g is None:
+                continue
+            dev(g)
+            if tuple(g.shape) not in ((n,), rec):
+                raise ValueError("Input data dimensions mismatch")
+            shapes.add(tuple(g.shape))
+            setattr(f, name, g.data_ptr())
+        if len(shapes) != 1:
+            raise ValueError("kp and kd must both be shared or both per sample")
+        f.gains_per_sample = 0 if shapes.pop() == (n,) else 1
+        f.hold = 1 if feedback.hold else 0
+        if feedback.tau_limit is not None:
+            if tuple(dev(feedback.tau_limit).shape) != (n,):
+                raise ValueError("Input data dimensions mismatch")
+            f.tau_limit = feedback.tau_limit.data_ptr()
+        return f
+
     def rollout(self, q0, Dq0, tau, dt, integrator="rk4", n_steps=None, layout="sample", trajectory_every=0, out=None, chunk_samples=0,
-                workspace=None, components=None, ext_wrenches=None, ext_link=None):
+                workspace=None, components=None, ext_wrenches=None, ext_link=None, feedback=None):
         """Rollout (include/rdyn.h: rdyn_rollout; no reference counterpart): n_steps integrator steps of size dt of the forward dynamics
         from (q0, Dq0), the torques held over each step.  integrator: "rk4" or "semi_implicit_euler" ("euler").
         tau: (T, N, n) for layout="sample", (T, n, N) for "element" -- n_steps defaults to T and may be smaller; or (N, n) / (n, N) with an
@@ -442,7 +491,9 @@ class Chain(object):
         stage's own state (rdyn_rollout_components).
         ext_wrenches, ext_link: None, or external link wrenches as in getJointAcceleration, evaluated at every integrator stage at the
         stage's own q (rdyn_rollout_ext): one record -- (N, links, 6) / (links * 6, N), or (N, 6) / (6, N) with ext_link -- is constant
-        over the horizon; a leading dimension T makes the sequence per step, held over each step like the torques."""
+        over the horizon; a leading dimension T makes the sequence per step, held over each step like the torques.
+        feedback: None, or a rosdyn_amd.Feedback: the closed loop (rdyn_rollout_feedback), tau its feed-forward term.  With
+        feedback.command_trajectory and trajectory_every >= 1 the command trajectory is appended as the last returned tensor."""
         torch = _torch()
         b, N, lay = self._batch(layout, q0, Dq0)
         if integrator not in _lib.INTEGRATORS:
@@ -475,14 +526,25 @@ class Chain(object):
             d.q_traj, d.dq_traj = q_traj.data_ptr(), dq_traj.data_ptr()
             d.traj_step_stride, d.traj_every = q0.numel(), int(trajectory_every)
         ext = self._ext_wrenches(q0, N, lay, ext_wrenches, ext_link, steps=int(n_steps)) if ext_wrenches is not None else None
-        if ext is not None:
+        fb = tau_traj = None
+        if feedback is not None:
+            fb = self._feedback(q0, feedback, int(n_steps))
+            if feedback.command_trajectory and trajectory_every:
+                tau_traj = torch.empty_like(q_traj)
+                fb.tau_traj = tau_traj.data_ptr()
+            ext_p = C.byref(ext) if ext is not None else None
+            nbytes = lib().rdyn_rollout_feedback_workspace_bytes(self._h, C.byref(d), ext_p, C.byref(fb), N, chunk_samples)
+        elif ext is not None:
             nbytes = lib().rdyn_rollout_ext_workspace_bytes(self._h, C.byref(d), C.byref(ext), N, chunk_samples)
         else:
             nbytes = lib().rdyn_rollout_workspace_bytes(self._h, C.byref(d), N, chunk_samples)
         if workspace is None and nbytes > 0:
             workspace = torch.empty((nbytes,), dtype=torch.uint8, device=q0.device)
         ws = (workspace.data_ptr() if workspace is not None else None, workspace.numel() if workspace is not None else 0)
-        if ext is not None:
+        if fb is not None:
+            comps, n_comps = self._component_list(components) if components is not None else (None, 0)
+            check(lib().rdyn_rollout_feedback(self._h, C.byref(b), C.byref(d), comps, n_comps, ext_p, C.byref(fb), chunk_samples, *ws))
+        elif ext is not None:
             comps, n_comps = self._component_list(components) if components is not None else (None, 0)
             check(lib().rdyn_rollout_ext(self._h, C.byref(b), C.byref(d), comps, n_comps, C.byref(ext), chunk_samples, *ws))
         elif components is None:
@@ -490,6 +552,8 @@ class Chain(object):
         else:
             comps, n_comps = self._component_list(components)
             check(lib().rdyn_rollout_components(self._h, C.byref(b), C.byref(d), comps, n_comps, chunk_samples, *ws))
+        if tau_traj is not None:
+            return q_end, dq_end, status, q_traj, dq_traj, tau_traj
         if trajectory_every:
             return q_end, dq_end, status, q_traj, dq_traj
         return q_end, dq_end, status

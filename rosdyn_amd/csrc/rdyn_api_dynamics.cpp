@@ -1,5 +1,6 @@
 // rdyn_api_dynamics.cpp -- the forward-dynamics family of the C-ABI (include/rdyn.h): rdyn_forward_dynamics(_components),
-// rdyn_rollout(_components), their forms with external link wrenches rdyn_forward_dynamics_ext and rdyn_rollout_ext,
+// rdyn_rollout(_components), their forms with external link wrenches rdyn_forward_dynamics_ext and rdyn_rollout_ext, the closed loop
+// rdyn_rollout_feedback,
 // rdyn_forward_dynamics_derivatives, rdyn_forward_dynamics_vjp, rdyn_rollout_adjoint, their parameter-gradient
 // forms rdyn_forward_dynamics_parameter_vjp and rdyn_rollout_adjoint_parameters, their forms with external link wrenches
 // rdyn_forward_dynamics_vjp_ext and rdyn_rollout_adjoint_ext, and the workspace queries.
@@ -44,7 +45,7 @@ struct StateLayout
   size_t first, stride, count, st_stage, st_run, total;
   double* array(void* workspace, size_t i) const { return i < count ? (double*)((char*)workspace + first + i * stride) : nullptr; }
 };
-// rollout: q | dq | ddq and for RK4 sq | sv | aq | av
+// rollout: q | dq | ddq and for RK4 sq | sv | aq | av; the closed loop: + u, the command of the evaluation, behind them
 struct RolloutLayout { FwdLayout f; StateLayout s; };
 // adjoint: lq | lv | mu | qb | vb | tb and for RK4 xq | xv | kq | kv | gt | x2q | x2v | x3q | x3v | x4q | x4v | acc
 struct AdjointLayout { VjpLayout v; StateLayout s; };
@@ -98,12 +99,13 @@ static StateLayout state_layout(size_t first, size_t count, const rdyn_chain* c,
   return s;
 }
 
-static RolloutLayout rollout_layout(const rdyn_chain* c, const rdyn_rollout_desc* d, int64_t n_samples, int64_t chunk_samples, bool ext = false)
+static RolloutLayout rollout_layout(const rdyn_chain* c, const rdyn_rollout_desc* d, int64_t n_samples, int64_t chunk_samples, bool ext = false,
+                                    bool fb = false)
 {
   RolloutLayout L = {};
   if (!d || n_samples < 0) return L;
   L.f = fwd_layout(c, chunk_samples, ext);
-  L.s = state_layout(L.f.total, d->integrator == RDYN_INTEGRATOR_RK4 ? 7 : 3, c, n_samples);
+  L.s = state_layout(L.f.total, (d->integrator == RDYN_INTEGRATOR_RK4 ? 7 : 3) + (fb ? 1 : 0), c, n_samples);
   return L;
 }
 
@@ -364,9 +366,13 @@ static int forward_dynamics(const rdyn_chain* c, const rdyn_batch* b, const rdyn
 // ---- rollouts: T integrator steps of the forward dynamics (rdyn_rollout.hip) ------------------------------------
 // Chains the unrolled kernels sweep: one launch for the whole horizon.  More input joints: per stage the chunked forward dynamics above,
 // then k_rollout_stage on the state arrays of RolloutLayout.
-// who = the entry point (error texts); comps with n_comps = 0 is the plain call: the same kernels; ext null, or without w: no wrenches
+// who = the entry point (error texts); comps with n_comps = 0 is the plain call: the same kernels; ext null, or without w: no wrenches;
+// fb null: open loop.  Otherwise the closed loop (rdyn_rollout_fb.hip): one launch of k_rollout_fb, or on the chunked route
+// k_rollout_command before the pass of every evaluation whose command is formed anew (hold: the step's first), the pass taking the command
+// array of the workspace where it took tau_t.
 static int rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_desc* d, const rdyn_component* comps, int n_comps,
-                   const rdyn_ext_wrenches* ext, int64_t chunk_samples, void* workspace, size_t workspace_bytes, const char* who)
+                   const rdyn_ext_wrenches* ext, int64_t chunk_samples, void* workspace, size_t workspace_bytes, const char* who,
+                   const rdyn_feedback* fb = nullptr)
 {
   int st = check_batch(c, b, true, false, who, LONG_KERNELS);
   if (st != RDYN_OK) return st;
@@ -375,14 +381,27 @@ static int rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_
   const int64_t N = b->n_samples;
   st = check_integration(d->n_steps, d->dt, d->integrator, d->tau, who);
   if (st != RDYN_OK) return st;
-  const bool traj = d->q_traj || d->dq_traj;
+  double* const tau_traj = fb ? fb->tau_traj : nullptr;
+  const bool traj = d->q_traj || d->dq_traj || tau_traj;
   if (N > 0 && !d->q_end && !d->dq_end && !traj) return refuse(who, "every output is null");
   if (traj && (d->traj_every < 1 || d->traj_step_stride < (int64_t)n * N))
     return refuse(who, "a trajectory needs traj_every >= 1 and traj_step_stride >= n * n_samples");
   RdynExtArgs x;
   st = check_ext(c, b, ext, true, who, &x);
   if (st != RDYN_OK) return st;
-  const RolloutLayout L = rollout_layout(c, d, N, chunk_samples, x.w != nullptr);
+  if (fb)
+  {
+    if (!fb->q_ref || !fb->kp) return refuse(who, "null reference (q_ref) or gain (kp) pointer");
+    if (fb->ref_step_stride < 0 || (fb->ref_step_stride != 0 && fb->ref_step_stride < (int64_t)n * N))
+    {
+      rdyn_set_error("%s: ref_step_stride %lld is negative, or not zero and smaller than one step's record (%lld doubles)", who,
+                     (long long)fb->ref_step_stride, (long long)((int64_t)n * N));
+      return RDYN_ERR_INVALID_ARGUMENT;
+    }
+    if ((fb->hold != 0 && fb->hold != 1) || (fb->gains_per_sample != 0 && fb->gains_per_sample != 1))
+      return refuse(who, "hold and gains_per_sample are 0 or 1");
+  }
+  const RolloutLayout L = rollout_layout(c, d, N, chunk_samples, x.w != nullptr, fb != nullptr);
   DynCall k;
   st = dyn_prepare(c, b, comps, n_comps, chunk_samples, L.s.total, workspace, workspace_bytes, who, &k, x.w != nullptr);
   if (st != RDYN_OK || !k.run) return st;
@@ -412,7 +431,26 @@ static int rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_
     a.n_active = n;
     // whole lines: every record of the kind starts on a line (the trajectory's step stride keeps the alignment of its first record)
     if ((d->q_end || d->dq_end) && stage_records(b, d->q_end, d->dq_end)) a.staged |= 1;
-    if (traj && stage_records(b, d->q_traj, d->dq_traj) && (d->traj_step_stride * (int64_t)sizeof(double)) % 128 == 0) a.staged |= 2;
+    if (traj && stage_records(b, d->q_traj, d->dq_traj, tau_traj) && (d->traj_step_stride * (int64_t)sizeof(double)) % 128 == 0) a.staged |= 2;
+    if (fb)
+    {
+      RdynRolloutFbArgs af;
+      memset(&af, 0, sizeof af);
+      af.e.c.r = a;
+      af.e.c.t = k.table;
+      af.e.x = x;
+      af.f.q_ref = fb->q_ref;
+      af.f.dq_ref = fb->dq_ref;
+      af.f.ref_step = fb->ref_step_stride;
+      af.f.kp = fb->kp;
+      af.f.kd = fb->kd;
+      af.f.lim = fb->tau_limit;
+      af.f.tau_traj = tau_traj;
+      af.f.per_sample = fb->gains_per_sample;
+      af.f.hold = fb->hold;
+      RDYN_HIP_TRY(rdyn_launch_rollout_feedback(k.sw->n_joints(), af, k.stream));
+      return RDYN_OK;
+    }
     if (x.w)
     {
       RdynRolloutExtArgs ae;
@@ -437,7 +475,8 @@ static int rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_
   int32_t* const st_stage = (int32_t*)((char*)workspace + L.s.st_stage);
   int32_t* const st_run = (int32_t*)((char*)workspace + L.s.st_run);
   double *const q = L.s.array(workspace, 0), *const dq = L.s.array(workspace, 1), *const ddq = L.s.array(workspace, 2);
-  double *const sq = L.s.array(workspace, 3), *const sv = L.s.array(workspace, 4);
+  const bool rk4 = d->integrator == RDYN_INTEGRATOR_RK4;  // (Euler has no stage arrays: with the closed loop, array 3 is the command)
+  double *const sq = rk4 ? L.s.array(workspace, 3) : nullptr, *const sv = rk4 ? L.s.array(workspace, 4) : nullptr;
   RdynRolloutCopyArgs ca;
   memset(&ca, 0, sizeof ca);
   ca.q_src = b->q;
@@ -454,8 +493,8 @@ static int rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_
   sa.dq = dq;
   sa.sq = sq;
   sa.sv = sv;
-  sa.aq = L.s.array(workspace, 5);
-  sa.av = L.s.array(workspace, 6);
+  sa.aq = rk4 ? L.s.array(workspace, 5) : nullptr;
+  sa.av = rk4 ? L.s.array(workspace, 6) : nullptr;
   sa.ddq = ddq;
   sa.st_stage = st_stage;
   sa.st_run = st_run;
@@ -466,15 +505,41 @@ static int rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_
   sa.integrator = d->integrator;
   sa.dt = d->dt;
   const int stages = d->integrator == RDYN_INTEGRATOR_RK4 ? 4 : 1;
+  RdynRolloutCommandArgs fa;
+  memset(&fa, 0, sizeof fa);
+  if (fb)
+  {
+    fa.kp = fb->kp;
+    fa.kd = fb->kd;
+    fa.lim = fb->tau_limit;
+    fa.u = L.s.array(workspace, L.s.count - 1);
+    fa.st_run = st_run;
+    fa.count = count;
+    fa.n_samples = N;
+    fa.n = n;
+    fa.element_major = sa.element_major;
+    fa.per_sample = fb->gains_per_sample;
+  }
   for (int t = 0; t < d->n_steps; ++t)
   {
-    const double* const tau_t = d->tau + (int64_t)t * d->tau_step_stride;
+    const double* const tau_ff = d->tau + (int64_t)t * d->tau_step_stride;
+    const double* const tau_t = fb ? fa.u : tau_ff;  // what the passes of the step take as their torques
     RdynExtArgs xt = x;  // the step's wrenches, held over its stages
     if (x.w) xt.w = x.w + (int64_t)t * x.step;
     const bool due = every > 0 && (t + 1) % every == 0;
     const int64_t rec = due ? ((t + 1) / every - 1) * d->traj_step_stride : 0;
     for (int stage = 0; stage < stages; ++stage)
     {
+      if (fb && (stage == 0 || !fb->hold))
+      {
+        fa.q = stage ? sq : q;
+        fa.dq = stage ? sv : dq;
+        fa.tau_ff = tau_ff;
+        fa.q_ref = fb->q_ref + (int64_t)t * fb->ref_step_stride;
+        fa.dq_ref = fb->dq_ref ? fb->dq_ref + (int64_t)t * fb->ref_step_stride : nullptr;
+        fa.rec = (stage == 0 && due && tau_traj) ? tau_traj + rec : nullptr;
+        RDYN_HIP_TRY(rdyn_launch_rollout_command(fa, k.stream));
+      }
       st = fwd_dyn_chunks(c, stage ? sq : q, stage ? sv : dq, tau_t, ddq, st_stage, N, k.in_ss, k.in_sj, L.f.chunk, (double*)workspace, k.stream,
                           k.comps, x.w ? &xt : nullptr);  // components and wrenches see the stage state
       if (st != RDYN_OK) return st;
@@ -664,6 +729,19 @@ size_t rdyn_rollout_ext_workspace_bytes(const rdyn_chain* c, const rdyn_rollout_
                                         int64_t chunk_samples)
 {
   return rollout_layout(c, d, n_samples, chunk_samples, ext && ext->w).s.total;
+}
+
+size_t rdyn_rollout_feedback_workspace_bytes(const rdyn_chain* c, const rdyn_rollout_desc* d, const rdyn_ext_wrenches* ext,
+                                             const rdyn_feedback* fb, int64_t n_samples, int64_t chunk_samples)
+{
+  return rollout_layout(c, d, n_samples, chunk_samples, ext && ext->w, fb != nullptr).s.total;
+}
+
+int rdyn_rollout_feedback(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_desc* d, const rdyn_component* comps, int n_comps,
+                          const rdyn_ext_wrenches* ext, const rdyn_feedback* fb, int64_t chunk_samples, void* workspace,
+                          size_t workspace_bytes)
+{
+  return rollout(c, b, d, comps, n_comps, ext, chunk_samples, workspace, workspace_bytes, "rdyn_rollout_feedback", fb);
 }
 
 int rdyn_rollout_ext(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_desc* d, const rdyn_component* comps, int n_comps,

@@ -598,6 +598,37 @@ struct RdynRolloutExtArgs
 };
 hipError_t rdyn_launch_rollout_ext(int n_joints, const RdynRolloutExtArgs& a, hipStream_t st);
 
+// closed-loop rollouts (rdyn_rollout_fb.hip): the evaluation's actuator torque is the command of a joint-space PD law,
+//     u = fma(kd, dq_ref - dq, fma(kp, q_ref - q, tau_ff)),  then clamped to +-lim by comparisons (a NaN command stays NaN),
+// tau_ff the torque sequence of RdynRolloutArgs; components and wrenches are applied behind the clamp.  Every array is in input order.
+struct RdynFeedbackArgs
+{
+  const double *q_ref, *dq_ref;  // step t at + t * ref_step, addressed like q; dq_ref null: zero
+  int64_t ref_step;              // doubles between the references of consecutive steps (0: a constant set point)
+  const double *kp, *kd;         // per_sample 0: n values shared by all samples; 1: addressed like q.  kd null: no velocity term
+  const double* lim;             // n values, may be null: no clamp
+  double* tau_traj;              // may be null: record k = the command of the first evaluation of step (k + 1) traj_every - 1, at + k * traj_step
+  int per_sample, hold;          // hold 1: the command of the step's first evaluation serves the whole step; 0: formed at every stage
+};
+struct RdynRolloutFbArgs
+{
+  RdynRolloutExtArgs e;  // e.x.w null: no wrenches (the kernels without the wrench path)
+  RdynFeedbackArgs f;
+};
+hipError_t rdyn_launch_rollout_feedback(int n_joints, const RdynRolloutFbArgs& a, hipStream_t st);
+// ... of a chain on the chunked route: the command of one evaluation, one thread per double of the (contiguous) arrays in the batch's
+// layout.  q, dq = the state the evaluation runs at; tau_ff, q_ref, dq_ref = the step's; u = the workspace array the pass takes as its
+// torques; rec = the command record that is due (null: none; a sample whose running status is below 0 gets quiet NaN).
+struct RdynRolloutCommandArgs
+{
+  const double *q, *dq, *tau_ff, *q_ref, *dq_ref, *kp, *kd, *lim;
+  double *u, *rec;
+  const int32_t* st_run;
+  int64_t count, n_samples;
+  int n, element_major, per_sample;
+};
+hipError_t rdyn_launch_rollout_command(const RdynRolloutCommandArgs& a, hipStream_t st);
+
 // reverse-mode product of the forward dynamics (rdyn_fwd_dyn_vjp.hip): with ddq = FD_c(q, dq, tau) and the seed ddq_bar per sample,
 // tau_bar = M^-1 ddq_bar, q_bar = dddq_dq' ddq_bar, dq_bar = dddq_dv' ddq_bar (the matrices of RdynFwdDynDerivArgs).  Every vector is
 // addressed like q; any output may be null (not all three of the products); tau_bar may alias ddq_bar.

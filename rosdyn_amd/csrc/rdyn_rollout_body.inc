@@ -5,6 +5,13 @@
 // RDYN_ROLLOUT_EVAL(c, q, dq, rhs): the evaluation, fwd_dyn_eval<NJ> but with external wrenches (rdyn_rollout_ext.hip), whose kernel also
 // fills RDYN_ROLLOUT_TAKE (statements run where rhs takes its copy of the step's torques, the step t in scope: the step's wrench is taken
 // the same way) and RDYN_ROLLOUT_PREFETCH (statements run where the torques of step t + 1 are requested); both empty everywhere else.
+// RDYN_ROLLOUT_HEAD: optional, statements run at the head of step t, before its first evaluation, with the step's start state in q, dq,
+// its torques in tau and alive, due, rec_off, sm, stg_traj in scope: the closed-loop kernel (rdyn_rollout_fb.hip) forms the held command
+// into tau there and writes the command record that is due.  Empty unless the including kernel defines it.
+#ifndef RDYN_ROLLOUT_HEAD
+#define RDYN_ROLLOUT_HEAD
+#define RDYN_ROLLOUT_HEAD_DEFAULTED
+#endif
   const ChainPtr c = as_const(a.chain);
   const int lane = threadIdx.x;
   const int64_t s_wave = (int64_t)blockIdx.x * 64;
@@ -55,6 +62,7 @@
     const bool more = t + 1 < T;
     tp += a.tau_step;
     bool ok = true;
+    RDYN_ROLLOUT_HEAD
     if (INTEGRATOR == RDYN_INTEGRATOR_SEMI_IMPLICIT_EULER)
     {
       double rhs[NJ];
@@ -145,3 +153,7 @@
   if (a.status) a.status[s] = alive ? 1 : -1;
   if (a.q_end) put_record<NJ>(c, sm, stg_end, q, a.q_end + s_wave * a.in_ss, a.q_end + s * a.in_ss, a.in_sj, lane);
   if (a.dq_end) put_record<NJ>(c, sm, stg_end, dq, a.dq_end + s_wave * a.in_ss, a.dq_end + s * a.in_ss, a.in_sj, lane);
+#ifdef RDYN_ROLLOUT_HEAD_DEFAULTED
+#undef RDYN_ROLLOUT_HEAD
+#undef RDYN_ROLLOUT_HEAD_DEFAULTED
+#endif

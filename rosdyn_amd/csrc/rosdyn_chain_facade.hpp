@@ -947,6 +947,20 @@ public:
     chk(rdyn_rollout_ext(m_h, &b, &desc, comps.empty() ? nullptr : comps.data(), (int)comps.size(), &ext, chunk_samples, workspace,
                          workspace_bytes));
   }
+  // ... in closed loop: a joint-space PD law with actuator limits around desc.tau, which becomes the feed-forward term
+  // (rdyn_rollout_feedback; every pointer of fb a device pointer, in input order; fb.hold = 1 holds the command over a step, 0 forms it
+  // at every stage).  The wrenches go by pointer: nullptr = none; comps may be empty.
+  size_t rolloutWorkspaceBytes(const rdyn_rollout_desc& desc, const rdyn_ext_wrenches* ext, const rdyn_feedback& fb, int64_t n_samples,
+                               int64_t chunk_samples = 0) const
+  {
+    return rdyn_rollout_feedback_workspace_bytes(m_h, &desc, ext, &fb, n_samples, chunk_samples);
+  }
+  void rolloutBatch(const std::vector<rdyn_component>& comps, const rdyn_ext_wrenches* ext, const rdyn_feedback& fb, const rdyn_batch& b,
+                    const rdyn_rollout_desc& desc, int64_t chunk_samples, void* workspace, size_t workspace_bytes) const
+  {
+    chk(rdyn_rollout_feedback(m_h, &b, &desc, comps.empty() ? nullptr : comps.data(), (int)comps.size(), ext, &fb, chunk_samples, workspace,
+                              workspace_bytes));
+  }
   // adjoint of a rollout of a batch (b.q, b.dq = the forward call's initial state; every pointer of desc a device pointer in the layout of
   // b.q; comps may be empty): the gradients with respect to the initial state and the torques from the seeds on the end state and on the
   // trajectory records, both integrators: rdyn_rollout_adjoint
