@@ -559,7 +559,9 @@ int rdyn_rollout_ext(const rdyn_chain* chain, const rdyn_batch* batch, const rdy
  * negative ref_step_stride or a non-zero one below n * n_samples; hold or gains_per_sample outside {0, 1}; tau_traj without traj_every >= 1
  * and traj_step_stride >= n * n_samples.  n_samples = 0 is RDYN_OK.  No allocation and no synchronisation: capturable into a graph once
  * the chain has been used on the device.
- * Reverse mode: rdyn_rollout_adjoint does not transpose the feedback law, and rosdyn_amd.autograd does not serve the closed loop yet. */
+ * Reverse mode: rdyn_rollout_adjoint_feedback (below) is the transpose of this call, the law included, for the chains this call runs
+ * in registers, and rosdyn_amd.autograd.rollout serves the closed loop through it.  On the chunked route it answers
+ * RDYN_ERR_UNSUPPORTED: there rosdyn_amd.autograd does not serve the closed loop yet (the follow-up named at that call). */
 typedef struct rdyn_feedback
 {
   const double* q_ref;        /* step t at q_ref + t * ref_step_stride, addressed like batch->q; required */
@@ -812,6 +814,80 @@ size_t rdyn_rollout_adjoint_ext_workspace_bytes(const rdyn_chain* chain, const r
 int rdyn_rollout_adjoint_ext(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_rollout_adjoint_desc* desc,
                              const rdyn_component* comps, int n_comps, const rdyn_ext_wrenches* ext, const rdyn_ext_wrench_gradient* gext,
                              int64_t chunk_samples, void* workspace, size_t workspace_bytes);
+
+/* Adjoint of a closed-loop rollout (no reference counterpart): the exact transpose of the scheme rdyn_rollout_feedback integrates, the
+ * PD law and its clamp included -- what gain tuning and the optimisation of references with a cost on the control effort need.  Notation
+ * of rdyn_rollout_feedback and rdyn_rollout_adjoint.  At an evaluation in step t at the state (q, v):
+ *     u_raw = fma(kd, Dq_ref_t - v, fma(kp, q_ref_t - q, tau_ff_t)),   u = clamp(u_raw, +-lim),   a = FD_E(q, v, u, ext_t)
+ * Let (q_bar, v_bar, tau_bar) = vjp_E(q, v, u; seed) be the product of rdyn_forward_dynamics_vjp_ext (rdyn_forward_dynamics_vjp without
+ * wrenches) taken at the command u; u is formed again in the backward sweep by the forward kernel's own text and carries its bits.  The
+ * mask follows the branch the forward call took: m_j = 1 where neither u_raw > lim nor u_raw < -lim (exactly at a limit the law passes
+ * through), 0 where clamped; sgn_j = +-1 on the clamped side, else 0.  The mask is a select, not a product: a clamped entry contributes
+ * +0.0.  With tot = tau_bar_total + gu (gu: the optional seed on the step's command record, below) and g = m o tot, per joint, in this
+ * order and with these roundings on every path:
+ *     q_bar = fma(-kp, g, q_bar)         v_bar = fma(-kd, g, v_bar)   (only with kd)           gtau_ff_t += g
+ *     gkp   = fma(q_ref_t - q, g, gkp)   gkd   = fma(Dq_ref_t - v, g, gkd)                     glim += sgn o tot
+ * and, once the step's gtau_ff_t is complete,   gq_ref_t = kp o gtau_ff_t,   gdq_ref_t = kd o gtau_ff_t   (kp, kd do not depend on the stage).
+ *   hold = 0 (the continuous law): this is applied at every product of the step -- RK4 stages 4 .. 1, each at its own rebuilt stage
+ *       state X_i, tau_bar_total that product's tau_bar; gu joins at the step's first evaluation only (stage 1).  The corrected
+ *       (q_bar, v_bar) enter X_bar_i exactly as the uncorrected ones do in rdyn_rollout_adjoint, g takes tau_bar's place in gtau_t.  The
+ *       stage rebuild forms the command anew at each stage state, as the forward call does.
+ *   hold = 1 (the digital controller): u = law(x_t) serves the stage rebuild and all four products; tau_bar_total is the sum of the four
+ *       stage tau_bars (rdyn_rollout_adjoint's gtau_t); the correction is applied once, at x_t, to lambda_t after the step's products.
+ * Semi-implicit Euler has one evaluation per step and is written once: the two modes give the same bits, as the forward call promises.
+ * Outputs.  desc->gtau is the gradient with respect to the FEED-FORWARD sequence (per step, or its sum with gtau_step_stride = 0); gq0,
+ * gdq0, the status, the running state seeds and gext keep the meaning they have in rdyn_rollout_adjoint_ext.  rdyn_feedback_gradient
+ * selects the law's gradients:
+ *     gq_ref, gdq_ref   step t at + t * gref_step_stride, addressed like batch->q; gref_step_stride = 0: one record, the sum over the
+ *                       steps (the gradient of a constant set point)
+ *     gkp, gkd, glim    n per SAMPLE, addressed like batch->q, summed over the steps -- ALWAYS per-sample rows, also when the forward call
+ *                       used shared gains (gains_per_sample = 0) and for the always-shared limits: the caller sums the rows over the
+ *                       samples.  A device-side reduction is deliberately out of scope.
+ *     gu_traj           optional seeds on the command record (fb->tau_traj of the forward call with traj_every = 1): record t =
+ *                       dL/d(command of step t's first evaluation), at + t * gu_step_stride
+ * Accumulation: every lane adds into its own record in memory, in the order of the backward sweep; no floating-point atomics, the same
+ * bits every run.  accumulate = 0 starts gkp, gkd, glim and the gref_step_stride = 0 sums from zero; 1 continues adding to what is there.
+ * Split horizons: a horizon split anywhere into two chained calls -- the later part first with accumulate = 0, then the earlier part
+ * with accumulate = 1, seeded by the later part's gq0 / gdq0, the later part's references (and gu_traj, torques, wrenches) starting at
+ * + t0 * their step strides -- gives the bits of the single call for EVERY output, gkp, gkd, glim included: the additions happen in the
+ * same order.
+ * Routing, decided before any device work:
+ *   fb == NULL   IS rdyn_rollout_adjoint_ext: the same kernels, the same bits, the same workspace query.  A non-NULL gfb with any
+ *                output or gu_traj in it is then RDYN_ERR_INVALID_ARGUMENT.
+ *   fb given     a chain is served when rdyn_rollout_feedback runs it in registers: at most RDYN_MAX_SWEPT_JOINTS chain joints, and
+ *                longer chains with at most that many input joints on their reduced companion when there are no wrenches.  ONE launch
+ *                for the horizon; the workspace query returns 0.
+ *   fb given and rdyn_rollout_feedback takes the chunked route for the chain: RDYN_ERR_UNSUPPORTED.
+ *                The adjoint of the chunked closed loop is the follow-up, and so are the parameter gradients of the closed loop
+ *                (rdyn_rollout_adjoint_parameters with feedback).
+ * Status: the rule of rdyn_rollout_adjoint_ext, extended to the references, gains and limits the sample reads: a non-finite entry gives
+ * -1.  From the failing backward step on every output of the sample is quiet NaN -- its reference gradients of that step and the earlier
+ * ones, and its whole gkp / gkd / glim rows and summed reference gradients.  No sample affects another.
+ * T = 0 copies the end seeds; with accumulate = 0 it writes zeros to the sums, with accumulate = 1 it leaves them as they are.
+ * Errors, all RDYN_ERR_INVALID_ARGUMENT before any device work: those of rdyn_rollout_adjoint_ext; those of rdyn_rollout_feedback
+ * concerning fb (NULL q_ref or kp, the ref_step_stride rule, hold or gains_per_sample outside {0, 1}); gkd or gdq_ref without fb->kd; glim
+ * without fb->tau_limit; a negative gref_step_stride or a non-zero one below n N (with gq_ref or gdq_ref); gu_traj with a gu_step_stride
+ * below n N; accumulate outside {0, 1}; gq0, gdq0, gtau, gw and every output of gfb NULL with samples.  n_samples = 0 is RDYN_OK.  No
+ * allocation and no synchronisation: capturable into a graph once the chain has been used on the device. */
+typedef struct rdyn_feedback_gradient
+{
+  double* gq_ref;            /* optional; step t at + t * gref_step_stride, addressed like batch->q */
+  double* gdq_ref;           /* optional, likewise; needs fb->kd */
+  int64_t gref_step_stride;  /* 0 = one record: the sum over the steps (a constant set point); otherwise >= n N */
+  double* gkp;               /* optional; n per SAMPLE, addressed like batch->q, summed over the steps */
+  double* gkd;               /* optional, likewise; needs fb->kd */
+  double* glim;              /* optional, likewise; needs fb->tau_limit */
+  int32_t accumulate;        /* 0: overwrite; 1: continue adding to what is there (gkp, gkd, glim, the stride-0 sums) */
+  const double* gu_traj;     /* optional seeds on the command record: record t = dL/d(command of step t's first evaluation) */
+  int64_t gu_step_stride;    /* >= n N when gu_traj is given */
+} rdyn_feedback_gradient;
+size_t rdyn_rollout_adjoint_feedback_workspace_bytes(const rdyn_chain* chain, const rdyn_rollout_adjoint_desc* desc,
+                                                     const rdyn_ext_wrenches* ext, const rdyn_feedback* fb, int64_t n_samples,
+                                                     int64_t chunk_samples);
+int rdyn_rollout_adjoint_feedback(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_rollout_adjoint_desc* desc,
+                                  const rdyn_component* comps, int n_comps, const rdyn_ext_wrenches* ext,
+                                  const rdyn_ext_wrench_gradient* gext, const rdyn_feedback* fb, const rdyn_feedback_gradient* gfb,
+                                  int64_t chunk_samples, void* workspace, size_t workspace_bytes);
 
 /* ---- mixed-chain batch (BASELINE.json configs[4]: 256 distinct 6-7-DOF chains x 4 096 samples) --------------
  * One launch per group of chains with equal joint count (and output-layout kind) evaluates rdyn_regressor for MANY

@@ -60,6 +60,11 @@ class ExtWrenchGradient(C.Structure):
     _fields_ = [("gw", C.c_void_p), ("step_stride", C.c_int64)]
 
 
+class FeedbackGradient(C.Structure):
+    _fields_ = [("gq_ref", C.c_void_p), ("gdq_ref", C.c_void_p), ("gref_step_stride", C.c_int64), ("gkp", C.c_void_p), ("gkd", C.c_void_p),
+                ("glim", C.c_void_p), ("accumulate", C.c_int32), ("gu_traj", C.c_void_p), ("gu_step_stride", C.c_int64)]
+
+
 class Component(C.Structure):
     _fields_ = [("type", C.c_int32), ("joint", C.c_int32), ("min_velocity", C.c_double), ("max_velocity", C.c_double),
                 ("parameters", C.c_double * 3)]
@@ -158,6 +163,11 @@ SYMBOLS = {
                                                               C.c_int64]),
     "rdyn_rollout_adjoint_ext": (_I, [_VP, _BP, C.POINTER(RolloutAdjointDesc), _VP, _I, C.POINTER(ExtWrenches),
                                       C.POINTER(ExtWrenchGradient), C.c_int64, _VP, C.c_size_t]),
+    "rdyn_rollout_adjoint_feedback_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(RolloutAdjointDesc), C.POINTER(ExtWrenches),
+                                                                   C.POINTER(Feedback), C.c_int64, C.c_int64]),
+    "rdyn_rollout_adjoint_feedback": (_I, [_VP, _BP, C.POINTER(RolloutAdjointDesc), _VP, _I, C.POINTER(ExtWrenches),
+                                           C.POINTER(ExtWrenchGradient), C.POINTER(Feedback), C.POINTER(FeedbackGradient), C.c_int64, _VP,
+                                           C.c_size_t]),
     "rdyn_local_ik": (_I, [_VP, _BP, _VP, _DP, C.c_double, _I, _VP, _VP, _VP]),
     "rdyn_local_ik_damped": (_I, [_VP, _BP, _VP, _DP, C.c_double, C.c_double, _I, _VP, _VP, _VP]),
     "rdyn_frame_distance": (_I, [C.c_int64, _VP, _VP, _I, _I, _VP, _VP, _I, _VP]),

@@ -30,11 +30,20 @@ it, differentiable) and ``ext_link``.  They run through ``JointAccelerationExtFu
 one step's record is held over the horizon and its gradient is the sum over the steps; a leading ``T`` axis means one record per step.
 Wrenches together with ``parameters`` / ``component_parameters`` raise ValueError: the parameter gradients with wrenches are the
 follow-up (include/rdyn.h).
+
+The closed loop: ``rollout`` takes ``feedback`` (a ``rosdyn_amd.Feedback``, as ``Chain.rollout`` takes it) and runs through
+``RolloutFeedbackFunction``, whose backward is ONE ``Chain.rolloutAdjoint(feedback=)`` call -- the exact transpose of the loop, the PD
+law and its clamp included.  Gradients flow to q0, Dq0, tau (now the feed-forward term) and to ``feedback.q_ref``, ``Dq_ref``, ``kp``,
+``kd`` and ``tau_limit``, whichever require grad: shared gains and the limits get the sum of the per-sample rows, a reference held over
+the horizon the sum over the steps.  With ``ext_wrenches`` the wrench gradient flows as above.  With ``feedback.command_trajectory`` the
+command trajectory (one record per step: the command of the step's first evaluation) is returned last and is differentiable: a cost
+on the control effort.  A clamped command has no slope: its gradient goes to ``tau_limit``.  ``parameters`` / ``component_parameters``
+together with ``feedback`` raise ValueError: the parameter gradients of the closed loop are the follow-up (include/rdyn.h).
 """
 import torch
 
 __all__ = ["joint_acceleration", "rollout", "JointAccelerationFunction", "RolloutFunction", "JointAccelerationParametersFunction",
-           "RolloutParametersFunction", "JointAccelerationExtFunction", "RolloutExtFunction"]
+           "RolloutParametersFunction", "JointAccelerationExtFunction", "RolloutExtFunction", "RolloutFeedbackFunction"]
 
 
 class JointAccelerationFunction(torch.autograd.Function):
@@ -223,6 +232,79 @@ class RolloutExtFunction(torch.autograd.Function):
         return (None,) * 8 + (gq0 if need[0] else None, gdq0 if need[1] else None, gtau if need[2] else None, gext)
 
 
+class RolloutFeedbackFunction(torch.autograd.Function):
+    """RolloutFunction around the closed loop: the law's references, gains and limits (and, optionally, external link wrenches) among the
+    inputs, the command trajectory (optionally) among the outputs; the backward is ONE Chain.rolloutAdjoint(feedback=) call.  Dq_ref, kd,
+    tau_limit and ext_wrenches may be None."""
+
+    NAMES = ("q_ref", "Dq_ref", "kp", "kd", "tau_limit")
+
+    @staticmethod
+    def forward(ctx, chain, components, layout, integrator, dt, n_steps, trajectory, ext_link, hold, command, q0, Dq0, tau, q_ref, Dq_ref,
+                kp, kd, tau_limit, ext_wrenches):
+        from .feedback import Feedback
+        det = lambda t: t.detach().contiguous() if t is not None else None
+        q0, Dq0, tau, q_ref, Dq_ref, kp, kd, tau_limit, w = (det(t) for t in (q0, Dq0, tau, q_ref, Dq_ref, kp, kd, tau_limit, ext_wrenches))
+        fb = Feedback(q_ref, kp, kd, Dq_ref, hold=hold, tau_limit=tau_limit, command_trajectory=command)
+        res = chain.rollout(q0, Dq0, tau, dt, integrator=integrator, n_steps=n_steps, layout=layout, trajectory_every=1, components=components,
+                            ext_wrenches=w, ext_link=ext_link, feedback=fb)
+        q_end, dq_end, q_traj, dq_traj = res[0], res[1], res[3], res[4]
+        ctx.chain, ctx.components, ctx.layout, ctx.integrator, ctx.dt, ctx.ext_link = chain, components, layout, integrator, dt, ext_link
+        ctx.n_steps, ctx.trajectory, ctx.sum_tau, ctx.hold, ctx.command = q_traj.shape[0], trajectory, tau.dim() == 2, hold, command
+        ctx.sum_ext = w is not None and w.dim() == (2 if ext_link is not None else (3 if layout == "sample" else 2))
+        ctx.present = tuple(t is not None for t in (Dq_ref, kd, tau_limit, w))
+        z = q0.new_empty((0,))
+        ctx.save_for_backward(q0, Dq0, tau, q_traj, dq_traj, q_ref, kp, *(t if t is not None else z for t in (Dq_ref, kd, tau_limit, w)))
+        out = (q_end, dq_end)
+        if trajectory:
+            out += (q_traj.clone(), dq_traj.clone())  # (the saved records must not be written to by the caller)
+        if command:
+            out += (res[5],)
+        return out
+
+    @staticmethod
+    def backward(ctx, gq_end, gdq_end, *rest):
+        from .feedback import Feedback
+        q0, Dq0, tau, q_traj, dq_traj, q_ref, kp = ctx.saved_tensors[:7]
+        Dq_ref, kd, tau_limit, w = (t if have else None for t, have in zip(ctx.saved_tensors[7:], ctx.present))
+        c = lambda t: t.contiguous() if t is not None else None
+        rest = list(rest)
+        gq_traj, gdq_traj = (rest.pop(0), rest.pop(0)) if ctx.trajectory else (None, None)
+        gu = rest.pop(0) if ctx.command else None
+        need = dict(zip(RolloutFeedbackFunction.NAMES, ctx.needs_input_grad[13:18]))
+        tensors = dict(zip(RolloutFeedbackFunction.NAMES, (q_ref, Dq_ref, kp, kd, tau_limit)))
+        names = tuple(k for k in RolloutFeedbackFunction.NAMES if need[k] and tensors[k] is not None)
+        want_ext = w is not None and bool(ctx.needs_input_grad[18])
+        fb = Feedback(q_ref, kp, kd, Dq_ref, hold=ctx.hold, tau_limit=tau_limit)
+        res = ctx.chain.rolloutAdjoint(q0, Dq0, tau, ctx.dt, q_traj, dq_traj, gq_end=c(gq_end), gDq_end=c(gdq_end), gq_traj=c(gq_traj),
+                                       gDq_traj=c(gdq_traj), integrator=ctx.integrator, n_steps=ctx.n_steps, layout=ctx.layout,
+                                       components=ctx.components, sum_tau=ctx.sum_tau, ext_wrenches=w, ext_link=ctx.ext_link if w is not None else None,
+                                       want_ext=want_ext, sum_ext=ctx.sum_ext if w is not None else False, feedback=fb, want_feedback=names,
+                                       gu_traj=c(gu))
+        gq0, gdq0, gtau = res[:3]
+
+        def padded(g, like):  # a sequence longer than the horizon: the unused records get 0
+            if g.dim() == like.dim() and g.shape[0] < like.shape[0]:
+                g = torch.cat([g, g.new_zeros((like.shape[0] - g.shape[0],) + tuple(g.shape[1:]))])
+            return g
+
+        gext = None
+        at = 4
+        if want_ext:
+            gext = res[at] if ctx.sum_ext else padded(res[at], w)
+            at += 1
+        grads = dict(zip(names, res[at:]))
+        for k in ("q_ref", "Dq_ref"):
+            if k in grads:
+                grads[k] = padded(grads[k], tensors[k])
+        for k in ("kp", "kd", "tau_limit"):
+            if k in grads and tensors[k].dim() == 1:  # shared by the samples: the sum of their rows
+                grads[k] = grads[k].sum(dim=0 if ctx.layout == "sample" else 1)
+        n3 = ctx.needs_input_grad[10:13]
+        return ((None,) * 10 + (gq0 if n3[0] else None, gdq0 if n3[1] else None, gtau if n3[2] else None)
+                + tuple(grads.get(k) for k in RolloutFeedbackFunction.NAMES) + (gext,))
+
+
 def _no_parameters_with_wrenches(parameters, component_parameters):
     if parameters is not None or component_parameters is not None:
         raise ValueError("ext_wrenches together with parameters / component_parameters is not served yet: the parameter gradients with "
@@ -244,7 +326,7 @@ def joint_acceleration(chain, q, Dq, tau, components=None, layout="sample", para
 
 
 def rollout(chain, q0, Dq0, tau, dt, integrator="rk4", n_steps=None, trajectory=False, components=None, layout="sample", parameters=None,
-            component_parameters=None, ext_wrenches=None, ext_link=None):
+            component_parameters=None, ext_wrenches=None, ext_link=None, feedback=None):
     """Differentiable ``Chain.rollout``: returns (q_end, Dq_end), and with trajectory=True also (q_traj, Dq_traj) with one record per
     step (record k = the state after step k + 1).  tau: (T, N, n) / (T, n, N), one torque per step, or shaped like q0 with an explicit
     n_steps (held over the horizon: its gradient is the sum over the steps).  Gradients flow to q0, Dq0 and tau from the end state and
@@ -253,11 +335,20 @@ def rollout(chain, q0, Dq0, tau, dt, integrator="rk4", n_steps=None, trajectory=
     parameters / component_parameters (the module docstring): the model to simulate, differentiable as well -- the backward is then one
     ``Chain.rolloutParameterAdjoint`` call (chains with at most 10 input joints).
     ext_wrenches, ext_link (the module docstring): external link wrenches as ``Chain.rollout`` takes them, differentiable: one step's
-    record is held over the horizon (its gradient is the sum over the steps), a leading T axis is one record per step."""
+    record is held over the horizon (its gradient is the sum over the steps), a leading T axis is one record per step.
+    feedback (the module docstring): a ``rosdyn_amd.Feedback``, the closed loop; tau is its feed-forward term and the law's tensors are
+    differentiable.  With ``feedback.command_trajectory`` the command trajectory is appended to the returned tuple."""
     if n_steps is None:
         if tau.dim() != 3:
             raise ValueError("torques shaped like q0 need an explicit n_steps")
         n_steps = tau.shape[0]
+    if feedback is not None:
+        if parameters is not None or component_parameters is not None:
+            raise ValueError("feedback together with parameters / component_parameters is not served yet: the parameter gradients of the "
+                             "closed loop are the follow-up")
+        return RolloutFeedbackFunction.apply(chain, components, layout, integrator, float(dt), int(n_steps), bool(trajectory), ext_link,
+                                             bool(feedback.hold), bool(feedback.command_trajectory), q0, Dq0, tau, feedback.q_ref,
+                                             feedback.Dq_ref, feedback.kp, feedback.kd, feedback.tau_limit, ext_wrenches)
     if ext_wrenches is not None:
         _no_parameters_with_wrenches(parameters, component_parameters)
         return RolloutExtFunction.apply(chain, components, layout, integrator, float(dt), int(n_steps), bool(trajectory), ext_link, q0, Dq0,

@@ -714,7 +714,8 @@ class Chain(object):
 
     def rolloutAdjoint(self, q0, Dq0, tau, dt, q_traj, Dq_traj, gq_end=None, gDq_end=None, gq_traj=None, gDq_traj=None, integrator="rk4",
                        n_steps=None, layout="sample", components=None, sum_tau=False, out=None, chunk_samples=0, workspace=None,
-                       ext_wrenches=None, ext_link=None, want_ext=False, sum_ext=False):
+                       ext_wrenches=None, ext_link=None, want_ext=False, sum_ext=False, feedback=None, want_feedback=(), gu_traj=None,
+                       accumulate=False, sum_ref=None):
         """Adjoint of rollout (include/rdyn.h: rdyn_rollout_adjoint; no reference counterpart): the exact transpose of the n_steps
         integrator steps rollout takes, from the seeds on the end state (gq_end, gDq_end, shaped like q0; None = 0) and, optionally, on
         every trajectory record (gq_traj, gDq_traj: (>= n_steps,) + q0.shape, record k seeds the state after step k + 1) back to the
@@ -728,14 +729,30 @@ class Chain(object):
         ext_wrenches, ext_link: the forward call's external link wrenches, with rollout's shape rules (rdyn_rollout_adjoint_ext): the
         transpose is that of rollout(ext_wrenches=).  want_ext=True appends gext to the returned tuple, the gradient with respect to the
         wrenches: (n_steps,) + one record's shape, one gradient per step, or one record with sum_ext=True (the sum over the steps: the
-        gradient of a wrench held over the horizon); out may hold "gext"."""
+        gradient of a wrench held over the horizon); out may hold "gext".
+        feedback: the forward call's rosdyn_amd.Feedback (rdyn_rollout_adjoint_feedback): the transpose is that of rollout(feedback=), the
+        PD law and its clamp included, and gtau is the gradient with respect to the feed-forward torques.  want_feedback: any selection
+        of "q_ref", "Dq_ref", "kp", "kd", "tau_limit"; their gradients are appended to the returned tuple in that order (behind gext):
+          q_ref, Dq_ref     (n_steps,) + q0.shape, one gradient per step, where the reference is per step; shaped like q0, the sum over
+                            the steps, where it is a constant set point.  sum_ref=True / False overrides the choice.
+          kp, kd, tau_limit shaped like q0: one row per SAMPLE summed over the steps, also for shared gains and the shared limits -- sum the
+                            rows over the samples for their gradient.
+        out may hold them as "gq_ref", "gDq_ref", "gkp", "gkd", "gtau_limit"; accumulate=True continues adding to the sums that out holds
+        (a horizon split into chained calls, the later part first).  gu_traj: None, or seeds on the command trajectory of
+        rollout(feedback=Feedback(command_trajectory=True), trajectory_every=1): (>= n_steps,) + q0.shape.  Chains for which
+        rollout(feedback=) takes its chunked route raise RdynError (RDYN_ERR_UNSUPPORTED)."""
+        closed = None
+        if feedback is not None:
+            closed = (feedback, tuple(want_feedback), gu_traj, bool(accumulate), sum_ref)
+        elif want_feedback or gu_traj is not None or accumulate or sum_ref is not None:
+            raise ValueError("want_feedback, gu_traj, accumulate and sum_ref need feedback")
         if ext_wrenches is None:
             if want_ext or sum_ext or ext_link is not None:
                 raise ValueError("want_ext, sum_ext and ext_link need ext_wrenches")
             return self._rollout_adjoint(q0, Dq0, tau, dt, q_traj, Dq_traj, gq_end, gDq_end, gq_traj, gDq_traj, integrator, n_steps, layout,
-                                         components, sum_tau, out, chunk_samples, workspace, None)
+                                         components, sum_tau, out, chunk_samples, workspace, None, None, closed)
         return self._rollout_adjoint(q0, Dq0, tau, dt, q_traj, Dq_traj, gq_end, gDq_end, gq_traj, gDq_traj, integrator, n_steps, layout, components,
-                                     sum_tau, out, chunk_samples, workspace, None, (ext_wrenches, ext_link, bool(want_ext), bool(sum_ext)))
+                                     sum_tau, out, chunk_samples, workspace, None, (ext_wrenches, ext_link, bool(want_ext), bool(sum_ext)), closed)
 
     def rolloutParameterAdjoint(self, q0, Dq0, tau, dt, q_traj, Dq_traj, gq_end=None, gDq_end=None, gq_traj=None, gDq_traj=None,
                                 integrator="rk4", n_steps=None, layout="sample", components=None, sum_tau=False, out=None, chunk_samples=0,
@@ -751,9 +768,9 @@ class Chain(object):
                                      sum_tau, out, chunk_samples, workspace, bool(accumulate))
 
     def _rollout_adjoint(self, q0, Dq0, tau, dt, q_traj, Dq_traj, gq_end, gDq_end, gq_traj, gDq_traj, integrator, n_steps, layout, components,
-                         sum_tau, out, chunk_samples, workspace, accumulate, wrenches=None):
+                         sum_tau, out, chunk_samples, workspace, accumulate, wrenches=None, closed=None):
         """the two calls above; accumulate None: without the parameter gradients; wrenches: None, or rolloutAdjoint's (ext_wrenches,
-        ext_link, want_ext, sum_ext)"""
+        ext_link, want_ext, sum_ext); closed: None, or rolloutAdjoint's (feedback, want_feedback, gu_traj, accumulate, sum_ref)"""
         torch = _torch()
         b, N, lay = self._batch(layout, q0, Dq0)
         if integrator not in _lib.INTEGRATORS:
@@ -804,20 +821,52 @@ class Chain(object):
         d.gtau, d.gtau_step_stride = ptr(gtau), 0 if sum_tau else q0.numel()
         d.status = status.data_ptr()
         comps, n_comps = self._component_list(components) if components is not None else (None, 0)
-        if wrenches is not None:
-            ext_wrenches, ext_link, want_ext, sum_ext = wrenches
-            ext = self._ext_wrenches(q0, N, lay, ext_wrenches, ext_link, steps=T)
-            g = _lib.ExtWrenchGradient()
-            gext = None
-            if want_ext:
-                rec = tuple(ext_wrenches.shape[1:]) if ext.step_stride else tuple(ext_wrenches.shape)
-                shape = rec if sum_ext else (max(T, 0),) + rec
-                gext = self._like_wrenches(shape, out.get("gext"), "gext") if out.get("gext") is not None else torch.empty(
-                    shape, dtype=torch.float64, device=q0.device)
-                g.gw, g.step_stride = ptr(gext), 0 if sum_ext else int(torch.Size(rec).numel())
-            check(lib().rdyn_rollout_adjoint_ext(self._h, C.byref(b), C.byref(d), comps, n_comps, C.byref(ext), C.byref(g), chunk_samples,
-                                                 None, 0))
-            return (gq0, gdq0, gtau, status) + ((gext,) if want_ext else ())
+        if wrenches is not None or closed is not None:
+            # rdyn_rollout_adjoint_feedback: without a law it is rdyn_rollout_adjoint_ext
+            ext, g, gext, want_ext = None, _lib.ExtWrenchGradient(), None, False
+            if wrenches is not None:
+                ext_wrenches, ext_link, want_ext, sum_ext = wrenches
+                ext = self._ext_wrenches(q0, N, lay, ext_wrenches, ext_link, steps=T)
+                if want_ext:
+                    rec = tuple(ext_wrenches.shape[1:]) if ext.step_stride else tuple(ext_wrenches.shape)
+                    shape = rec if sum_ext else (max(T, 0),) + rec
+                    gext = self._like_wrenches(shape, out.get("gext"), "gext") if out.get("gext") is not None else torch.empty(
+                        shape, dtype=torch.float64, device=q0.device)
+                    g.gw, g.step_stride = ptr(gext), 0 if sum_ext else int(torch.Size(rec).numel())
+            fb, gf, grads = None, None, []
+            if closed is not None:
+                feedback, want_fb, gu_traj, fb_acc, sum_ref = closed
+                fb = self._feedback(q0, feedback, T)
+                gf = _lib.FeedbackGradient()
+                gf.accumulate = 1 if fb_acc else 0
+                if gu_traj is not None:
+                    if not ok(gu_traj, max(T, 0)):
+                        raise ValueError("Input data dimensions mismatch")
+                    gf.gu_traj, gf.gu_step_stride = ptr(gu_traj), q0.numel()
+                if sum_ref is None:
+                    sum_ref = fb.ref_step_stride == 0
+                fields = {"q_ref": ("gq_ref", "gq_ref"), "Dq_ref": ("gDq_ref", "gdq_ref"), "kp": ("gkp", "gkp"), "kd": ("gkd", "gkd"),
+                          "tau_limit": ("gtau_limit", "glim")}
+                for name in want_fb:
+                    if name not in fields:
+                        raise ValueError("want_feedback: unknown name %r" % (name,))
+                    key, field = fields[name]
+                    summed = sum_ref or name in ("kp", "kd", "tau_limit")
+                    shape = tuple(q0.shape) if summed else (max(T, 0),) + tuple(q0.shape)
+                    t = out.get(key)
+                    if t is None:
+                        if fb_acc and summed:
+                            raise ValueError("accumulate=True needs out[%r]" % (key,))
+                        t = torch.empty(shape, dtype=torch.float64, device=q0.device)
+                    elif tuple(t.shape) != shape or t.dtype != torch.float64 or not t.is_contiguous() or t.device != q0.device:
+                        raise ValueError("out[%r] must be a contiguous float64 tensor of shape %s" % (key, shape))
+                    setattr(gf, field, ptr(t))
+                    grads.append(t)
+                gf.gref_step_stride = 0 if sum_ref else q0.numel()
+            ref = lambda x: C.byref(x) if x is not None else None
+            check(lib().rdyn_rollout_adjoint_feedback(self._h, C.byref(b), C.byref(d), comps, n_comps, ref(ext), C.byref(g), ref(fb), ref(gf),
+                                                      chunk_samples, None, 0))
+            return (gq0, gdq0, gtau, status) + ((gext,) if want_ext else ()) + tuple(grads)
         if accumulate is None:
             nbytes = lib().rdyn_rollout_adjoint_workspace_bytes(self._h, C.byref(d), N, chunk_samples)
         else:

@@ -3,7 +3,8 @@
 // rdyn_rollout_feedback,
 // rdyn_forward_dynamics_derivatives, rdyn_forward_dynamics_vjp, rdyn_rollout_adjoint, their parameter-gradient
 // forms rdyn_forward_dynamics_parameter_vjp and rdyn_rollout_adjoint_parameters, their forms with external link wrenches
-// rdyn_forward_dynamics_vjp_ext and rdyn_rollout_adjoint_ext, and the workspace queries.
+// rdyn_forward_dynamics_vjp_ext and rdyn_rollout_adjoint_ext, the adjoint of the closed loop rdyn_rollout_adjoint_feedback, and the
+// workspace queries.
 // Every entry runs check_batch and its own pointer / descriptor checks, then dyn_prepare (the checks and the set-up all of them share),
 // then either one launch (chains the unrolled kernels sweep) or the chunked route through its workspace.  The workspace of every chunked
 // route is described ONCE, by a *Layout struct: the query returns its total, the call carves its pointers from its offsets.
@@ -1114,10 +1115,12 @@ static AdjointParamLayout adjoint_param_layout(const rdyn_chain* c, const rdyn_c
 }
 
 // who = the entry point (error texts); pg null: rdyn_rollout_adjoint; ext with w (never with pg): rdyn_rollout_adjoint_ext with wrenches,
-// gext its gradient selection (may be null)
+// gext its gradient selection (may be null); fb (never with pg): rdyn_rollout_adjoint_feedback with the law, gfb its gradient selection
+// (may be null)
 static int rollout_adjoint(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_adjoint_desc* d, const rdyn_component* comps, int n_comps,
                            const rdyn_parameter_gradient* pg, bool with_pg, int64_t chunk_samples, void* workspace, size_t workspace_bytes,
-                           const char* who, const rdyn_ext_wrenches* ext = nullptr, const rdyn_ext_wrench_gradient* gext = nullptr)
+                           const char* who, const rdyn_ext_wrenches* ext = nullptr, const rdyn_ext_wrench_gradient* gext = nullptr,
+                           const rdyn_feedback* fb = nullptr, const rdyn_feedback_gradient* gfb = nullptr)
 {
   int st = check_batch(c, b, true, false, who, LONG_KERNELS);
   if (st != RDYN_OK) return st;
@@ -1150,8 +1153,52 @@ static int rollout_adjoint(const rdyn_chain* c, const rdyn_batch* b, const rdyn_
       return RDYN_ERR_INVALID_ARGUMENT;
     }
   }
-  if (N > 0 && !with_pg && !d->gq0 && !d->gdq0 && !d->gtau && !gw) return refuse(who, "every output is null");
+  RdynFeedbackGradArgs gf;
+  memset(&gf, 0, sizeof gf);
+  if (fb)
+  {
+    if (!fb->q_ref || !fb->kp) return refuse(who, "null reference (q_ref) or gain (kp) pointer");
+    if (fb->ref_step_stride < 0 || (fb->ref_step_stride != 0 && fb->ref_step_stride < nN))
+    {
+      rdyn_set_error("%s: ref_step_stride %lld is negative, or not zero and smaller than one step's record (%lld doubles)", who,
+                     (long long)fb->ref_step_stride, (long long)nN);
+      return RDYN_ERR_INVALID_ARGUMENT;
+    }
+    if ((fb->hold != 0 && fb->hold != 1) || (fb->gains_per_sample != 0 && fb->gains_per_sample != 1))
+      return refuse(who, "hold and gains_per_sample are 0 or 1");
+    if (gfb)
+    {
+      if ((gfb->gkd || gfb->gdq_ref) && !fb->kd) return refuse(who, "gkd or gdq_ref without a velocity gain (fb->kd)");
+      if (gfb->glim && !fb->tau_limit) return refuse(who, "glim without limits (fb->tau_limit)");
+      if ((gfb->gq_ref || gfb->gdq_ref) && (gfb->gref_step_stride < 0 || (gfb->gref_step_stride != 0 && gfb->gref_step_stride < nN)))
+      {
+        rdyn_set_error("%s: gref_step_stride %lld is negative, or not zero and smaller than one step's record (%lld doubles)", who,
+                       (long long)gfb->gref_step_stride, (long long)nN);
+        return RDYN_ERR_INVALID_ARGUMENT;
+      }
+      if (gfb->gu_traj && gfb->gu_step_stride < nN) return refuse(who, "gu_traj needs gu_step_stride >= n * n_samples");
+      if (gfb->accumulate != 0 && gfb->accumulate != 1) return refuse(who, "accumulate is 0 or 1");
+      gf.gq_ref = gfb->gq_ref;
+      gf.gdq_ref = gfb->gdq_ref;
+      gf.gref_step = (gfb->gq_ref || gfb->gdq_ref) ? gfb->gref_step_stride : 0;
+      gf.gkp = gfb->gkp;
+      gf.gkd = gfb->gkd;
+      gf.glim = gfb->glim;
+      gf.gu = gfb->gu_traj;
+      gf.gu_step = gfb->gu_traj ? gfb->gu_step_stride : 0;
+      gf.accumulate = gfb->accumulate;
+    }
+  }
+  const bool law_out = gf.gq_ref || gf.gdq_ref || gf.gkp || gf.gkd || gf.glim;
+  if (N > 0 && !with_pg && !d->gq0 && !d->gdq0 && !d->gtau && !gw && !law_out) return refuse(who, "every output is null");
   if (x.w && (st = ext_reverse_refusal(c, who)) != RDYN_OK) return st;
+  if (fb && fwd_dyn_by_chunks(c))
+  {
+    rdyn_set_error("%s: chains that rdyn_rollout_feedback serves by its chunked route (more than %d input joints; this chain has %d) are not "
+                   "served yet: the adjoint of the chunked closed loop is the follow-up",
+                   who, RDYN_MAX_SWEPT_JOINTS, n);
+    return RDYN_ERR_UNSUPPORTED;
+  }
   if (with_pg && fwd_dyn_by_chunks(c))
   {
     rdyn_set_error("%s: chains with more than %d input joints are not served yet (this chain has %d); rdyn_rollout_adjoint serves them", who,
@@ -1161,7 +1208,7 @@ static int rollout_adjoint(const rdyn_chain* c, const rdyn_batch* b, const rdyn_
   const AdjointLayout L = adjoint_layout(c, d, N, chunk_samples);
   const AdjointParamLayout PL = adjoint_param_layout(c, comps, n_comps, with_pg ? N : 0);
   DynCall k;
-  st = dyn_prepare(c, b, comps, n_comps, chunk_samples, with_pg ? PL.total : (x.w ? 0 : L.s.total), workspace, workspace_bytes, who, &k);
+  st = dyn_prepare(c, b, comps, n_comps, chunk_samples, with_pg ? PL.total : ((x.w || fb) ? 0 : L.s.total), workspace, workspace_bytes, who, &k);
   if (st != RDYN_OK || !k.run) return st;
   if (k.sw)
   {
@@ -1196,6 +1243,29 @@ static int rollout_adjoint(const rdyn_chain* c, const rdyn_batch* b, const rdyn_
     if ((d->gq0 || d->gdq0) && stage_records(b, d->gq0, d->gdq0)) a.staged |= 1;
     if (d->gtau && stage_records(b, d->gtau) && (d->gtau_step_stride * (int64_t)sizeof(double)) % 128 == 0) a.staged |= 2;
     a.t = k.table;
+    if (fb)
+    {
+      RdynRolloutAdjointFbArgs af;
+      memset(&af, 0, sizeof af);
+      af.ax.a = a;
+      af.ax.x = x;
+      af.ax.gw = gw;
+      af.ax.gw_step = gw ? gext->step_stride : 0;
+      af.f.q_ref = fb->q_ref;
+      af.f.dq_ref = fb->dq_ref;
+      af.f.ref_step = fb->ref_step_stride;
+      af.f.kp = fb->kp;
+      af.f.kd = fb->kd;
+      af.f.lim = fb->tau_limit;
+      af.f.per_sample = fb->gains_per_sample;
+      af.f.hold = fb->hold;
+      af.g = gf;
+      if ((gf.gq_ref || gf.gdq_ref) && gf.gref_step != 0 && stage_records(b, gf.gq_ref, gf.gdq_ref) &&
+          (gf.gref_step * (int64_t)sizeof(double)) % 128 == 0)
+        af.g.staged = 1;
+      RDYN_HIP_TRY(rdyn_launch_rollout_adjoint_feedback(k.sw->n_joints(), af, k.stream));
+      return RDYN_OK;
+    }
     if (x.w)
     {
       RdynRolloutAdjointExtArgs ax;
@@ -1381,4 +1451,25 @@ int rdyn_rollout_adjoint_ext(const rdyn_chain* c, const rdyn_batch* b, const rdy
     return rollout_adjoint(c, b, d, comps, n_comps, nullptr, false, chunk_samples, workspace, workspace_bytes, "rdyn_rollout_adjoint");
   }
   return rollout_adjoint(c, b, d, comps, n_comps, nullptr, false, chunk_samples, workspace, workspace_bytes, who, ext, gext);
+}
+
+size_t rdyn_rollout_adjoint_feedback_workspace_bytes(const rdyn_chain* c, const rdyn_rollout_adjoint_desc* d, const rdyn_ext_wrenches* ext,
+                                                     const rdyn_feedback* fb, int64_t n_samples, int64_t chunk_samples)
+{
+  return fb ? 0 : rdyn_rollout_adjoint_ext_workspace_bytes(c, d, ext, n_samples, chunk_samples);
+}
+
+int rdyn_rollout_adjoint_feedback(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_adjoint_desc* d, const rdyn_component* comps,
+                                  int n_comps, const rdyn_ext_wrenches* ext, const rdyn_ext_wrench_gradient* gext, const rdyn_feedback* fb,
+                                  const rdyn_feedback_gradient* gfb, int64_t chunk_samples, void* workspace, size_t workspace_bytes)
+{
+  const char* const who = "rdyn_rollout_adjoint_feedback";
+  if (!fb)
+  {
+    if (gfb && (gfb->gq_ref || gfb->gdq_ref || gfb->gkp || gfb->gkd || gfb->glim || gfb->gu_traj))
+      return refuse(who, "a feedback gradient without a feedback law");
+    return rdyn_rollout_adjoint_ext(c, b, d, comps, n_comps, ext, gext, chunk_samples, workspace, workspace_bytes);
+  }
+  if ((!ext || !ext->w) && gext && gext->gw) return refuse(who, "a wrench gradient without external wrenches");
+  return rollout_adjoint(c, b, d, comps, n_comps, nullptr, false, chunk_samples, workspace, workspace_bytes, who, ext, gext, fb, gfb);
 }

@@ -801,6 +801,27 @@ struct RdynRolloutAdjointExtArgs
 hipError_t rdyn_launch_rollout_adjoint_ext_euler(int n_joints, const RdynRolloutAdjointExtArgs& a, hipStream_t st);
 hipError_t rdyn_launch_rollout_adjoint_ext_rk4(int n_joints, const RdynRolloutAdjointExtArgs& a, hipStream_t st);
 
+// the adjoint of a closed-loop rollout (rdyn_rollout_adjoint_fb.hip): of the rollout RdynRolloutFbArgs describes.  ax = the adjoint's
+// arguments (ax.x.w null: no wrenches, ax.gw null then; ax.a.gtau is the gradient with respect to the feed-forward torques), f = the
+// forward call's law (tau_traj is not read), g = where the law's gradients go.  Every array of g is addressed like q.
+struct RdynFeedbackGradArgs
+{
+  double *gq_ref, *gdq_ref;   // may be null: step t at + t * gref_step
+  int64_t gref_step;          // 0: one record, the sum over the steps
+  double *gkp, *gkd, *glim;   // may be null: one row per SAMPLE, summed over the steps
+  const double* gu;           // may be null: record t = the seed on the command of step t's first evaluation, at + t * gu_step
+  int64_t gu_step;
+  int accumulate;             // 1: gkp, gkd, glim and the gref_step = 0 sums continue from what is there
+  int staged;                 // the per-step records of gq_ref / gdq_ref leave through the wave's LDS tile in whole lines
+};
+struct RdynRolloutAdjointFbArgs
+{
+  RdynRolloutAdjointExtArgs ax;
+  RdynFeedbackArgs f;
+  RdynFeedbackGradArgs g;
+};
+hipError_t rdyn_launch_rollout_adjoint_feedback(int n_joints, const RdynRolloutAdjointFbArgs& a, hipStream_t st);
+
 // pieces of rdyn_identification_tsqr for the multi-device form (rdyn_api_tsqr.cpp): widths of the swept / the chain's factor, the factor of
 // the swept chain alone, the expansion (+ accumulation) of a swept factor
 int rdyn_internal_tsqr_widths(const rdyn_chain* c, const rdyn_component* comps, int n_comps, int* n1s, int* n1, int* expands);

@@ -9,6 +9,15 @@
 // (fwd_dyn_vjp_ext_eval) at that stage's own q.  With gw every product ADDS its -(d tau_E / d ext)' w to the lane's own record of the
 // step in memory (6 (NJ + 1) doubles per lane do not belong in registers), zeroed when the step begins -- or once, here, when the
 // record is the sum over the steps (gw_step = 0): read-modify-write by the one lane that owns it, in the order of the products.
+// RDYN_ADJ_FB 1 (k_rollout_adjoint_fb; RDYN_ADJ_PARAMS 0, RDYN_ADJ_EXT either; also expects fb, RdynFeedbackArgs, and gf,
+// RdynFeedbackGradArgs): the rollout is rdyn_rollout_feedback's.  The command hook (fb_command, the forward kernel's text) runs before
+// each rebuilt stage evaluation and before each product -- at the head of the step over tau[] where the command is held (hold = 1, and
+// semi-implicit Euler, written once for both modes), into the evaluation's copy otherwise -- and the law's transpose (fb_transpose)
+// after each product (hold = 0 with RK4) or after the step's products (rdyn_rollout_adjoint_fb.hip has the scheme).
+#ifndef RDYN_ADJ_FB
+#define RDYN_ADJ_FB 0
+#define RDYN_ADJ_FB_DEFAULTED
+#endif
   const ChainPtr c = as_const(a.chain);
   const int lane = threadIdx.x;
   const int64_t s_wave = (int64_t)blockIdx.x * 64;
@@ -16,11 +25,18 @@
   if (s >= a.n_samples) return;
   const bool full = a.n_samples - s_wave >= 64;  // wave-uniform
   const bool stg_x = (a.staged & 1) && full, stg_tau = (a.staged & 2) && full;
+#if RDYN_ADJ_FB
+  const bool stg_ref = gf.staged && full;
+#endif
   const double dt = a.dt;
   const int T = a.n_steps;
   const int64_t so = s * a.in_ss;
   SmallRecords sm;
+#if RDYN_ADJ_FB
+  if (stg_x || stg_tau || stg_ref)
+#else
   if (stg_x || stg_tau)
+#endif
   {
     extern __shared__ __attribute__((aligned(16))) char adjoint_stage_lds[];
     sm.init(adjoint_stage_lds, c->n_active, lane);
@@ -91,6 +107,10 @@
     }
   }
   bool alive = true;
+#if RDYN_ADJ_FB
+  if (!gf.accumulate) fb_rows_fill<NJ>(c, gf, so, a.in_sj, 0.0);
+  const bool held = INTEGRATOR == RDYN_INTEGRATOR_SEMI_IMPLICIT_EULER || fb.hold;  // wave-uniform: one command serves the step
+#endif
 
 #pragma unroll 1
   for (int t = T - 1; t >= 0; --t)
@@ -113,6 +133,9 @@
     }
 #endif
     bool ok = true;
+#if RDYN_ADJ_FB
+    if (held) fb_command<NJ>(c, fb, so, a.in_sj, t, q, dq, tau);  // tau = the command from here on; the transpose loads tau_ff again
+#endif
     if (INTEGRATOR == RDYN_INTEGRATOR_SEMI_IMPLICIT_EULER)
     {
       double qb[NJ], vb[NJ];
@@ -132,6 +155,13 @@
 #else
       ok = fwd_dyn_vjp_eval<NJ>(per_evaluation(c), a.t, [&](int f, int) { return q[f]; }, [&](int f, int) { return dq[f]; }, tau, gt, qb, vb, true,
                                 true, [](bool, double (&)[NJ]) {});
+#endif
+#if RDYN_ADJ_FB
+      {
+        double ff[NJ];
+        load_record<NJ>(c, a.tau + (int64_t)t * a.tau_step + so, a.in_sj, ff);
+        ok = fb_transpose<NJ>(c, fb, gf, so, a.in_sj, t, true, ff, q, dq, gt, qb, vb) && ok;
+      }
 #endif
 #pragma unroll
       for (int f = 0; f < NJ; ++f)
@@ -157,6 +187,17 @@
         for (int stage = 0; stage < 3; ++stage)
         {
           double rhs[NJ];
+#if RDYN_ADJ_FB
+#pragma unroll
+          for (int f = 0; f < NJ; ++f) rhs[f] = tau[f];
+          if (!held) fb_command<NJ>(c, fb, so, a.in_sj, t, sq, kq, rhs);  // the continuous law at the stage state, the components behind the clamp
+#pragma unroll
+          for (int f = 0; f < NJ; ++f)
+          {
+            const int idx = c->j[f].in_idx;
+            if (idx >= 0) rhs[f] -= joint_component_torque(a.t, idx, sq[f], kq[f]);
+          }
+#else
 #pragma unroll
           for (int f = 0; f < NJ; ++f)
           {
@@ -164,6 +205,7 @@
             rhs[f] = tau[f];
             if (idx >= 0) rhs[f] -= joint_component_torque(a.t, idx, sq[f], kq[f]);
           }
+#endif
 #if RDYN_ADJ_EXT
           fwd_dyn_eval_ext<NJ>(per_evaluation(c), sq, kq, rhs, xe);
 #else
@@ -208,6 +250,9 @@
           cq[f] = fma(dtb, lq[f], cq[f]);  // kq_i
           mu[f] = fma(dtb, lv[f], cv[f]);  // kv_i
         }
+#if RDYN_ADJ_FB
+        if (!held) fb_command<NJ>(c, fb, so, a.in_sj, t, sq, sv, rhs);
+#endif
 #if RDYN_ADJ_PARAMS
         ok = fwd_dyn_vjp_params_eval<NJ>(per_evaluation(c), a.t, [&](int f, int) { return sq[f]; }, [&](int f, int) { return sv[f]; }, rhs, mu,
                                          qb, vb, true, true, [](bool, double (&)[NJ]) {}, link) &&
@@ -221,6 +266,9 @@
         ok = fwd_dyn_vjp_eval<NJ>(per_evaluation(c), a.t, [&](int f, int) { return sq[f]; }, [&](int f, int) { return sv[f]; }, rhs, mu, qb, vb,
                                 true, true, [](bool, double (&)[NJ]) {}) &&
              ok;
+#endif
+#if RDYN_ADJ_FB
+        if (!held) ok = fb_transpose<NJ>(c, fb, gf, so, a.in_sj, t, i == 0, tau, sq, sv, mu, qb, vb) && ok;  // (tau is tau_ff here)
 #endif
 #pragma unroll
         for (int f = 0; f < NJ; ++f)
@@ -239,6 +287,14 @@
         lq[f] = xq[f];
         lv[f] = xv[f];
       }
+#if RDYN_ADJ_FB
+      if (held)  // the held command: one transpose at x_t, of the sum of the four stage products, applied to lambda_t
+      {
+        double ff[NJ];
+        load_record<NJ>(c, a.tau + (int64_t)t * a.tau_step + so, a.in_sj, ff);
+        ok = fb_transpose<NJ>(c, fb, gf, so, a.in_sj, t, true, ff, q, dq, gt, lq, lv) && ok;
+      }
+#endif
     }
     alive = alive && ok;
 #pragma unroll
@@ -261,6 +317,9 @@
       const int64_t go = (int64_t)t * a.gtau_step;
       put_record<NJ>(c, sm, stg_tau, gt, a.gtau + go + s_wave * a.in_ss, a.gtau + go + so, a.in_sj, lane);
     }
+#if RDYN_ADJ_FB
+    fb_reference_gradients<NJ>(c, fb, gf, sm, stg_ref, so, s_wave * a.in_ss, a.in_sj, t, gt, lane);
+#endif
     if (t >= 1)
     {
       double g[NJ];
@@ -290,6 +349,13 @@
 #if RDYN_ADJ_PARAMS
   p.status[s] = alive ? 1 : -1;
 #endif
+#if RDYN_ADJ_FB
+  if (!alive) fb_rows_fill<NJ>(c, gf, so, a.in_sj, qnan);
+#endif
   if (a.gtau && !a.gtau_step) put_record<NJ>(c, sm, stg_tau, gsum, a.gtau + s_wave * a.in_ss, a.gtau + so, a.in_sj, lane);
   if (a.gq0) put_record<NJ>(c, sm, stg_x, lq, a.gq0 + s_wave * a.in_ss, a.gq0 + so, a.in_sj, lane);
   if (a.gdq0) put_record<NJ>(c, sm, stg_x, lv, a.gdq0 + s_wave * a.in_ss, a.gdq0 + so, a.in_sj, lane);
+#ifdef RDYN_ADJ_FB_DEFAULTED
+#undef RDYN_ADJ_FB_DEFAULTED
+#undef RDYN_ADJ_FB
+#endif

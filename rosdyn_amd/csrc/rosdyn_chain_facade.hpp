@@ -1009,6 +1009,22 @@ public:
     chk(rdyn_rollout_adjoint_ext(m_h, &b, &desc, comps.empty() ? nullptr : comps.data(), (int)comps.size(), &ext, &gext, chunk_samples, workspace,
                                  workspace_bytes));
   }
+  // ... of a closed-loop rollout: the transpose of rolloutBatch(comps, ext, fb, ...), the PD law and its clamp included
+  // (rdyn_rollout_adjoint_feedback; fb = the forward call's law, gfb = where the gradients with respect to references, gains and limits
+  // go -- gkp, gkd, glim are rows per SAMPLE; desc.gtau is the gradient with respect to the feed-forward torques).  The wrenches and their
+  // gradient go by pointer: nullptr = none; comps may be empty.
+  size_t rolloutAdjointWorkspaceBytes(const rdyn_rollout_adjoint_desc& desc, const rdyn_ext_wrenches* ext, const rdyn_feedback& fb,
+                                      int64_t n_samples, int64_t chunk_samples = 0) const
+  {
+    return rdyn_rollout_adjoint_feedback_workspace_bytes(m_h, &desc, ext, &fb, n_samples, chunk_samples);
+  }
+  void rolloutAdjointBatch(const std::vector<rdyn_component>& comps, const rdyn_ext_wrenches* ext, const rdyn_ext_wrench_gradient* gext,
+                           const rdyn_feedback& fb, const rdyn_feedback_gradient& gfb, const rdyn_batch& b,
+                           const rdyn_rollout_adjoint_desc& desc, int64_t chunk_samples, void* workspace, size_t workspace_bytes) const
+  {
+    chk(rdyn_rollout_adjoint_feedback(m_h, &b, &desc, comps.empty() ? nullptr : comps.data(), (int)comps.size(), ext, gext, &fb, &gfb,
+                                      chunk_samples, workspace, workspace_bytes));
+  }
   // ---- gradients with respect to the model's parameters (no reference counterpart)
   // the chain with the inertial parameters pi (10 per chain joint, the order of getNominalParameters; stored as given): an independent
   // chain equal to clone() in everything else: rdyn_chain_with_parameters
