@@ -858,8 +858,8 @@ int rdyn_rollout_adjoint_ext(const rdyn_chain* chain, const rdyn_batch* batch, c
  *                longer chains with at most that many input joints on their reduced companion when there are no wrenches.  ONE launch
  *                for the horizon; the workspace query returns 0.
  *   fb given and rdyn_rollout_feedback takes the chunked route for the chain: RDYN_ERR_UNSUPPORTED.
- *                The adjoint of the chunked closed loop is the follow-up, and so are the parameter gradients of the closed loop
- *                (rdyn_rollout_adjoint_parameters with feedback).
+ *                The adjoint of the chunked closed loop is the follow-up.  The parameter gradients of the closed loop come from
+ *                rdyn_rollout_adjoint_feedback_parameters (below).
  * Status: the rule of rdyn_rollout_adjoint_ext, extended to the references, gains and limits the sample reads: a non-finite entry gives
  * -1.  From the failing backward step on every output of the sample is quiet NaN -- its reference gradients of that step and the earlier
  * ones, and its whole gkp / gkd / glim rows and summed reference gradients.  No sample affects another.
@@ -888,6 +888,46 @@ int rdyn_rollout_adjoint_feedback(const rdyn_chain* chain, const rdyn_batch* bat
                                   const rdyn_component* comps, int n_comps, const rdyn_ext_wrenches* ext,
                                   const rdyn_ext_wrench_gradient* gext, const rdyn_feedback* fb, const rdyn_feedback_gradient* gfb,
                                   int64_t chunk_samples, void* workspace, size_t workspace_bytes);
+
+/* Adjoint of a closed-loop rollout WITH the gradients with respect to the model's parameters (no reference counterpart): what
+ * loss.backward() through the simulated closed loop needs for output-error identification of a robot that is only ever excited under
+ * its controller.  It is rdyn_rollout_adjoint_feedback and rdyn_rollout_adjoint_parameters in one sweep.
+ * Outputs shared with rdyn_rollout_adjoint_feedback: for the same descriptor, law and selection this call writes the same bits in gq0,
+ * gdq0, gtau, the status and the law's gradients gq_ref, gdq_ref, gkp, gkd and glim, gu_traj seeds and gfb->accumulate included.  gfb may
+ * be NULL or empty, and gq0, gdq0, gtau may all be NULL: gpi or gcomp is an output.
+ * gpi and gcomp are defined as at rdyn_rollout_adjoint_parameters: the sum, over the samples whose FINAL status is 1, of the
+ * one-evaluation products pi_bar = -Y' w and comp_bar = -C' w with w = M^-1 seed, taken at the very seeds the closed-loop adjoint uses:
+ * semi-implicit Euler one product per step at (x_t, u_t; mu); RK4 four per step at (X_i, u; kv_i), i = 4 .. 1.  u is the command the
+ * forward call applied there: under hold = 1, and for semi-implicit Euler, the held command of the step; under hold = 0 with RK4 the
+ * command formed at the stage state.  w is the product's tau_bar BEFORE the law's transpose masks it.  The law does not depend on the
+ * model, so there is no further term.
+ * Reproducibility and accumulation: gpi and gcomp are reproducible bit for bit from run to run (every lane adds into its own
+ * accumulators, element-major in the workspace, [10 n_swept + K][n_samples]; one fixed-order reduction follows; no floating-point
+ * atomics).  A sample with status -1 contributes NOTHING to gpi / gcomp, not even from the backward steps before it failed, and is NaN in
+ * its own rows of the other outputs only.  pg->accumulate and gfb->accumulate are independent flags.  A horizon split into two chained
+ * calls, the earlier part with both flags 1, gives the single call's bits in the state and law gradients and its gpi / gcomp to rounding.
+ * T = 0: what rdyn_rollout_adjoint_feedback does, and zeros in gpi / gcomp (pg->accumulate = 1: leaves them as they are).
+ * Routing, decided before any device work:
+ *   fb == NULL and no wrenches   IS rdyn_rollout_adjoint_parameters: the same kernels, the same bits, the same workspace query.  A gfb
+ *                with any output or gu_traj in it is then RDYN_ERR_INVALID_ARGUMENT.
+ *   ext with w != NULL           RDYN_ERR_UNSUPPORTED: the parameter gradients with external wrenches are the next step; ext and gext are
+ *                in the signature so that it need not change then.  The query returns 0.
+ *   fb given and rdyn_rollout_feedback takes the chunked route for the chain: RDYN_ERR_UNSUPPORTED, as at rdyn_rollout_adjoint_feedback.
+ *   otherwise    at most RDYN_MAX_SWEPT_JOINTS chain joints, and longer chains with at most that many input joints on their reduced
+ *                companion, the sums expanded by X_f' on the device: ONE launch for the horizon plus the reduction of
+ *                rdyn_rollout_adjoint_parameters; the workspace is that call's.
+ * Errors, all RDYN_ERR_INVALID_ARGUMENT before any device work: those of rdyn_rollout_adjoint_feedback and those of
+ * rdyn_rollout_adjoint_parameters; "every output NULL" cannot occur, since a NULL pg, or one with gpi and gcomp both NULL, is invalid as
+ * in the open-loop call.  n_samples = 0 is RDYN_OK.  No allocation and no synchronisation: capturable into a graph once the chain has
+ * been used on the device. */
+size_t rdyn_rollout_adjoint_feedback_parameters_workspace_bytes(const rdyn_chain* chain, const rdyn_rollout_adjoint_desc* desc,
+                                                                const rdyn_component* comps, int n_comps, const rdyn_ext_wrenches* ext,
+                                                                const rdyn_feedback* fb, int64_t n_samples, int64_t chunk_samples);
+int rdyn_rollout_adjoint_feedback_parameters(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_rollout_adjoint_desc* desc,
+                                             const rdyn_component* comps, int n_comps, const rdyn_ext_wrenches* ext,
+                                             const rdyn_ext_wrench_gradient* gext, const rdyn_feedback* fb,
+                                             const rdyn_feedback_gradient* gfb, const rdyn_parameter_gradient* pg, int64_t chunk_samples,
+                                             void* workspace, size_t workspace_bytes);
 
 /* ---- mixed-chain batch (BASELINE.json configs[4]: 256 distinct 6-7-DOF chains x 4 096 samples) --------------
  * One launch per group of chains with equal joint count (and output-layout kind) evaluates rdyn_regressor for MANY

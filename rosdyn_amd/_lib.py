@@ -168,6 +168,12 @@ SYMBOLS = {
     "rdyn_rollout_adjoint_feedback": (_I, [_VP, _BP, C.POINTER(RolloutAdjointDesc), _VP, _I, C.POINTER(ExtWrenches),
                                            C.POINTER(ExtWrenchGradient), C.POINTER(Feedback), C.POINTER(FeedbackGradient), C.c_int64, _VP,
                                            C.c_size_t]),
+    "rdyn_rollout_adjoint_feedback_parameters_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(RolloutAdjointDesc), _VP, _I,
+                                                                              C.POINTER(ExtWrenches), C.POINTER(Feedback), C.c_int64,
+                                                                              C.c_int64]),
+    "rdyn_rollout_adjoint_feedback_parameters": (_I, [_VP, _BP, C.POINTER(RolloutAdjointDesc), _VP, _I, C.POINTER(ExtWrenches),
+                                                      C.POINTER(ExtWrenchGradient), C.POINTER(Feedback), C.POINTER(FeedbackGradient),
+                                                      C.POINTER(ParameterGradient), C.c_int64, _VP, C.c_size_t]),
     "rdyn_local_ik": (_I, [_VP, _BP, _VP, _DP, C.c_double, _I, _VP, _VP, _VP]),
     "rdyn_local_ik_damped": (_I, [_VP, _BP, _VP, _DP, C.c_double, C.c_double, _I, _VP, _VP, _VP]),
     "rdyn_frame_distance": (_I, [C.c_int64, _VP, _VP, _I, _I, _VP, _VP, _I, _VP]),

@@ -38,11 +38,19 @@ law and its clamp included.  Gradients flow to q0, Dq0, tau (now the feed-forwar
 the horizon the sum over the steps.  With ``ext_wrenches`` the wrench gradient flows as above.  With ``feedback.command_trajectory`` the
 command trajectory (one record per step: the command of the step's first evaluation) is returned last and is differentiable: a cost
 on the control effort.  A clamped command has no slope: its gradient goes to ``tau_limit``.  ``parameters`` / ``component_parameters``
-together with ``feedback`` raise ValueError: the parameter gradients of the closed loop are the follow-up (include/rdyn.h).
+together with ``feedback`` raise ValueError in ``rollout``: the parameter gradients of the closed loop were its follow-up and are served by
+
+    q_T, Dq_T, ... = closed_loop_rollout(chain, q0, Dq0, tau, dt, feedback, parameters=pi, component_parameters=cp)
+
+(closed-loop output-error identification).  Without parameters it returns what ``rollout(feedback=)`` returns; with them it runs through
+``RolloutFeedbackParametersFunction``: the model is built as above (``withParameters``, the host round trip), gradients flow to q0, Dq0,
+tau, the law's tensors, ``parameters`` and ``component_parameters``, and the backward is ONE ``Chain.rolloutParameterAdjoint(feedback=)``
+call (include/rdyn.h: rdyn_rollout_adjoint_feedback_parameters).  The law does not depend on the model: the parameter gradients are the
+open loop's products, taken at the commands the closed loop applied.  External link wrenches are not among its arguments yet.
 """
 import torch
 
-__all__ = ["joint_acceleration", "rollout", "JointAccelerationFunction", "RolloutFunction", "JointAccelerationParametersFunction",
+__all__ = ["joint_acceleration", "rollout", "closed_loop_rollout", "RolloutFeedbackParametersFunction", "JointAccelerationFunction", "RolloutFunction", "JointAccelerationParametersFunction",
            "RolloutParametersFunction", "JointAccelerationExtFunction", "RolloutExtFunction", "RolloutFeedbackFunction"]
 
 
@@ -305,6 +313,66 @@ class RolloutFeedbackFunction(torch.autograd.Function):
                 + tuple(grads.get(k) for k in RolloutFeedbackFunction.NAMES) + (gext,))
 
 
+class RolloutFeedbackParametersFunction(torch.autograd.Function):
+    """RolloutFeedbackFunction (without wrenches) with the model among the inputs; the backward is ONE
+    Chain.rolloutParameterAdjoint(feedback=) call.  Dq_ref, kd, tau_limit, parameters and component_parameters may be None."""
+
+    @staticmethod
+    def forward(ctx, chain, components, layout, integrator, dt, n_steps, trajectory, hold, command, q0, Dq0, tau, q_ref, Dq_ref, kp, kd,
+                tau_limit, parameters, component_parameters):
+        from .feedback import Feedback
+        det = lambda t: t.detach().contiguous() if t is not None else None
+        q0, Dq0, tau, q_ref, Dq_ref, kp, kd, tau_limit = (det(t) for t in (q0, Dq0, tau, q_ref, Dq_ref, kp, kd, tau_limit))
+        chain, components = _with_parameters(chain, components, parameters, component_parameters)
+        fb = Feedback(q_ref, kp, kd, Dq_ref, hold=hold, tau_limit=tau_limit, command_trajectory=command)
+        res = chain.rollout(q0, Dq0, tau, dt, integrator=integrator, n_steps=n_steps, layout=layout, trajectory_every=1, components=components,
+                            feedback=fb)
+        q_end, dq_end, q_traj, dq_traj = res[0], res[1], res[3], res[4]
+        ctx.chain, ctx.components, ctx.layout, ctx.integrator, ctx.dt = chain, components, layout, integrator, dt
+        ctx.n_steps, ctx.trajectory, ctx.sum_tau, ctx.hold, ctx.command = q_traj.shape[0], trajectory, tau.dim() == 2, hold, command
+        ctx.present = tuple(t is not None for t in (Dq_ref, kd, tau_limit))
+        ctx.devices = tuple(t.device if t is not None else None for t in (parameters, component_parameters))
+        z = q0.new_empty((0,))
+        ctx.save_for_backward(q0, Dq0, tau, q_traj, dq_traj, q_ref, kp, *(t if t is not None else z for t in (Dq_ref, kd, tau_limit)))
+        out = (q_end, dq_end)
+        if trajectory:
+            out += (q_traj.clone(), dq_traj.clone())  # (the saved records must not be written to by the caller)
+        if command:
+            out += (res[5],)
+        return out
+
+    @staticmethod
+    def backward(ctx, gq_end, gdq_end, *rest):
+        from .feedback import Feedback
+        q0, Dq0, tau, q_traj, dq_traj, q_ref, kp = ctx.saved_tensors[:7]
+        Dq_ref, kd, tau_limit = (t if have else None for t, have in zip(ctx.saved_tensors[7:], ctx.present))
+        c = lambda t: t.contiguous() if t is not None else None
+        rest = list(rest)
+        gq_traj, gdq_traj = (rest.pop(0), rest.pop(0)) if ctx.trajectory else (None, None)
+        gu = rest.pop(0) if ctx.command else None
+        NAMES = RolloutFeedbackFunction.NAMES
+        need = dict(zip(NAMES, ctx.needs_input_grad[12:17]))
+        tensors = dict(zip(NAMES, (q_ref, Dq_ref, kp, kd, tau_limit)))
+        names = tuple(k for k in NAMES if need[k] and tensors[k] is not None)
+        fb = Feedback(q_ref, kp, kd, Dq_ref, hold=ctx.hold, tau_limit=tau_limit)
+        res = ctx.chain.rolloutParameterAdjoint(q0, Dq0, tau, ctx.dt, q_traj, dq_traj, gq_end=c(gq_end), gDq_end=c(gdq_end), gq_traj=c(gq_traj),
+                                                gDq_traj=c(gdq_traj), integrator=ctx.integrator, n_steps=ctx.n_steps, layout=ctx.layout,
+                                                components=ctx.components, sum_tau=ctx.sum_tau, feedback=fb, want_feedback=names,
+                                                gu_traj=c(gu))
+        gq0, gdq0, gtau, gpi, gcomp = res[:5]
+        grads = dict(zip(names, res[6:]))
+        for k in ("q_ref", "Dq_ref"):  # a sequence longer than the horizon: the unused records get 0
+            if k in grads and grads[k].dim() == tensors[k].dim() and grads[k].shape[0] < tensors[k].shape[0]:
+                g = grads[k]
+                grads[k] = torch.cat([g, g.new_zeros((tensors[k].shape[0] - g.shape[0],) + tuple(g.shape[1:]))])
+        for k in ("kp", "kd", "tau_limit"):
+            if k in grads and tensors[k].dim() == 1:  # shared by the samples: the sum of their rows
+                grads[k] = grads[k].sum(dim=0 if ctx.layout == "sample" else 1)
+        n3 = ctx.needs_input_grad[9:12]
+        return ((None,) * 9 + (gq0 if n3[0] else None, gdq0 if n3[1] else None, gtau if n3[2] else None)
+                + tuple(grads.get(k) for k in NAMES) + _parameter_grads(ctx, gpi, gcomp, 17))
+
+
 def _no_parameters_with_wrenches(parameters, component_parameters):
     if parameters is not None or component_parameters is not None:
         raise ValueError("ext_wrenches together with parameters / component_parameters is not served yet: the parameter gradients with "
@@ -344,8 +412,8 @@ def rollout(chain, q0, Dq0, tau, dt, integrator="rk4", n_steps=None, trajectory=
         n_steps = tau.shape[0]
     if feedback is not None:
         if parameters is not None or component_parameters is not None:
-            raise ValueError("feedback together with parameters / component_parameters is not served yet: the parameter gradients of the "
-                             "closed loop are the follow-up")
+            raise ValueError("feedback together with parameters / component_parameters is not served by rollout: the parameter gradients "
+                             "of the closed loop, its follow-up, come from closed_loop_rollout")
         return RolloutFeedbackFunction.apply(chain, components, layout, integrator, float(dt), int(n_steps), bool(trajectory), ext_link,
                                              bool(feedback.hold), bool(feedback.command_trajectory), q0, Dq0, tau, feedback.q_ref,
                                              feedback.Dq_ref, feedback.kp, feedback.kd, feedback.tau_limit, ext_wrenches)
@@ -357,3 +425,27 @@ def rollout(chain, q0, Dq0, tau, dt, integrator="rk4", n_steps=None, trajectory=
         return RolloutFunction.apply(chain, components, layout, integrator, float(dt), int(n_steps), bool(trajectory), q0, Dq0, tau)
     return RolloutParametersFunction.apply(chain, components, layout, integrator, float(dt), int(n_steps), bool(trajectory), q0, Dq0, tau,
                                            parameters, component_parameters)
+
+
+def closed_loop_rollout(chain, q0, Dq0, tau, dt, feedback, integrator="rk4", n_steps=None, trajectory=False, components=None, layout="sample",
+                        parameters=None, component_parameters=None):
+    """Differentiable ``Chain.rollout(feedback=)`` with the model among the inputs (the module docstring): what closed-loop output-error
+    identification descends through.  feedback: a ``rosdyn_amd.Feedback``; tau is its feed-forward term.  Returns (q_end, Dq_end), with
+    trajectory=True also (q_traj, Dq_traj), and with ``feedback.command_trajectory`` the command trajectory last.
+    Without parameters and component_parameters it returns what ``rollout(feedback=)`` returns.  With either, the closed loop runs on
+    ``chain.withParameters(parameters)`` / ``components.withParameters(component_parameters)`` and gradients flow to q0, Dq0, tau, the
+    law's tensors, parameters and component_parameters; the backward is one ``Chain.rolloutParameterAdjoint(feedback=)`` call (chains
+    that call serves: at most 10 input joints).  A failed sample is NaN in its own gradients and adds nothing to the parameter gradients."""
+    if feedback is None:
+        raise ValueError("closed_loop_rollout needs feedback (rollout serves the open loop)")
+    if parameters is None and component_parameters is None:
+        return rollout(chain, q0, Dq0, tau, dt, integrator=integrator, n_steps=n_steps, trajectory=trajectory, components=components,
+                       layout=layout, feedback=feedback)
+    if n_steps is None:
+        if tau.dim() != 3:
+            raise ValueError("torques shaped like q0 need an explicit n_steps")
+        n_steps = tau.shape[0]
+    return RolloutFeedbackParametersFunction.apply(chain, components, layout, integrator, float(dt), int(n_steps), bool(trajectory),
+                                                   bool(feedback.hold), bool(feedback.command_trajectory), q0, Dq0, tau, feedback.q_ref,
+                                                   feedback.Dq_ref, feedback.kp, feedback.kd, feedback.tau_limit, parameters,
+                                                   component_parameters)

@@ -756,21 +756,38 @@ class Chain(object):
 
     def rolloutParameterAdjoint(self, q0, Dq0, tau, dt, q_traj, Dq_traj, gq_end=None, gDq_end=None, gq_traj=None, gDq_traj=None,
                                 integrator="rk4", n_steps=None, layout="sample", components=None, sum_tau=False, out=None, chunk_samples=0,
-                                workspace=None, accumulate=False):
+                                workspace=None, accumulate=False, feedback=None, want_feedback=(), gu_traj=None, sum_ref=None,
+                                ext_wrenches=None, ext_link=None):
         """rolloutAdjoint with the gradients with respect to the model's parameters (include/rdyn.h: rdyn_rollout_adjoint_parameters; no
         reference counterpart).  The arguments are rolloutAdjoint's; returns (gq0, gDq0, gtau, gpi, gcomp, status): the first three and the
         status are rolloutAdjoint's, bit for bit; gpi (10 getJointsNumber(),) = dL/d(inertial parameters, the order of
         getNominalParameters) and gcomp (components.columns,) = dL/d(component parameters, column order; None without components), each
         summed over the samples whose status is 1 -- a failed sample contributes nothing -- and reproducible bit for bit from run to run.
         out may also hold "gpi" and "gcomp": preallocated tensors, which accumulate=True adds to instead of overwriting (a horizon split into
-        chained calls).  Chains with more than 10 input joints raise RdynError (RDYN_ERR_UNSUPPORTED)."""
+        chained calls).  Chains with more than 10 input joints raise RdynError (RDYN_ERR_UNSUPPORTED).
+        feedback: the forward call's rosdyn_amd.Feedback (rdyn_rollout_adjoint_feedback_parameters): the adjoint is that of
+        rollout(feedback=) -- rolloutAdjoint(feedback=)'s bits in gq0, gDq0, gtau, the status and the law's gradients -- and gpi / gcomp are
+        the parameter gradients of the closed loop, every product taken at the command the forward call applied.  want_feedback,
+        gu_traj, sum_ref: as in rolloutAdjoint; returns (gq0, gDq0, gtau, gpi, gcomp, status) followed by the law's gradients in
+        want_feedback order.  accumulate=True then continues the law's sums in out as well as gpi / gcomp (a split horizon wants both).
+        ext_wrenches (with ext_link): the parameter gradients with external wrenches are not served yet; the library's
+        RDYN_ERR_UNSUPPORTED is raised as RdynError."""
+        closed = None
+        if feedback is not None:
+            closed = (feedback, tuple(want_feedback), gu_traj, bool(accumulate), sum_ref)
+        elif want_feedback or gu_traj is not None or sum_ref is not None:
+            raise ValueError("want_feedback, gu_traj and sum_ref need feedback")
+        if ext_wrenches is None and ext_link is not None:
+            raise ValueError("ext_link needs ext_wrenches")
+        wrenches = None if ext_wrenches is None else (ext_wrenches, ext_link, False, False)
         return self._rollout_adjoint(q0, Dq0, tau, dt, q_traj, Dq_traj, gq_end, gDq_end, gq_traj, gDq_traj, integrator, n_steps, layout, components,
-                                     sum_tau, out, chunk_samples, workspace, bool(accumulate))
+                                     sum_tau, out, chunk_samples, workspace, bool(accumulate), wrenches, closed)
 
     def _rollout_adjoint(self, q0, Dq0, tau, dt, q_traj, Dq_traj, gq_end, gDq_end, gq_traj, gDq_traj, integrator, n_steps, layout, components,
                          sum_tau, out, chunk_samples, workspace, accumulate, wrenches=None, closed=None):
         """the two calls above; accumulate None: without the parameter gradients; wrenches: None, or rolloutAdjoint's (ext_wrenches,
-        ext_link, want_ext, sum_ext); closed: None, or rolloutAdjoint's (feedback, want_feedback, gu_traj, accumulate, sum_ref)"""
+        ext_link, want_ext, sum_ext); closed: None, or rolloutAdjoint's (feedback, want_feedback, gu_traj, accumulate, sum_ref).  With
+        the parameter gradients AND wrenches or a law: rdyn_rollout_adjoint_feedback_parameters"""
         torch = _torch()
         b, N, lay = self._batch(layout, q0, Dq0)
         if integrator not in _lib.INTEGRATORS:
@@ -864,10 +881,14 @@ class Chain(object):
                     grads.append(t)
                 gf.gref_step_stride = 0 if sum_ref else q0.numel()
             ref = lambda x: C.byref(x) if x is not None else None
-            check(lib().rdyn_rollout_adjoint_feedback(self._h, C.byref(b), C.byref(d), comps, n_comps, ref(ext), C.byref(g), ref(fb), ref(gf),
-                                                      chunk_samples, None, 0))
-            return (gq0, gdq0, gtau, status) + ((gext,) if want_ext else ()) + tuple(grads)
-        if accumulate is None:
+            if accumulate is None:
+                check(lib().rdyn_rollout_adjoint_feedback(self._h, C.byref(b), C.byref(d), comps, n_comps, ref(ext), C.byref(g), ref(fb), ref(gf),
+                                                          chunk_samples, None, 0))
+                return (gq0, gdq0, gtau, status) + ((gext,) if want_ext else ()) + tuple(grads)
+            law_grads = tuple(grads)
+            nbytes = lib().rdyn_rollout_adjoint_feedback_parameters_workspace_bytes(self._h, C.byref(d), comps, n_comps, ref(ext), ref(fb), N,
+                                                                                    chunk_samples)
+        elif accumulate is None:
             nbytes = lib().rdyn_rollout_adjoint_workspace_bytes(self._h, C.byref(d), N, chunk_samples)
         else:
             nbytes = lib().rdyn_rollout_adjoint_parameters_workspace_bytes(self._h, C.byref(d), comps, n_comps, N, chunk_samples)
@@ -889,8 +910,13 @@ class Chain(object):
                 raise ValueError("out[%r] must be a contiguous float64 tensor of %d entries" % (key, size))
             grads[key] = t
         pg = _lib.ParameterGradient(grads["gpi"].data_ptr(), ptr(grads["gcomp"]), 1 if accumulate else 0)
+        gcomp = grads["gcomp"] if components is not None else None
+        if wrenches is not None or closed is not None:
+            check(lib().rdyn_rollout_adjoint_feedback_parameters(self._h, C.byref(b), C.byref(d), comps, n_comps, ref(ext), C.byref(g), ref(fb),
+                                                                 ref(gf), C.byref(pg), chunk_samples, *ws))
+            return (gq0, gdq0, gtau, grads["gpi"], gcomp, status) + law_grads
         check(lib().rdyn_rollout_adjoint_parameters(self._h, C.byref(b), C.byref(d), comps, n_comps, C.byref(pg), chunk_samples, *ws))
-        return gq0, gdq0, gtau, grads["gpi"], (grads["gcomp"] if components is not None else None), status
+        return gq0, gdq0, gtau, grads["gpi"], gcomp, status
 
     def getRegressor(self, q, Dq, DDq, layout="sample", y_layout=None, out=None, tau_out=None, with_torque=False):
         """Regressor (and optionally the fused joint torque).

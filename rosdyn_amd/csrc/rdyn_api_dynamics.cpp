@@ -1115,8 +1115,9 @@ static AdjointParamLayout adjoint_param_layout(const rdyn_chain* c, const rdyn_c
 }
 
 // who = the entry point (error texts); pg null: rdyn_rollout_adjoint; ext with w (never with pg): rdyn_rollout_adjoint_ext with wrenches,
-// gext its gradient selection (may be null); fb (never with pg): rdyn_rollout_adjoint_feedback with the law, gfb its gradient selection
-// (may be null)
+// gext its gradient selection (may be null); fb: rdyn_rollout_adjoint_feedback with the law, gfb its gradient selection (may be null);
+// fb with pg: rdyn_rollout_adjoint_feedback_parameters (rdyn_rollout_adjoint_fb_params.hip), the closed loop's launch with the
+// accumulators of the parameter route and the same reduction behind it
 static int rollout_adjoint(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_adjoint_desc* d, const rdyn_component* comps, int n_comps,
                            const rdyn_parameter_gradient* pg, bool with_pg, int64_t chunk_samples, void* workspace, size_t workspace_bytes,
                            const char* who, const rdyn_ext_wrenches* ext = nullptr, const rdyn_ext_wrench_gradient* gext = nullptr,
@@ -1191,6 +1192,13 @@ static int rollout_adjoint(const rdyn_chain* c, const rdyn_batch* b, const rdyn_
   }
   const bool law_out = gf.gq_ref || gf.gdq_ref || gf.gkp || gf.gkd || gf.glim;
   if (N > 0 && !with_pg && !d->gq0 && !d->gdq0 && !d->gtau && !gw && !law_out) return refuse(who, "every output is null");
+  if (x.w && with_pg)
+  {
+    rdyn_set_error("%s: the parameter gradients with external wrenches are the follow-up: rdyn_rollout_adjoint_feedback serves the wrenches, "
+                   "this call the parameters, not yet both",
+                   who);
+    return RDYN_ERR_UNSUPPORTED;
+  }
   if (x.w && (st = ext_reverse_refusal(c, who)) != RDYN_OK) return st;
   if (fb && fwd_dyn_by_chunks(c))
   {
@@ -1243,10 +1251,10 @@ static int rollout_adjoint(const rdyn_chain* c, const rdyn_batch* b, const rdyn_
     if ((d->gq0 || d->gdq0) && stage_records(b, d->gq0, d->gdq0)) a.staged |= 1;
     if (d->gtau && stage_records(b, d->gtau) && (d->gtau_step_stride * (int64_t)sizeof(double)) % 128 == 0) a.staged |= 2;
     a.t = k.table;
+    RdynRolloutAdjointFbArgs af;
+    memset(&af, 0, sizeof af);
     if (fb)
     {
-      RdynRolloutAdjointFbArgs af;
-      memset(&af, 0, sizeof af);
       af.ax.a = a;
       af.ax.x = x;
       af.ax.gw = gw;
@@ -1263,10 +1271,13 @@ static int rollout_adjoint(const rdyn_chain* c, const rdyn_batch* b, const rdyn_
       if ((gf.gq_ref || gf.gdq_ref) && gf.gref_step != 0 && stage_records(b, gf.gq_ref, gf.gdq_ref) &&
           (gf.gref_step * (int64_t)sizeof(double)) % 128 == 0)
         af.g.staged = 1;
-      RDYN_HIP_TRY(rdyn_launch_rollout_adjoint_feedback(k.sw->n_joints(), af, k.stream));
-      return RDYN_OK;
+      if (!with_pg)
+      {
+        RDYN_HIP_TRY(rdyn_launch_rollout_adjoint_feedback(k.sw->n_joints(), af, k.stream));
+        return RDYN_OK;
+      }
     }
-    if (x.w)
+    if (x.w && !fb)
     {
       RdynRolloutAdjointExtArgs ax;
       memset(&ax, 0, sizeof ax);
@@ -1297,7 +1308,12 @@ static int rollout_adjoint(const rdyn_chain* c, const rdyn_batch* b, const rdyn_
       if (st != RDYN_OK) return st;
       for (int f = 0; f < c->n_joints(); ++f) sa.red_of[f] = c->red_of[f];
     }
-    if (d->integrator == RDYN_INTEGRATOR_RK4)
+    const bool rk4 = d->integrator == RDYN_INTEGRATOR_RK4;
+    if (fb && rk4)
+      RDYN_HIP_TRY(rdyn_launch_rollout_adjoint_feedback_params_rk4(k.sw->n_joints(), af, acc, N, st_final, C, k.stream));
+    else if (fb)
+      RDYN_HIP_TRY(rdyn_launch_rollout_adjoint_feedback_params_euler(k.sw->n_joints(), af, acc, N, st_final, C, k.stream));
+    else if (rk4)
       RDYN_HIP_TRY(rdyn_launch_rollout_adjoint_params_rk4(k.sw->n_joints(), a, acc, N, st_final, C, k.stream));
     else
       RDYN_HIP_TRY(rdyn_launch_rollout_adjoint_params_euler(k.sw->n_joints(), a, acc, N, st_final, C, k.stream));
@@ -1472,4 +1488,26 @@ int rdyn_rollout_adjoint_feedback(const rdyn_chain* c, const rdyn_batch* b, cons
   }
   if ((!ext || !ext->w) && gext && gext->gw) return refuse(who, "a wrench gradient without external wrenches");
   return rollout_adjoint(c, b, d, comps, n_comps, nullptr, false, chunk_samples, workspace, workspace_bytes, who, ext, gext, fb, gfb);
+}
+
+size_t rdyn_rollout_adjoint_feedback_parameters_workspace_bytes(const rdyn_chain* c, const rdyn_rollout_adjoint_desc* d, const rdyn_component* comps,
+                                                                int n_comps, const rdyn_ext_wrenches* ext, const rdyn_feedback* fb,
+                                                                int64_t n_samples, int64_t chunk_samples)
+{
+  (void)fb;  // the law needs no workspace: with it or without, the accumulators of the parameter route
+  if (ext && ext->w) return 0;  // refused
+  return rdyn_rollout_adjoint_parameters_workspace_bytes(c, d, comps, n_comps, n_samples, chunk_samples);
+}
+
+int rdyn_rollout_adjoint_feedback_parameters(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_adjoint_desc* d, const rdyn_component* comps,
+                                             int n_comps, const rdyn_ext_wrenches* ext, const rdyn_ext_wrench_gradient* gext,
+                                             const rdyn_feedback* fb, const rdyn_feedback_gradient* gfb, const rdyn_parameter_gradient* pg,
+                                             int64_t chunk_samples, void* workspace, size_t workspace_bytes)
+{
+  const char* const who = "rdyn_rollout_adjoint_feedback_parameters";
+  if (!fb && gfb && (gfb->gq_ref || gfb->gdq_ref || gfb->gkp || gfb->gkd || gfb->glim || gfb->gu_traj))
+    return refuse(who, "a feedback gradient without a feedback law");
+  if ((!ext || !ext->w) && gext && gext->gw) return refuse(who, "a wrench gradient without external wrenches");
+  if (!fb && (!ext || !ext->w)) return rdyn_rollout_adjoint_parameters(c, b, d, comps, n_comps, pg, chunk_samples, workspace, workspace_bytes);
+  return rollout_adjoint(c, b, d, comps, n_comps, pg, true, chunk_samples, workspace, workspace_bytes, who, ext, gext, fb, gfb);
 }

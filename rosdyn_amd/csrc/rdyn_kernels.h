@@ -821,6 +821,12 @@ struct RdynRolloutAdjointFbArgs
   RdynFeedbackGradArgs g;
 };
 hipError_t rdyn_launch_rollout_adjoint_feedback(int n_joints, const RdynRolloutAdjointFbArgs& a, hipStream_t st);
+// ... with the gradients with respect to the parameters (rdyn_rollout_adjoint_fb_params.hip, one object per integrator; a.ax.x.w null): the
+// same sweep, and every product adds its rows to acc[col * ld + s] as rdyn_launch_rollout_adjoint_params_* does
+hipError_t rdyn_launch_rollout_adjoint_feedback_params_euler(int n_joints, const RdynRolloutAdjointFbArgs& a, double* acc, int64_t ld,
+                                                             int32_t* status, int n_comp_cols, hipStream_t st);
+hipError_t rdyn_launch_rollout_adjoint_feedback_params_rk4(int n_joints, const RdynRolloutAdjointFbArgs& a, double* acc, int64_t ld, int32_t* status,
+                                                           int n_comp_cols, hipStream_t st);
 
 // pieces of rdyn_identification_tsqr for the multi-device form (rdyn_api_tsqr.cpp): widths of the swept / the chain's factor, the factor of
 // the swept chain alone, the expansion (+ accumulation) of a swept factor

@@ -1066,6 +1066,22 @@ public:
     chk(rdyn_rollout_adjoint_parameters(m_h, &b, &desc, comps.empty() ? nullptr : comps.data(), (int)comps.size(), &pg, chunk_samples, workspace,
                                         workspace_bytes));
   }
+  // ... of a closed-loop rollout (rdyn_rollout_adjoint_feedback_parameters; fb = the forward call's law, gfb = where the law's gradients
+  // go, nullptr = none of them): rolloutAdjointBatch(comps, nullptr, nullptr, fb, gfb, ...)'s bits and, beside them, pg.gpi / pg.gcomp taken
+  // at the commands the closed loop applied.  External wrenches are not served with the parameter gradients yet.
+  size_t rolloutParameterAdjointWorkspaceBytes(const std::vector<rdyn_component>& comps, const rdyn_rollout_adjoint_desc& desc,
+                                               const rdyn_feedback& fb, int64_t n_samples, int64_t chunk_samples = 0) const
+  {
+    return rdyn_rollout_adjoint_feedback_parameters_workspace_bytes(m_h, &desc, comps.empty() ? nullptr : comps.data(), (int)comps.size(), nullptr,
+                                                                    &fb, n_samples, chunk_samples);
+  }
+  void rolloutParameterAdjointBatch(const std::vector<rdyn_component>& comps, const rdyn_feedback& fb, const rdyn_feedback_gradient* gfb,
+                                    const rdyn_batch& b, const rdyn_rollout_adjoint_desc& desc, const rdyn_parameter_gradient& pg,
+                                    int64_t chunk_samples, void* workspace, size_t workspace_bytes) const
+  {
+    chk(rdyn_rollout_adjoint_feedback_parameters(m_h, &b, &desc, comps.empty() ? nullptr : comps.data(), (int)comps.size(), nullptr, nullptr, &fb,
+                                                 gfb, &pg, chunk_samples, workspace, workspace_bytes));
+  }
   // derivatives of the joint torque of a batch (b.q, b.dq, b.ddq; every output n x n per sample, any may be null): rdyn_joint_torque_derivatives
   void getJointTorqueDerivativesBatch(const rdyn_batch& b, double* dtau_dq, double* dtau_dDq, double* M = nullptr) const
   {
