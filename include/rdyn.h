@@ -519,7 +519,8 @@ size_t rdyn_rollout_ext_workspace_bytes(const rdyn_chain* chain, const rdyn_roll
 int rdyn_rollout_ext(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_rollout_desc* desc, const rdyn_component* comps,
                      int n_comps, const rdyn_ext_wrenches* ext, int64_t chunk_samples, void* workspace, size_t workspace_bytes);
 
-/* Closed-loop rollouts (no reference counterpart): rdyn_rollout_ext with a joint-space PD controller and actuator limits in the loop.  A
+/* Closed-loop rollouts (no reference counterpart): rdyn_rollout_ext with a joint-space PD controller and actuator limits in the loop
+ * (the model-based laws -- gravity compensation, computed torque -- are rdyn_rollout_model_feedback's, below).  A
  * feedback torque depends on the state, so like the components it cannot be folded into tau across steps.  n = the number of active
  * joints; every array of rdyn_feedback is in INPUT order.  At an evaluation with state (q, Dq) in step t, per sample and joint j,
  *     u_j = fma(kd_j, Dq_ref[t]_j - Dq_j, fma(kp_j, q_ref[t]_j - q_j, tau_ff[t]_j))        (this order, on every route)
@@ -579,6 +580,51 @@ size_t rdyn_rollout_feedback_workspace_bytes(const rdyn_chain* chain, const rdyn
 int rdyn_rollout_feedback(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_rollout_desc* desc, const rdyn_component* comps,
                           int n_comps, const rdyn_ext_wrenches* ext, const rdyn_feedback* fb, int64_t chunk_samples, void* workspace,
                           size_t workspace_bytes);
+
+/* Closed-loop rollouts under a model-based law (no reference counterpart): rdyn_rollout_feedback with the controller's own model of the
+ * arm inside the loop -- PD with gravity compensation, and computed torque (inverse-dynamics control).  `model` is a chain of its own
+ * (rdyn_chain_with_parameters makes "the same arm with other inertial parameters"; it may be the plant chain itself); its geometry,
+ * gravity and parameters may differ from the plant's: the mismatch is what such a simulation is for.  fb is the rdyn_feedback of
+ * rdyn_rollout_feedback: references, gains, hold, limits and tau_traj keep their addressing and meaning.
+ * RNEA_m(q, v, a) = the function rdyn_joint_torque evaluates for `model` as configured (its own inertial parameters, geometry and
+ * gravity; input order; locked joints at 0); no components and no wrenches enter the model.  At an evaluation at the state (q, Dq) in
+ * step t, per sample and input joint j:
+ *   RDYN_LAW_COMPUTED_TORQUE
+ *     a_j = fma(kd_j, Dq_ref[t]_j - Dq_j, fma(kp_j, q_ref[t]_j - q_j, ddq_ref[t]_j))
+ *     u   = tau_ff[t] + RNEA_m(q, Dq, a),  then the clamp of rdyn_rollout_feedback
+ *     kp and kd are in 1/s^2 and 1/s here.  kd == NULL: the velocity term is not formed and dq_ref is not read.
+ *   RDYN_LAW_GRAVITY_COMPENSATION
+ *     u_j = the unclamped PD command of rdyn_rollout_feedback (the same fma order) + RNEA_m(q, 0, 0)_j,  then the clamp
+ * hold decides where the law is formed, the model sweep included: hold = 1 at the head of the step, held over the stages; hold = 0 at
+ * every stage at that stage's own state.  Semi-implicit Euler is one computation under both modes.  Components and wrenches of the
+ * plant act behind the clamp, as in rdyn_rollout_feedback; tau_traj, the sticky status, NaN propagation, aliasing and the split horizon
+ * (ddq_ref advances by t0 * ref_step_stride like the other references) are that call's.
+ * Routing, before any device work:
+ *   mfb == NULL IS rdyn_rollout_feedback: the same kernels, the same bits, the same workspace query.
+ *   with mfb, the call serves the chains rdyn_rollout_feedback runs in registers: at most RDYN_MAX_SWEPT_JOINTS swept joints, longer
+ *     chains through their reduced companion (the model's companion is swept for the law).  ONE launch for the horizon, the workspace
+ *     query answers 0, no allocation and no synchronisation: capturable into a graph once both chains have been used on the device.
+ *   chains for which rdyn_rollout_feedback takes the chunked route: RDYN_ERR_UNSUPPORTED (the message names the route); the query
+ *     answers 0.
+ * Errors, all RDYN_ERR_INVALID_ARGUMENT before any device work: every argument error of rdyn_rollout_feedback, fb being required once
+ * mfb is given; a NULL model; an unknown law; ddq_ref with RDYN_LAW_GRAVITY_COMPENSATION; a model that differs from the chain in the
+ * number of chain joints, in any joint type, in the input-joint selection or order, or in the swept joint count of the chain actually
+ * swept.  n_samples = 0 is RDYN_OK.
+ * Reverse mode is the follow-up: rdyn_rollout_adjoint_feedback is the transpose of the PD law alone and does not take a
+ * rdyn_model_feedback; Chain.rolloutAdjoint and rosdyn_amd.autograd raise an error when handed a rosdyn_amd.ModelFeedback. */
+typedef enum rdyn_feedback_law { RDYN_LAW_GRAVITY_COMPENSATION = 1, RDYN_LAW_COMPUTED_TORQUE = 2 } rdyn_feedback_law;
+typedef struct rdyn_model_feedback
+{
+  const rdyn_chain* model;  /* the controller's model of the arm; may be the plant chain itself; required */
+  int32_t law;              /* rdyn_feedback_law */
+  const double* ddq_ref;    /* computed torque only: step t at ddq_ref + t * fb->ref_step_stride, addressed like batch->q; NULL = zero */
+} rdyn_model_feedback;
+size_t rdyn_rollout_model_feedback_workspace_bytes(const rdyn_chain* chain, const rdyn_rollout_desc* desc, const rdyn_ext_wrenches* ext,
+                                                   const rdyn_feedback* fb, const rdyn_model_feedback* mfb, int64_t n_samples,
+                                                   int64_t chunk_samples);
+int rdyn_rollout_model_feedback(const rdyn_chain* chain, const rdyn_batch* batch, const rdyn_rollout_desc* desc, const rdyn_component* comps,
+                                int n_comps, const rdyn_ext_wrenches* ext, const rdyn_feedback* fb, const rdyn_model_feedback* mfb,
+                                int64_t chunk_samples, void* workspace, size_t workspace_bytes);
 
 /* Derivatives of the forward dynamics (no reference counterpart): the linearisation of DDq = FD_c(q, Dq, tau).  Per sample, with FD_c the
  * function of rdyn_forward_dynamics_components for the chain AS CONFIGURED (input-joint selection and order, locked joints, the reduced

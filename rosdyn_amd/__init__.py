@@ -4,5 +4,5 @@ The product is the C-ABI shared library ``librdyn_hip.so`` (include/rdyn.h, sour
 this package is the thin Python/ctypes mirror used by the tests and bench.py.
 """
 from .chain import Chain, createChain  # noqa: F401
-from .feedback import Feedback  # noqa: F401
+from .feedback import Feedback, ModelFeedback  # noqa: F401
 from ._lib import LIB_PATH, RdynError  # noqa: F401

@@ -56,6 +56,13 @@ class Feedback(C.Structure):
                 ("gains_per_sample", C.c_int32), ("hold", C.c_int32), ("tau_limit", C.c_void_p), ("tau_traj", C.c_void_p)]
 
 
+class ModelFeedback(C.Structure):
+    _fields_ = [("model", C.c_void_p), ("law", C.c_int32), ("ddq_ref", C.c_void_p)]
+
+
+LAWS = {"gravity_compensation": 1, "computed_torque": 2}
+
+
 class ExtWrenchGradient(C.Structure):
     _fields_ = [("gw", C.c_void_p), ("step_stride", C.c_int64)]
 
@@ -143,6 +150,10 @@ SYMBOLS = {
                                                            C.c_int64]),
     "rdyn_rollout_feedback": (_I, [_VP, _BP, C.POINTER(RolloutDesc), _VP, _I, C.POINTER(ExtWrenches), C.POINTER(Feedback), C.c_int64, _VP,
                                    C.c_size_t]),
+    "rdyn_rollout_model_feedback_workspace_bytes": (C.c_size_t, [_VP, C.POINTER(RolloutDesc), C.POINTER(ExtWrenches), C.POINTER(Feedback),
+                                                                 C.POINTER(ModelFeedback), C.c_int64, C.c_int64]),
+    "rdyn_rollout_model_feedback": (_I, [_VP, _BP, C.POINTER(RolloutDesc), _VP, _I, C.POINTER(ExtWrenches), C.POINTER(Feedback),
+                                         C.POINTER(ModelFeedback), C.c_int64, _VP, C.c_size_t]),
     "rdyn_joint_torque_derivatives": (_I, [_VP, _BP, _VP, _VP, _VP]),
     "rdyn_forward_dynamics_derivatives_workspace_bytes": (C.c_size_t, [_VP, C.c_int64]),
     "rdyn_forward_dynamics_derivatives": (_I, [_VP, _BP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP, C.c_size_t]),

@@ -240,6 +240,13 @@ class RolloutExtFunction(torch.autograd.Function):
         return (None,) * 8 + (gq0 if need[0] else None, gdq0 if need[1] else None, gtau if need[2] else None, gext)
 
 
+def _refuse_model_law(feedback):
+    from .feedback import ModelFeedback
+    if isinstance(feedback, ModelFeedback):
+        raise NotImplementedError("rosdyn_amd.autograd does not differentiate a model-based law (rosdyn_amd.ModelFeedback) yet: its adjoint is "
+                                  "the follow-up; Chain.rollout(feedback=) runs it forward")
+
+
 class RolloutFeedbackFunction(torch.autograd.Function):
     """RolloutFunction around the closed loop: the law's references, gains and limits (and, optionally, external link wrenches) among the
     inputs, the command trajectory (optionally) among the outputs; the backward is ONE Chain.rolloutAdjoint(feedback=) call.  Dq_ref, kd,
@@ -405,7 +412,9 @@ def rollout(chain, q0, Dq0, tau, dt, integrator="rk4", n_steps=None, trajectory=
     ext_wrenches, ext_link (the module docstring): external link wrenches as ``Chain.rollout`` takes them, differentiable: one step's
     record is held over the horizon (its gradient is the sum over the steps), a leading T axis is one record per step.
     feedback (the module docstring): a ``rosdyn_amd.Feedback``, the closed loop; tau is its feed-forward term and the law's tensors are
-    differentiable.  With ``feedback.command_trajectory`` the command trajectory is appended to the returned tuple."""
+    differentiable.  With ``feedback.command_trajectory`` the command trajectory is appended to the returned tuple.  A
+    ``rosdyn_amd.ModelFeedback`` raises NotImplementedError: the adjoint of the model-based laws is not served yet."""
+    _refuse_model_law(feedback)
     if n_steps is None:
         if tau.dim() != 3:
             raise ValueError("torques shaped like q0 need an explicit n_steps")
@@ -438,6 +447,7 @@ def closed_loop_rollout(chain, q0, Dq0, tau, dt, feedback, integrator="rk4", n_s
     that call serves: at most 10 input joints).  A failed sample is NaN in its own gradients and adds nothing to the parameter gradients."""
     if feedback is None:
         raise ValueError("closed_loop_rollout needs feedback (rollout serves the open loop)")
+    _refuse_model_law(feedback)
     if parameters is None and component_parameters is None:
         return rollout(chain, q0, Dq0, tau, dt, integrator=integrator, n_steps=n_steps, trajectory=trajectory, components=components,
                        layout=layout, feedback=feedback)

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .feedback import ModelFeedback
 from ._lib import LAYOUT_ELEMENT_MAJOR, LAYOUT_SAMPLE_MAJOR, Batch, RegressorLayout, check, lib
 
 
@@ -478,6 +479,26 @@ class Chain(object):
             f.tau_limit = feedback.tau_limit.data_ptr()
         return f
 
+    def _model_feedback(self, q0, feedback, fb, steps):
+        """The rdyn_model_feedback of a rosdyn_amd.ModelFeedback; fb: its rdyn_feedback (the acceleration reference shares its step stride)"""
+        torch = _torch()
+        if not isinstance(feedback.model, Chain):
+            raise ValueError("ModelFeedback needs a Chain as its model")
+        m = _lib.ModelFeedback()
+        m.model, m.law = feedback.model._h, _lib.LAWS[feedback.law]
+        ref = feedback.DDq_ref
+        if ref is not None:
+            if ref.dtype != torch.float64 or not ref.is_cuda or not ref.is_contiguous() or ref.device != q0.device:
+                raise ValueError("inputs must be contiguous float64 CUDA tensors")
+            rec = tuple(q0.shape)
+            per_step = ref.dim() == len(rec) + 1 and tuple(ref.shape[1:]) == rec and ref.shape[0] >= steps
+            if not (tuple(ref.shape) == rec or per_step):
+                raise ValueError("Input data dimensions mismatch")
+            if (q0.numel() if per_step else 0) != fb.ref_step_stride:
+                raise ValueError("q_ref and DDq_ref must both be per step or both constant")
+            m.ddq_ref = ref.data_ptr()
+        return m
+
     def rollout(self, q0, Dq0, tau, dt, integrator="rk4", n_steps=None, layout="sample", trajectory_every=0, out=None, chunk_samples=0,
                 workspace=None, components=None, ext_wrenches=None, ext_link=None, feedback=None):
         """Rollout (include/rdyn.h: rdyn_rollout; no reference counterpart): n_steps integrator steps of size dt of the forward dynamics
@@ -493,7 +514,9 @@ class Chain(object):
         stage's own q (rdyn_rollout_ext): one record -- (N, links, 6) / (links * 6, N), or (N, 6) / (6, N) with ext_link -- is constant
         over the horizon; a leading dimension T makes the sequence per step, held over each step like the torques.
         feedback: None, or a rosdyn_amd.Feedback: the closed loop (rdyn_rollout_feedback), tau its feed-forward term.  With
-        feedback.command_trajectory and trajectory_every >= 1 the command trajectory is appended as the last returned tensor."""
+        feedback.command_trajectory and trajectory_every >= 1 the command trajectory is appended as the last returned tensor.  A
+        rosdyn_amd.ModelFeedback runs a model-based law (computed torque, gravity compensation: rdyn_rollout_model_feedback), for the
+        chains a Feedback runs in one launch; nothing more is allocated than for a Feedback."""
         torch = _torch()
         b, N, lay = self._batch(layout, q0, Dq0)
         if integrator not in _lib.INTEGRATORS:
@@ -527,13 +550,18 @@ class Chain(object):
             d.traj_step_stride, d.traj_every = q0.numel(), int(trajectory_every)
         ext = self._ext_wrenches(q0, N, lay, ext_wrenches, ext_link, steps=int(n_steps)) if ext_wrenches is not None else None
         fb = tau_traj = None
+        mfb = None
         if feedback is not None:
             fb = self._feedback(q0, feedback, int(n_steps))
             if feedback.command_trajectory and trajectory_every:
                 tau_traj = torch.empty_like(q_traj)
                 fb.tau_traj = tau_traj.data_ptr()
             ext_p = C.byref(ext) if ext is not None else None
-            nbytes = lib().rdyn_rollout_feedback_workspace_bytes(self._h, C.byref(d), ext_p, C.byref(fb), N, chunk_samples)
+            if isinstance(feedback, ModelFeedback):
+                mfb = self._model_feedback(q0, feedback, fb, int(n_steps))
+                nbytes = lib().rdyn_rollout_model_feedback_workspace_bytes(self._h, C.byref(d), ext_p, C.byref(fb), C.byref(mfb), N, chunk_samples)
+            else:
+                nbytes = lib().rdyn_rollout_feedback_workspace_bytes(self._h, C.byref(d), ext_p, C.byref(fb), N, chunk_samples)
         elif ext is not None:
             nbytes = lib().rdyn_rollout_ext_workspace_bytes(self._h, C.byref(d), C.byref(ext), N, chunk_samples)
         else:
@@ -541,7 +569,11 @@ class Chain(object):
         if workspace is None and nbytes > 0:
             workspace = torch.empty((nbytes,), dtype=torch.uint8, device=q0.device)
         ws = (workspace.data_ptr() if workspace is not None else None, workspace.numel() if workspace is not None else 0)
-        if fb is not None:
+        if mfb is not None:
+            comps, n_comps = self._component_list(components) if components is not None else (None, 0)
+            check(lib().rdyn_rollout_model_feedback(self._h, C.byref(b), C.byref(d), comps, n_comps, ext_p, C.byref(fb), C.byref(mfb),
+                                                    chunk_samples, *ws))
+        elif fb is not None:
             comps, n_comps = self._component_list(components) if components is not None else (None, 0)
             check(lib().rdyn_rollout_feedback(self._h, C.byref(b), C.byref(d), comps, n_comps, ext_p, C.byref(fb), chunk_samples, *ws))
         elif ext is not None:
@@ -788,6 +820,9 @@ class Chain(object):
         """the two calls above; accumulate None: without the parameter gradients; wrenches: None, or rolloutAdjoint's (ext_wrenches,
         ext_link, want_ext, sum_ext); closed: None, or rolloutAdjoint's (feedback, want_feedback, gu_traj, accumulate, sum_ref).  With
         the parameter gradients AND wrenches or a law: rdyn_rollout_adjoint_feedback_parameters"""
+        if closed is not None and isinstance(closed[0], ModelFeedback):
+            raise NotImplementedError("the adjoint of a model-based law (rosdyn_amd.ModelFeedback) is not served yet: rdyn_rollout_adjoint_feedback "
+                                      "is the transpose of the PD law alone")
         torch = _torch()
         b, N, lay = self._batch(layout, q0, Dq0)
         if integrator not in _lib.INTEGRATORS:

@@ -1,6 +1,6 @@
 // rdyn_api_dynamics.cpp -- the forward-dynamics family of the C-ABI (include/rdyn.h): rdyn_forward_dynamics(_components),
 // rdyn_rollout(_components), their forms with external link wrenches rdyn_forward_dynamics_ext and rdyn_rollout_ext, the closed loop
-// rdyn_rollout_feedback,
+// rdyn_rollout_feedback and its model-based laws rdyn_rollout_model_feedback,
 // rdyn_forward_dynamics_derivatives, rdyn_forward_dynamics_vjp, rdyn_rollout_adjoint, their parameter-gradient
 // forms rdyn_forward_dynamics_parameter_vjp and rdyn_rollout_adjoint_parameters, their forms with external link wrenches
 // rdyn_forward_dynamics_vjp_ext and rdyn_rollout_adjoint_ext, the adjoint of the closed loop rdyn_rollout_adjoint_feedback, and the
@@ -371,9 +371,13 @@ static int forward_dynamics(const rdyn_chain* c, const rdyn_batch* b, const rdyn
 // fb null: open loop.  Otherwise the closed loop (rdyn_rollout_fb.hip): one launch of k_rollout_fb, or on the chunked route
 // k_rollout_command before the pass of every evaluation whose command is formed anew (hold: the step's first), the pass taking the command
 // array of the workspace where it took tau_t.
+// mfb null: the PD law.  Otherwise a model-based law (rdyn_rollout_fb_model.hip): the chains swept in registers only, one launch of
+// k_rollout_fb_model, which sweeps the model chain (its reduced companion where the plant's is swept) where the command is formed.
+static bool model_feedback_by_chunks(const rdyn_chain* c, const rdyn_ext_wrenches* ext) { return fwd_dyn_by_chunks(c, ext && ext->w); }
+
 static int rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_desc* d, const rdyn_component* comps, int n_comps,
                    const rdyn_ext_wrenches* ext, int64_t chunk_samples, void* workspace, size_t workspace_bytes, const char* who,
-                   const rdyn_feedback* fb = nullptr)
+                   const rdyn_feedback* fb = nullptr, const rdyn_model_feedback* mfb = nullptr)
 {
   int st = check_batch(c, b, true, false, who, LONG_KERNELS);
   if (st != RDYN_OK) return st;
@@ -402,9 +406,48 @@ static int rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_
     if ((fb->hold != 0 && fb->hold != 1) || (fb->gains_per_sample != 0 && fb->gains_per_sample != 1))
       return refuse(who, "hold and gains_per_sample are 0 or 1");
   }
+  const rdyn_chain* model_sw = nullptr;  // the model chain the law sweeps
+  if (mfb)
+  {
+    if (!fb) return refuse(who, "a model-based law (mfb) without the feedback (fb) that holds its references and gains");
+    const rdyn_chain* const m = mfb->model;
+    if (!m) return refuse(who, "null model chain");
+    if (mfb->law != RDYN_LAW_GRAVITY_COMPENSATION && mfb->law != RDYN_LAW_COMPUTED_TORQUE)
+    {
+      rdyn_set_error("%s: unknown law %d (gravity compensation is %d, computed torque %d)", who, (int)mfb->law,
+                     (int)RDYN_LAW_GRAVITY_COMPENSATION, (int)RDYN_LAW_COMPUTED_TORQUE);
+      return RDYN_ERR_INVALID_ARGUMENT;
+    }
+    if (mfb->law == RDYN_LAW_GRAVITY_COMPENSATION && mfb->ddq_ref)
+      return refuse(who, "ddq_ref belongs to the computed-torque law: gravity compensation takes none");
+    if (m->n_joints() != c->n_joints())
+    {
+      rdyn_set_error("%s: the model has %d chain joints, the chain %d", who, m->n_joints(), c->n_joints());
+      return RDYN_ERR_INVALID_ARGUMENT;
+    }
+    for (int j = 0; j < c->n_joints(); ++j)
+      if (m->host_joints[(size_t)j].type != c->host_joints[(size_t)j].type)
+      {
+        rdyn_set_error("%s: chain joint %d of the model is of another type than the chain's", who, j);
+        return RDYN_ERR_INVALID_ARGUMENT;
+      }
+    if (m->active != c->active) return refuse(who, "the model's input joints differ from the chain's in selection or order");
+    if (model_feedback_by_chunks(c, ext))
+    {
+      rdyn_set_error("%s: chains that rdyn_rollout_feedback serves by its chunked route (more than %d input joints, or with external wrenches "
+                     "more than %d chain joints; this chain has %d input joints, %d chain joints) are not served with a model-based law: the "
+                     "law is swept in registers",
+                     who, RDYN_MAX_SWEPT_JOINTS, RDYN_MAX_SWEPT_JOINTS, n, c->n_joints());
+      return RDYN_ERR_UNSUPPORTED;
+    }
+    const rdyn_chain* const sw = c->long_chain() ? c->reduced.get() : c;
+    model_sw = m->long_chain() ? m->reduced.get() : m;
+    if (!model_sw || model_sw->n_joints() != sw->n_joints())
+      return refuse(who, "the model's swept chain (its reduced companion) has another joint count than the chain's");
+  }
   const RolloutLayout L = rollout_layout(c, d, N, chunk_samples, x.w != nullptr, fb != nullptr);
   DynCall k;
-  st = dyn_prepare(c, b, comps, n_comps, chunk_samples, L.s.total, workspace, workspace_bytes, who, &k, x.w != nullptr);
+  st = dyn_prepare(c, b, comps, n_comps, chunk_samples, mfb ? 0 : L.s.total, workspace, workspace_bytes, who, &k, x.w != nullptr);
   if (st != RDYN_OK || !k.run) return st;
   const int every = traj ? d->traj_every : 0;
   if (k.sw)
@@ -449,6 +492,18 @@ static int rollout(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_
       af.f.tau_traj = tau_traj;
       af.f.per_sample = fb->gains_per_sample;
       af.f.hold = fb->hold;
+      if (mfb)
+      {
+        RdynRolloutModelFbArgs am;
+        memset(&am, 0, sizeof am);
+        am.b = af;
+        st = device_const(model_sw, &am.m.model);
+        if (st != RDYN_OK) return st;
+        am.m.ddq_ref = mfb->ddq_ref;
+        am.m.law = mfb->law;
+        RDYN_HIP_TRY(rdyn_launch_rollout_model_feedback(k.sw->n_joints(), am, k.stream));
+        return RDYN_OK;
+      }
       RDYN_HIP_TRY(rdyn_launch_rollout_feedback(k.sw->n_joints(), af, k.stream));
       return RDYN_OK;
     }
@@ -743,6 +798,21 @@ int rdyn_rollout_feedback(const rdyn_chain* c, const rdyn_batch* b, const rdyn_r
                           size_t workspace_bytes)
 {
   return rollout(c, b, d, comps, n_comps, ext, chunk_samples, workspace, workspace_bytes, "rdyn_rollout_feedback", fb);
+}
+
+size_t rdyn_rollout_model_feedback_workspace_bytes(const rdyn_chain* c, const rdyn_rollout_desc* d, const rdyn_ext_wrenches* ext,
+                                                   const rdyn_feedback* fb, const rdyn_model_feedback* mfb, int64_t n_samples,
+                                                   int64_t chunk_samples)
+{
+  return mfb ? 0 : rdyn_rollout_feedback_workspace_bytes(c, d, ext, fb, n_samples, chunk_samples);
+}
+
+int rdyn_rollout_model_feedback(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_desc* d, const rdyn_component* comps, int n_comps,
+                                const rdyn_ext_wrenches* ext, const rdyn_feedback* fb, const rdyn_model_feedback* mfb, int64_t chunk_samples,
+                                void* workspace, size_t workspace_bytes)
+{
+  if (!mfb) return rdyn_rollout_feedback(c, b, d, comps, n_comps, ext, fb, chunk_samples, workspace, workspace_bytes);
+  return rollout(c, b, d, comps, n_comps, ext, chunk_samples, workspace, workspace_bytes, "rdyn_rollout_model_feedback", fb, mfb);
 }
 
 int rdyn_rollout_ext(const rdyn_chain* c, const rdyn_batch* b, const rdyn_rollout_desc* d, const rdyn_component* comps, int n_comps,

@@ -629,6 +629,23 @@ struct RdynRolloutCommandArgs
 };
 hipError_t rdyn_launch_rollout_command(const RdynRolloutCommandArgs& a, hipStream_t st);
 
+// closed-loop rollouts under a model-based law (rdyn_rollout_fb_model.hip, rdyn_model_law.h): the controller's model is swept at every
+// evaluation whose command is formed; chains swept in registers only.  With tau_m = RNEA_model (rdyn_joint_torque of the model chain):
+//   RDYN_LAW_COMPUTED_TORQUE        a = fma(kd, dq_ref - dq, fma(kp, q_ref - q, ddq_ref)),  u = clamp(tau_ff + tau_m(q, dq, a))
+//   RDYN_LAW_GRAVITY_COMPENSATION   u = clamp(fma(kd, dq_ref - dq, fma(kp, q_ref - q, tau_ff)) + tau_m(q, 0, 0))
+struct RdynModelFeedbackArgs
+{
+  const RdynChainConst* model;  // device pointer: the constants of the model chain that is swept (the same joints and input joints as the plant's)
+  const double* ddq_ref;        // computed torque, may be null (zero): step t at + t * ref_step of RdynFeedbackArgs, addressed like q
+  int law;                      // rdyn_feedback_law
+};
+struct RdynRolloutModelFbArgs
+{
+  RdynRolloutFbArgs b;
+  RdynModelFeedbackArgs m;
+};
+hipError_t rdyn_launch_rollout_model_feedback(int n_joints, const RdynRolloutModelFbArgs& a, hipStream_t st);
+
 // reverse-mode product of the forward dynamics (rdyn_fwd_dyn_vjp.hip): with ddq = FD_c(q, dq, tau) and the seed ddq_bar per sample,
 // tau_bar = M^-1 ddq_bar, q_bar = dddq_dq' ddq_bar, dq_bar = dddq_dv' ddq_bar (the matrices of RdynFwdDynDerivArgs).  Every vector is
 // addressed like q; any output may be null (not all three of the products); tau_bar may alias ddq_bar.

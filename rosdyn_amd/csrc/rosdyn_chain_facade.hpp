@@ -961,6 +961,21 @@ public:
     chk(rdyn_rollout_feedback(m_h, &b, &desc, comps.empty() ? nullptr : comps.data(), (int)comps.size(), ext, &fb, chunk_samples, workspace,
                               workspace_bytes));
   }
+  // ... under a model-based law: computed torque or PD with gravity compensation, the controller's model of the arm (mfb.model: the
+  // handle() of another chain, withParameters for instance, or of this one) swept inside the loop; fb keeps the references, gains, hold,
+  // limits and the command record (rdyn_rollout_model_feedback).  The chains rolloutBatch(comps, ext, fb, ...) runs in one launch; the
+  // workspace query answers 0.
+  size_t rolloutWorkspaceBytes(const rdyn_rollout_desc& desc, const rdyn_ext_wrenches* ext, const rdyn_feedback& fb, const rdyn_model_feedback& mfb,
+                               int64_t n_samples, int64_t chunk_samples = 0) const
+  {
+    return rdyn_rollout_model_feedback_workspace_bytes(m_h, &desc, ext, &fb, &mfb, n_samples, chunk_samples);
+  }
+  void rolloutBatch(const std::vector<rdyn_component>& comps, const rdyn_ext_wrenches* ext, const rdyn_feedback& fb, const rdyn_model_feedback& mfb,
+                    const rdyn_batch& b, const rdyn_rollout_desc& desc, int64_t chunk_samples, void* workspace, size_t workspace_bytes) const
+  {
+    chk(rdyn_rollout_model_feedback(m_h, &b, &desc, comps.empty() ? nullptr : comps.data(), (int)comps.size(), ext, &fb, &mfb, chunk_samples,
+                                    workspace, workspace_bytes));
+  }
   // adjoint of a rollout of a batch (b.q, b.dq = the forward call's initial state; every pointer of desc a device pointer in the layout of
   // b.q; comps may be empty): the gradients with respect to the initial state and the torques from the seeds on the end state and on the
   // trajectory records, both integrators: rdyn_rollout_adjoint

@@ -1,4 +1,5 @@
-"""The joint-space PD feedback law of a closed-loop rollout (include/rdyn.h: rdyn_feedback, rdyn_rollout_feedback)."""
+"""The feedback laws of a closed-loop rollout: the joint-space PD law (include/rdyn.h: rdyn_feedback, rdyn_rollout_feedback) and the
+model-based laws around it (rdyn_model_feedback, rdyn_rollout_model_feedback)."""
 
 
 class Feedback(object):
@@ -16,3 +17,23 @@ class Feedback(object):
     def __init__(self, q_ref, kp, kd=None, Dq_ref=None, hold=True, tau_limit=None, command_trajectory=False):
         self.q_ref, self.Dq_ref, self.kp, self.kd = q_ref, Dq_ref, kp, kd
         self.hold, self.tau_limit, self.command_trajectory = bool(hold), tau_limit, bool(command_trajectory)
+
+
+class ModelFeedback(Feedback):
+    """A model-based law, as Chain.rollout(feedback=) applies it: the controller's own model of the arm inside the loop.
+    model: a Chain with the plant's joints and input joints -- Chain.withParameters makes "the same arm with other inertial parameters";
+    it may be the plant itself.  RNEA_m below is model.getJointTorque.
+    law: "computed_torque": a = DDq_ref + kp (q_ref - q) + kd (Dq_ref - Dq), u = tau + RNEA_m(q, Dq, a), clamped (kp in 1/s^2, kd in
+    1/s); "gravity_compensation": u = tau + kp (q_ref - q) + kd (Dq_ref - Dq) + RNEA_m(q, 0, 0), clamped.
+    DDq_ref: computed torque only; shaped like q_ref (per step, or a constant record), None: zero.
+    Everything else is Feedback's.  Reverse mode is not served yet: Chain.rolloutAdjoint and rosdyn_amd.autograd raise."""
+
+    LAWS = ("computed_torque", "gravity_compensation")
+
+    def __init__(self, model, law, q_ref, kp, kd=None, Dq_ref=None, DDq_ref=None, hold=True, tau_limit=None, command_trajectory=False):
+        if law not in self.LAWS:
+            raise ValueError("unknown law %r: one of %s" % (law, ", ".join(self.LAWS)))
+        if DDq_ref is not None and law != "computed_torque":
+            raise ValueError("DDq_ref belongs to the computed-torque law")
+        Feedback.__init__(self, q_ref, kp, kd, Dq_ref, hold=hold, tau_limit=tau_limit, command_trajectory=command_trajectory)
+        self.model, self.law, self.DDq_ref = model, law, DDq_ref
